@@ -53,7 +53,13 @@ def parse():
     ap.add_argument("--native-collective", action="store_true",
                     help="also aggregate the counters through the C ABI's own collective (lbft_batch_counters_allgather_reduce: ncclAllGather on a "
                          "communicator built with ncclCommInitRank, one device per rank) and check it against the torch.distributed aggregate")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy (float64, at most 64 MB; "
+                         "N > 1: rank 0's shard), so that two builds can be compared output for output on the same seeded inputs")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def self_launch(args):
@@ -84,7 +90,12 @@ def traffic_measured_here(argv):
         return {"error": "rocprofv3 not found"}
     if os.environ.get("LBFT_BENCH_CHILD"):  # (a child of this very function never profiles again, whatever its command line says)
         return {"error": "nested --measure-traffic refused"}
-    child = [sys.executable, os.path.abspath(__file__)] + [a for a in argv if a != "--measure-traffic"] + ["--no-cpu-baseline", "--parity-instances", "0", "--no-measure-traffic"]
+    argv = list(argv)
+    if "--dump-outputs" in argv:  # (the profiled children write no outputs: only the parent's run is the one to compare)
+        k = argv.index("--dump-outputs")
+        del argv[k:k + 2]
+    argv = [a for a in argv if a != "--measure-traffic" and not a.startswith("--dump-outputs=")]
+    child = [sys.executable, os.path.abspath(__file__)] + argv + ["--no-cpu-baseline", "--parity-instances", "0", "--no-measure-traffic"]
     vals = {}
     for counter in ("FETCH_SIZE", "WRITE_SIZE"):
         d = tempfile.mkdtemp(prefix="lbft_pmc_", dir="/tmp")
@@ -286,6 +297,51 @@ def parity_gate(args, sim, res, seeds, nodes, max_clock):
             "oracle_seconds": dt, "oracle": "oracle/lbft_oracle.cpp, math_mode 1"}
 
 
+DUMP_NODE_BYTES = 48 << 20  # per-node arrays: every instance while they fit, else a fixed seeded sample of instances
+DUMP_HISTORY_BYTES = 12 << 20  # committed histories: a fixed seeded sample of at most 1 024 instances, the first 64 commits per node
+DUMP_HISTORY_CAP = 64
+
+
+def dump_outputs(path, res):
+    """--dump-outputs DIR: what the last timed step handed its caller (the BatchResult of loop_until), written after the timed region as
+    DIR/<name>.npy, all float64 and at most 64 MB, so that two builds of the project can be compared output for output.  The u64 State
+    hashes are split into 32-bit halves (exact in float64).  `instances` / `history_instances` name the instances of the batch each array
+    covers (samples are drawn with fixed seeds, so the same arguments give the same sample).  `counters` = events[0..3], rounds, commits,
+    rng_draws, faulted_instances of the whole batch."""
+    import numpy as np
+    from librabft_simulator_amd._lib import COMMIT_DTYPE
+    cc = res.commit_counts
+    n, nodes = cc.shape
+    states = res.last_committed_states
+    per_node = {"commit_counts": cc, "active_rounds": res.active_rounds, "last_committed_states_hi": states >> np.uint64(32),
+                "last_committed_states_lo": states & np.uint64(0xFFFFFFFF), "startup_times": res.startup_times, "epochs": res.epochs}
+    row_bytes = 8 * (nodes * len(per_node) + 2)  # + the instance's index and fault word
+    rows = np.arange(n)
+    if n * row_bytes > DUMP_NODE_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n, DUMP_NODE_BYTES // row_bytes, replace=False))
+    out = {"instances": rows, "faults": res.faults[rows]}
+    out.update({k: v[rows] for k, v in per_node.items()})
+    k = min(n, 1024, DUMP_HISTORY_BYTES // (nodes * DUMP_HISTORY_CAP * 3 * 8))
+    hrows = np.sort(np.random.default_rng(1).choice(n, k, replace=False))
+    hist = np.zeros((k, nodes, DUMP_HISTORY_CAP), dtype=COMMIT_DTYPE)
+    for i, inst in enumerate(hrows):
+        for node in range(nodes):
+            h = res.committed_history(int(inst), node)[:DUMP_HISTORY_CAP]
+            hist[i, node, :len(h)] = h
+    out["history_instances"] = hrows
+    for field in hist.dtype.names:
+        out["committed_history_" + field] = hist[field]
+    c = res.counters
+    out["counters"] = np.array(list(c["events"]) + [c["rounds"], c["commits"], c["rng_draws"], c["faulted_instances"]])
+    out = {name: np.ascontiguousarray(a, dtype=np.float64) for name, a in out.items()}
+    total = sum(a.nbytes for a in out.values())
+    assert total <= 64 << 20, total
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {"dir": path, "arrays": len(out), "bytes": total}
+
+
 def run_kernel_name(kc):
     """The run kernel a batch executes, from lbft_batch_layout's flag word (include/lbft.h)."""
     cls = kc & 255
@@ -467,6 +523,8 @@ def main():
             out["parity"] = parity_gate(args, sim, res, seeds, args.nodes, args.max_clock)
         if not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args, args.nodes, args.max_clock)
+        if args.dump_outputs:  # (rank 0's shard of the timed batch, as its last timed step left it)
+            out["dumped_outputs"] = dump_outputs(args.dump_outputs, res)
         print(json.dumps(out))
         if out["roofline"]["executed_le_traffic"] is False:  # the "algorithmic" bytes must be a lower bound of what crosses the L2 boundary
             sys.stderr.write("bench.py: executed algorithmic bytes %.2f GB exceed the measured traffic %.2f GB\n" % (ex_bytes / 1e9, out["roofline"]["traffic"]))
