@@ -128,6 +128,27 @@ typedef struct lbft_batch lbft_batch;
  * the device here; nothing else crosses PCIe until results are read back. */
 int lbft_batch_create(const lbft_config* cfg, const uint64_t* seeds, size_t n_instances, int device, lbft_batch** out);
 
+/* Parameter sets: one batch whose instances run a grid of delay, pacemaker and loss settings (the study variables of the reference's
+ * CLI, librabft-v2/src/main.rs:73-140).  A set holds what varies; everything else -- num_nodes, delay_model, quirks, equivocate_every,
+ * voting_rights, rights_rotation, commands_per_epoch, the capacities (0 = chosen for the most demanding set) -- comes from `base`.
+ * Instance i runs sets[set_of_instance[i]] with seeds[i] and gives exactly what lbft_batch_create gives for `base` with that set's
+ * fields and that seed.  Networks of at most 32 nodes (LBFT_ERR_UNSUPPORTED above).  Every set is validated like a config, and the
+ * arguments (n_sets in 1..LBFT_MAX_PARAM_SETS, every index < n_sets) before any HIP call.  The kernels live in liblbft_paramsets.so
+ * beside this library (LBFT_ERR_UNSUPPORTED when it is missing).  Every run / read-back / checkpoint call works on such a batch;
+ * lbft_batch_save_node / load_node use the instance's own NodeConfig; the node-level interface (lbft_batch_manual_begin, lbft_node_*,
+ * lbft_node_calls) is LBFT_ERR_UNSUPPORTED. */
+typedef struct lbft_param_set {
+  double mean, variance;                   /* delay_model 0 */
+  int64_t uniform_lo, uniform_hi;          /* delay_model 1 */
+  int64_t target_commit_interval, delta;   /* NodeConfig */
+  double gamma, lambda;
+  uint32_t drop_per_million, partition_size; /* lossy network */
+  int64_t partition_start, partition_end;
+} lbft_param_set;
+#define LBFT_MAX_PARAM_SETS 256
+int lbft_batch_create_param_sets(const lbft_config* base, const lbft_param_set* sets, uint32_t n_sets, const uint32_t* set_of_instance,
+                                 const uint64_t* seeds, size_t n_instances, int device, lbft_batch** out);
+
 /* Simulator::loop_until(GlobalTime(max_clock), None) for every instance (simulator.rs:380-475), including
  * the initial scheduling done by Simulator::new.  0 <= max_clock < 2^31 - 1.  May be called again after
  * lbft_batch_reset.  Returns LBFT_ERR_FAULT if any instance faulted (results of the others are valid). */
@@ -223,7 +244,8 @@ size_t lbft_batch_device_bytes(const lbft_batch* b);
  * (lean kernel with the record exchange of quirks bit 0, lbft_k_run2q) << 12 | (small-batch class-0 kernel lbft_k_run0s: the pop's scan
  * of the LDS event queues by all lanes of the wavefront) << 13 | (class-0 kernel with the headline network -- 4 nodes, unit voting rights,
  * log-normal delays -- fixed at compile time, lbft_k_run0q) << 14 | (small-batch kernel with ONE network per wavefront executed as
- * wavefront-uniform code on the scalar unit, lbft_k_run0u -- set together with bit 13) << 15. */
+ * wavefront-uniform code on the scalar unit, lbft_k_run0u -- set together with bit 13) << 15 | (parameter-set batch: lbft_k_ps_run0 /
+ * lbft_k_ps_run1 of liblbft_paramsets.so, bits 10-15 clear) << 16. */
 int lbft_batch_layout(const lbft_batch* b, uint32_t* out);
 /* Events processed per run-kernel launch (0 = whole simulation in one launch). */
 int lbft_batch_set_max_steps(lbft_batch* b, uint32_t max_steps);

@@ -6,7 +6,7 @@ the C ABI), the ctypes binding and the host-side mirror of the reference's simul
 """
 from ._lib import LbftError, lib  # noqa: F401
 from .simulator import (BatchResult, BatchSimulator, Command, Duration, GlobalTime, NodeConfig, NodeTime,  # noqa: F401
-                        RandomDelay, Simulator, State)
+                        ParamSet, RandomDelay, Simulator, State)
 
-__all__ = ["BatchSimulator", "BatchResult", "Simulator", "RandomDelay", "NodeConfig", "GlobalTime", "NodeTime", "Duration", "State",
+__all__ = ["BatchSimulator", "BatchResult", "ParamSet", "Simulator", "RandomDelay", "NodeConfig", "GlobalTime", "NodeTime", "Duration", "State",
            "Command", "LbftError", "lib"]

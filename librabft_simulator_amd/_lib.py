@@ -52,6 +52,27 @@ class LbftConfig(C.Structure):
     ]
 
 
+class LbftParamSet(C.Structure):
+    """lbft_param_set: what one parameter set of a batch varies (include/lbft.h)."""
+    _fields_ = [
+        ("mean", C.c_double),
+        ("variance", C.c_double),
+        ("uniform_lo", C.c_int64),
+        ("uniform_hi", C.c_int64),
+        ("target_commit_interval", C.c_int64),
+        ("delta", C.c_int64),
+        ("gamma", C.c_double),
+        ("lambda_", C.c_double),
+        ("drop_per_million", C.c_uint32),
+        ("partition_size", C.c_uint32),
+        ("partition_start", C.c_int64),
+        ("partition_end", C.c_int64),
+    ]
+
+
+MAX_PARAM_SETS = 256  # LBFT_MAX_PARAM_SETS
+
+
 class LbftCounters(C.Structure):
     _fields_ = [
         ("events", C.c_uint64 * 4),
@@ -115,7 +136,7 @@ RECORD_HASH_DTYPE = np.dtype([("block_hash", "<u8"), ("state", "<u8"), ("qc_hash
 
 # every symbol include/lbft.h declares (tests check that the library exports all of them)
 ABI_SYMBOLS = [
-    "lbft_batch_create", "lbft_batch_run_until", "lbft_batch_reset", "lbft_batch_commit_counts",
+    "lbft_batch_create", "lbft_batch_create_param_sets", "lbft_batch_run_until", "lbft_batch_reset", "lbft_batch_commit_counts",
     "lbft_batch_active_rounds", "lbft_batch_committed_history", "lbft_batch_committed_histories", "lbft_batch_committed_record_hashes",
     "lbft_batch_last_committed_states", "lbft_batch_last_committed_state", "lbft_batch_save_node", "lbft_batch_load_node", "lbft_batch_startup_times", "lbft_batch_epochs", "lbft_batch_counters",
     "lbft_batch_faults", "lbft_batch_destroy", "lbft_batch_stream", "lbft_batch_last_run_ms",
@@ -224,6 +245,8 @@ def lib():
     vp = C.c_void_p
     L.lbft_batch_create.argtypes = [C.POINTER(LbftConfig), vp, C.c_size_t, C.c_int, C.POINTER(vp)]
     L.lbft_batch_create.restype = C.c_int
+    L.lbft_batch_create_param_sets.argtypes = [C.POINTER(LbftConfig), C.POINTER(LbftParamSet), C.c_uint32, vp, vp, C.c_size_t, C.c_int, C.POINTER(vp)]
+    L.lbft_batch_create_param_sets.restype = C.c_int
     L.lbft_batch_run_until.argtypes = [vp, C.c_int64]
     L.lbft_batch_run_until.restype = C.c_int
     L.lbft_batch_reset.argtypes = [vp]

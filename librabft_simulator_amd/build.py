@@ -1,7 +1,8 @@
-"""Build liblbft_hip.so (hand-written HIP for gfx950) in-tree with hipcc.
+"""Build liblbft_hip.so and liblbft_paramsets.so (hand-written HIP for gfx950) in-tree with hipcc.
 
-`python -m librabft_simulator_amd.build` or `build()`; the .so is git-ignored but travels to the GPU
-box with the gpurun snapshot.
+`python -m librabft_simulator_amd.build` or `build()`; the libraries are git-ignored build products.
+liblbft_paramsets.so holds the kernels of parameter-set batches (lbft_batch_create_param_sets); liblbft_hip.so
+opens it beside itself on first use, so that its own code object stays as it is.
 """
 import os
 import shutil
@@ -9,9 +10,14 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc", "lbft_hip.hip")
-DEPS = [SRC] + [os.path.join(HERE, "csrc", f) for f in ("lbft_core.h", "lbft_math.h", "lbft_tables.h", "lbft_save_node.h")] + [
+DEPS = [SRC] + [os.path.join(HERE, "csrc", f) for f in ("lbft_core.h", "lbft_math.h", "lbft_tables.h", "lbft_save_node.h", "lbft_launch.h",
+                                                         "lbft_paramsets.h")] + [
     os.path.join(HERE, "..", "include", "lbft.h")]
 OUT = os.path.join(HERE, "liblbft_hip.so")
+PS_SRC = os.path.join(HERE, "csrc", "lbft_paramsets.hip")
+PS_DEPS = [PS_SRC] + [os.path.join(HERE, "csrc", f) for f in ("lbft_core.h", "lbft_math.h", "lbft_launch.h", "lbft_paramsets.h")] + [
+    os.path.join(HERE, "..", "include", "lbft.h")]
+PS_OUT = os.path.join(HERE, "liblbft_paramsets.so")
 
 # -ffp-contract=off: Rust never fuses; every fused multiply-add in lbft_math.h is explicit.
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wno-unused-value"]
@@ -78,20 +84,29 @@ def source_hash():
     return kernel_hash()
 
 
-def is_stale():
-    if not os.path.exists(OUT):
+def _stale(out, deps):
+    if not os.path.exists(out):
         return True
-    t = os.path.getmtime(OUT)
-    return any(os.path.getmtime(d) > t for d in DEPS)
+    t = os.path.getmtime(out)
+    return any(os.path.getmtime(d) > t for d in deps)
+
+
+def is_stale():
+    return _stale(OUT, DEPS) or _stale(PS_OUT, PS_DEPS)
 
 
 def build(force=False, verbose=False):
-    if not force and not is_stale():
-        return OUT
-    cmd = [hipcc_path()] + HIPCC_FLAGS + [SRC, "-o", OUT]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.check_call(cmd)
+    """Both libraries, each with exactly HIPCC_FLAGS (the two compile in parallel)."""
+    jobs = [(src, out) for src, out, deps in ((SRC, OUT, DEPS), (PS_SRC, PS_OUT, PS_DEPS)) if force or _stale(out, deps)]
+    procs = []
+    for src, out in jobs:
+        cmd = [hipcc_path()] + HIPCC_FLAGS + [src, "-o", out]
+        if verbose:
+            print(" ".join(cmd))
+        procs.append((cmd, subprocess.Popen(cmd)))
+    failed = [cmd for cmd, proc in procs if proc.wait() != 0]
+    if failed:
+        raise subprocess.CalledProcessError(1, failed[0])
     return OUT
 
 

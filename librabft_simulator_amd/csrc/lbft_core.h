@@ -703,6 +703,24 @@ enum KernelClass : int {
   K_HEADLINE = 9,        // lbft_k_run0q: K_SMALL with the headline network (4 nodes, unit rights, log-normal delays) fixed at compile time (sim_quad)
   K_SMALL_UNIFORM = 12   // lbft_k_run0u: K_SMALL_WAVE_POP for ONE network per wavefront, wavefront-uniform code on the scalar unit
 };
+// Parameter-set batches (lbft_batch_create_param_sets, liblbft_paramsets.so): the flag added to a class above gives the same step with the
+// delay, pacemaker and loss parameters read from the lane's own set (SimTSets, LBFT_SET) instead of the batch-wide Params.
+enum : int { K_PARAM_SETS = 32, K_SMALL_SETS = K_SMALL | K_PARAM_SETS, K_MID_SETS = K_MID | K_PARAM_SETS, K_GENERIC_SETS = K_GENERIC | K_PARAM_SETS };
+// One parameter set as the device reads it: what fill_params derives from a config's delay / NodeConfig / loss fields, and the set's own
+// duration table (delta * k^gamma, host libm).  Built on the host (lbft_hip.hip), loaded once per lane at kernel entry (SimTSets::load_set).
+struct ParamSetDev {
+  double mu, sigma;
+  i64 uni_lo;
+  u64 uni_span;
+  i64 tci;
+  double lambda;
+  const i64* dur_tab;
+  u32 drop_ppm, part_size;
+  i32 part_start, part_end;
+};
+// The step of a K_PARAM_SETS class runs on a SimTSets (below): SimT plus the lane's set.  The plain classes' SimT carries no trace of it
+// (no base, no member: a base class, even an empty one, changed the machine code of lbft_k_run2l).
+template <int KCLS> struct SimTSets;
 // ------------------------------------------------------------------------------------------------
 // One simulated network: `tile` is the instance's tile, `lane4` the byte offset of its column in a row.
 // ------------------------------------------------------------------------------------------------
@@ -715,8 +733,10 @@ enum KernelClass : int {
 // sim_class() picks the class a batch runs with.
 //   5  class 2 without the record exchange of quirks bit 0, the round-switch trace and the lossy network (sim_lean()): the
 //      plain large-network path fits 256 registers (21 spilled) and runs two wavefronts per SIMD with half the lanes each
-template <int CLS>
+template <int KCLS>
 struct SimT {
+  static constexpr int CLS = KCLS & ~K_PARAM_SETS;            // the class whose step this is
+  static constexpr bool PSET = (KCLS & K_PARAM_SETS) != 0;    // ... with the lane's own parameter set (LBFT_SET below)
   static constexpr bool LEAN2 = CLS == K_LARGE_LEAN || CLS == K_LARGE_EXCHANGE;  // 7 = 5 plus the record exchange of quirks bit 0 (24 spilled registers; a kernel of its own: with
                                                        // that code compiled in, the runs without it lose 10 %)
   static constexpr bool BIG = CLS == K_LARGE || LEAN2;       // multi-word node / author sets
@@ -778,6 +798,11 @@ struct SimT {
   LBFT_HD u32 DMODEL() const { return QUAD ? 0u : P.delay_model; }
   LBFT_HD u32 QUORUM() const { return QUAD ? 3u : P.quorum; }
   LBFT_HD u32 ROT() const { return QUAD ? 0u : P.rot; }
+  // The parameters a parameter set varies, read as LBFT_SET(mu) etc.: the lane's set in the K_PARAM_SETS classes, the batch's Params
+  // otherwise.  (A macro, not accessor functions: in the plain classes the expression is the former `P.mu` itself -- accessor calls, even
+  // inlined ones, changed the machine code of lbft_k_run2l.)
+#define LBFT_SET(f) (PSET ? sets_self()->ls.f : P.f)
+  LBFT_HD const SimTSets<KCLS>* sets_self() const { return static_cast<const SimTSets<KCLS>*>(this); }
   static constexpr bool C0I = C0 && LBFT_C0_IMAJOR != 0;
   static constexpr bool TILE64 = (C0 && !C0I) || CLS == K_MID || CLS == K_MID_LEAN;
   static constexpr bool HCREG = CLS == K_HEADLINE && C0I && LBFT_C0_HCREG != 0;  // (lbft_k_run0q: 18.7 -> 18.1 ms; no gain in the generic class-0 kernels)
@@ -1313,9 +1338,9 @@ struct SimT {
     return f64_to_i64_sat(wuni(lbft_exp(y, exp_tab)));
   }
   LBFT_HD i64 sample_delay() {
-    if (DMODEL() == 1) return P.uni_lo + (i64)rng.gen_range_u64(P.uni_span);
+    if (DMODEL() == 1) return LBFT_SET(uni_lo) + (i64)rng.gen_range_u64(LBFT_SET(uni_span));
     double nrm = standard_normal();
-    return trunc_exp(P.mu + P.sigma * nrm);
+    return trunc_exp(LBFT_SET(mu) + LBFT_SET(sigma) * nrm);
   }
 
   // ---- event queue: unsorted compact array, ordered by (time asc, kind desc, stamp asc)
@@ -1724,12 +1749,12 @@ LBFT_UNROLL
   }
 
   // extension "lossy network": called right after a message's delay draw; true = the message is lost
-  LBFT_HD bool lossy() const { return !C0 && !LEAN && (P.drop_ppm | P.part_size) != 0; }
+  LBFT_HD bool lossy() const { return !C0 && !LEAN && (LBFT_SET(drop_ppm) | LBFT_SET(part_size)) != 0; }
   LBFT_HD bool net_lost(u32 a, u32 b) {
     if (!lossy()) return false;
     bool lost = false;
-    if (P.drop_ppm) { u64 d = rng.next_u64(); lost = mulhi64(d, 1000000ULL) < (u64)P.drop_ppm; }
-    if (P.part_size && clock >= P.part_start && clock < P.part_end && ((a < P.part_size) != (b < P.part_size))) lost = true;
+    if (LBFT_SET(drop_ppm)) { u64 d = rng.next_u64(); lost = mulhi64(d, 1000000ULL) < (u64)LBFT_SET(drop_ppm); }
+    if (LBFT_SET(part_size) && clock >= LBFT_SET(part_start) && clock < LBFT_SET(part_end) && ((a < LBFT_SET(part_size)) != (b < LBFT_SET(part_size)))) lost = true;
     return lost;
   }
   LBFT_HD bool is_equivocator(u32 node) const { return !C0 && P.equiv != 0 && node % P.equiv == 0; }  // class 0: all honest
@@ -2058,6 +2083,7 @@ LBFT_UNROLL
       if (LBFT_LIKELY(k < dur_lds_len)) return dur_lds[k];
       return P.dur_tab[k];
     }
+    if constexpr (PSET) return sets_self()->ls.dur_tab[k];  // the lane's set's table (L2-resident; the LDS copy holds the batch's)
     const i64* tab = k < dur_lds_len ? dur_lds : P.dur_tab;  // (a selected pointer: see leader())
     return (i64)wuni((u64)tab[k]);
   }
@@ -2096,7 +2122,7 @@ LBFT_UNROLL
       if (lclock >= deadline) { a.create_timeout = true; a.timeout_round = ar; a.broadcast = true; }
       else if (deadline < a.next) a.next = deadline;
     } else {
-      i64 period = f64_to_i64_sat(P.lambda * (double)dur);
+      i64 period = f64_to_i64_sat(LBFT_SET(lambda) * (double)dur);
       i64 qd = (i64)((u64)lqat + (u64)period);
       if (lclock >= qd) { a.query_all = true; qd = (i64)((u64)lclock + (u64)period); }
       if (qd < a.next) a.next = qd;
@@ -2121,9 +2147,9 @@ LBFT_UNROLL
         nfs(node, NF_TR_LCT, (u32)(i32)lclock);
       }
     }
-    i64 deadline = (i64)((u64)(lct > lqat ? lct : lqat) + (u64)P.tci);
+    i64 deadline = (i64)((u64)(lct > lqat ? lct : lqat) + (u64)LBFT_SET(tci));
     query_all = false;
-    if (lclock >= deadline) { query_all = true; deadline = (i64)((u64)lclock + (u64)P.tci); }
+    if (lclock >= deadline) { query_all = true; deadline = (i64)((u64)lclock + (u64)LBFT_SET(tci)); }
     next = deadline;
   }
 
@@ -2368,13 +2394,13 @@ LBFT_UNROLL
     const bool has_timeout = (ar == nf(node, NF_CUR_ROUND)) && am_test(node, NF_TO_MASK, node);
     i64 nx;
     if (!has_timeout) nx = (i64)((u64)start + (u64)dur);
-    else nx = (i64)((u64)lqat + (u64)f64_to_i64_sat(P.lambda * (double)dur));
+    else nx = (i64)((u64)lqat + (u64)f64_to_i64_sat(LBFT_SET(lambda) * (double)dur));
     ok = ok && lclock < nx;
     ok = ok && !(pb != 0 && nf(node, NF_CUR_ROUND) > nf(node, NF_LVR));
     ok = ok && (nf(node, NF_ELECTION) & 0xffu) != 1u;
     ok = ok && epoch <= nf(node, NF_TR_EPOCH) && nf(node, NF_HC_ROUND) <= nf(node, NF_TR_HCR);
     const i64 lct = (i64)(i32)nf(node, NF_TR_LCT);
-    const i64 dl = (i64)((u64)(lct > lqat ? lct : lqat) + (u64)P.tci);
+    const i64 dl = (i64)((u64)(lct > lqat ? lct : lqat) + (u64)LBFT_SET(tci));
     ok = ok && lclock < dl;
     next = dl < nx ? dl : nx;
     return ok;
@@ -3781,15 +3807,15 @@ LBFT_UNROLL
   // the first try of sample_delay() on the draw `bits`: true = accepted (then d is the delay sample_delay() returns)
   LBFT_HD bool fast_delay(u64 bits, i64& d) const {
     if (DMODEL() == 1) {
-      u64 zone = (P.uni_span << clz64(P.uni_span)) - 1;
-      d = P.uni_lo + (i64)mulhi64(bits, P.uni_span);
-      return bits * P.uni_span <= zone;
+      u64 zone = (LBFT_SET(uni_span) << clz64(LBFT_SET(uni_span))) - 1;
+      d = LBFT_SET(uni_lo) + (i64)mulhi64(bits, LBFT_SET(uni_span));
+      return bits * LBFT_SET(uni_span) <= zone;
     }
     u32 i = (u32)(bits & 0xff);
     double u = lbft_asdouble((1024ULL << 52) | (bits >> 12)) - 3.0;
     double x = u * lbft_asdouble(zig_x[i]);
     double ax = x < 0.0 ? -x : x;
-    d = trunc_exp(P.mu + P.sigma * x);
+    d = trunc_exp(LBFT_SET(mu) + LBFT_SET(sigma) * x);
     return ax < lbft_asdouble(zig_x[i + 1]);
   }
   LBFT_HD u32 horizon_time(i32 clk, i64 d) const {  // clock + delay, 0xffffffff = past max_clock (never queued)
@@ -4425,6 +4451,13 @@ LBFT_UNROLL
 };
 
 typedef SimT<K_GENERIC> Sim;
+// SimT of a K_PARAM_SETS class with the lane's parameter set, loaded once at kernel entry (load_set)
+template <int KCLS>
+struct SimTSets : SimT<KCLS> {  // (SimT names it for every class -- LBFT_SET's untaken branch -- but only K_PARAM_SETS classes construct one)
+  ParamSetDev ls;
+  using SimT<KCLS>::SimT;
+  LBFT_HD void load_set(const ParamSetDev& s) { ls = s; }
+};
 // The class lbft_k_run (and the host model) executes a batch with.
 inline int sim_class(const Params& p) {
   if (p.n > 32) return K_LARGE;

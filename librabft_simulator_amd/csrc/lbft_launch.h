@@ -1,0 +1,58 @@
+// lbft_launch.h -- launch geometry and LDS layout of the run kernels, shared by liblbft_hip.so (lbft_hip.hip) and the
+// parameter-set kernels of liblbft_paramsets.so (lbft_paramsets.hip), so that the host code of the first sizes the LDS of both alike.
+#ifndef LBFT_LAUNCH_H
+#define LBFT_LAUNCH_H
+#define LBFT_BLOCK 64  // one wavefront per workgroup: wavefronts retire independently
+
+// Simulator::loop_until for every instance (simulator.rs:380-475).
+//
+// Workgroup = LBFT_RUN_WAVES (8) wavefronts = both wavefront slots of a CU's four SIMDs (256 registers per lane: two per SIMD);
+// wavefront w of workgroup g advances instances [(g * 8 + w) * lpw, +lpw).  LDS (dynamic, up to the CU's whole 160 KiB):
+//   [zig_x 257][zig_f 257][exp_tab 256]  u64   read-only tables of the delay sampler, one copy per workgroup
+//   [dur 128] i64, [leader 1024] u8            pacemaker duration / leader tables (first rounds)
+//   keys  [wave][slot][lane]              u64   event-queue keys, lane-private columns: class 0 one packed word per event
+//                                               (time | 3-kind | stamp | node | sender | slot), other classes (time, 3-kind, stamp)
+//   metas [wave][slot][lane]              u32   classes 1-2 only: (node, sender, snapshot slot)
+//   [diagnostic phase counters], then      --   n > 16: one 128-byte receiver list per instance; class 0 with n <= 4: the nodes'
+//                                               hcbr buffers, 32 words per instance ([wave][word][lane])
+// A lane only ever touches its own column (address = slot * lpw + lane), so data-dependent slot
+// indices are bank-conflict free and no workgroup barrier is needed after the table fill.
+// (round 3: 8 instead of 4.  Equal for every batch that fills the chip -- 65 536 x 4: 21.61 vs 21.67 ms, 32 768: 18.4 vs 18.6, 16 384: 15.7 vs
+// 15.5 -- but a batch of <= 1 024 networks then packs two wavefronts on every SIMD of half the CUs instead of one on each SIMD of all
+// of them, and a wavefront that shares its SIMD runs FASTER per step (phase timers, one network per wavefront: 13.2 k cycles per step
+// with a partner, 17.3 k alone): 1 024 x 4 nodes 9.8 -> 7.0 ms.)
+#ifndef LBFT_RUN_WAVES
+#define LBFT_RUN_WAVES 8
+#endif
+#define LBFT_RUN_BLOCK (64 * LBFT_RUN_WAVES)
+#define LBFT_RUN_WAVES_FULL 4  // the kernels that use the whole register file (lbft_k_run<1>, <2>): one wavefront per SIMD = 4 per workgroup
+                               // (a 512-thread launch bound would cap them at 256 registers)
+#define LBFT_LDS_HCBR_WORDS 32  // class 0, n <= 4: hcbr[node][2][4] per instance
+#ifndef LBFT_PACKED_QL_MAX
+#define LBFT_PACKED_QL_MAX 64  // LDS slots per instance of the packed (class 0) queue: the 4-node bench workload peaks at 53 pending events
+#endif
+#define LBFT_LDS_LEADERS 1024  // rounds of the leader table kept in LDS (bytes)
+#define LBFT_LDS_DURS 128      // entries of the duration table kept in LDS (i64)
+#define LBFT_LDS_WEIGHTS LBFT_MAX_NODES  // voting rights (u32)
+#define LBFT_TABLE_U64 (257 + 257 + 256 + LBFT_LDS_DURS + LBFT_LDS_LEADERS / 8 + LBFT_LDS_WEIGHTS / 2)
+
+// [tables][queue keys][queue metas][diagnostics: LBFT_NPHASES u64 per wavefront][n > 16: one 128-byte receiver list per instance]
+// `slot_bytes`: 12 (key + meta) or 8 (packed one-word entries, kernel class 0)
+// `hcbr_lds`: class 0 with networks of <= 4 nodes keeps the nodes' hcbr buffers in LDS -- except lbft_k_run0q, which carries them in
+// registers with the node burst (LBFT_C0_HCREG)
+// the LDS window of block records of the large-network kernels (SimT::attach_blk_window): `entries` records + tags per network
+static inline size_t blk_window_bytes(u32 entries, u32 lpw, u32 nwaves) { return (size_t)nwaves * lpw * entries * (1u + BC_WORDS) * 4u; }
+static inline size_t run_lds_bytes(u32 ql, u32 lpw, u32 n, u32 slot_bytes, u32 nwaves, bool hcbr_lds = true) {
+  return (size_t)LBFT_TABLE_U64 * 8 + (size_t)nwaves * ql * lpw * slot_bytes + (size_t)nwaves * LBFT_NPHASES * 8 + 8 +
+         (n > 16 ? (size_t)nwaves * lpw * LBFT_MAX_NODES : 0) +
+         (n <= 4 && slot_bytes == 8 && hcbr_lds ? (size_t)nwaves * lpw * LBFT_LDS_HCBR_WORDS * 4 : 0);  // class 0, n <= 4: hcbr buffers
+}
+
+__device__ __forceinline__ size_t run_lds_bytes_dev(u32 ql, u32 lpw, u32 slot_bytes, u32 nwaves) {  // = run_lds_bytes(ql, lpw, 0, ..): where the receiver lists start
+  return (size_t)LBFT_TABLE_U64 * 8 + (size_t)nwaves * ql * lpw * slot_bytes + (size_t)nwaves * LBFT_NPHASES * 8 + 8;
+}
+#ifndef LBFT_RUN_WAVES_PER_SIMD
+#define LBFT_RUN_WAVES_PER_SIMD 2  // register budget of the class-0 run kernel: 512 / 2 = 256 VGPRs + AGPRs per lane (the
+                                   // large-network classes run one 8- or 16-lane wavefront per SIMD and may use all 512)
+#endif
+#endif  // LBFT_LAUNCH_H

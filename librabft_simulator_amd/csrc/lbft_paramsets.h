@@ -1,0 +1,23 @@
+// lbft_paramsets.h -- the interface between liblbft_hip.so and liblbft_paramsets.so (the kernels of parameter-set batches,
+// lbft_batch_create_param_sets).  The second library is a code object of its own so that the machine code of the first stays exactly
+// what it was; liblbft_hip.so opens it on first use (dlopen beside itself) and calls these launchers on the batch's stream.
+#ifndef LBFT_PARAMSETS_H
+#define LBFT_PARAMSETS_H
+
+#include <hip/hip_runtime.h>
+
+#include "lbft_core.h"
+
+#define LBFT_PARAMSETS_LIB "liblbft_paramsets.so"
+
+extern "C" {
+// Simulator::new for every instance with its set's delay parameters (grid = instances / p->lpw workgroups of LBFT_BLOCK lanes).
+// sets: device array of the batch's sets; set_of: device array, set_of[instance] < number of sets.
+typedef hipError_t (*lbft_ps_init_fn)(const lbft::Params* p, lbft::u32* state, const lbft::u64* seeds, const lbft::ParamSetDev* sets,
+                                      const lbft::u8* set_of, lbft::u32 grid, hipStream_t stream);
+// One launch of the run kernel of class `cls` (K_SMALL or K_MID) with the geometry prepare_run chose.
+typedef hipError_t (*lbft_ps_run_fn)(int cls, const lbft::Params* p, lbft::u32* state, lbft::u32* unfinished, const lbft::ParamSetDev* sets,
+                                     const lbft::u8* set_of, lbft::u32 grid, lbft::u32 block, size_t lds_bytes, hipStream_t stream);
+}
+
+#endif  // LBFT_PARAMSETS_H

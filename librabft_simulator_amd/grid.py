@@ -1,0 +1,83 @@
+"""Grid of parameter sets in one batch: ``python -m librabft_simulator_amd.grid``.
+
+Comma lists for the reference's study variables (librabft-v2/src/main.rs:73-140) -- ``--mean``, ``--variance``, ``--delta``, ``--gamma``,
+``--lambda``, ``--target-commit-interval`` -- and ``--drop-per-million``; their cross product is the grid, at most 256 points.  Every point
+runs ``--seeds-per-point`` networks of ``--nodes`` nodes to ``--max-clock``, all points in ONE batch (BatchSimulator.with_param_sets).
+``--assign blocked`` gives point k the instances [k * seeds, (k + 1) * seeds); ``interleaved`` gives it instances k, k + points, ...
+Seeds are first-seed .. first-seed + seeds-per-point - 1 for every point.  Prints one JSON line per grid point.
+"""
+import argparse
+import itertools
+import json
+import sys
+
+import numpy as np
+
+from ._lib import MAX_PARAM_SETS
+from .simulator import BatchSimulator, NodeConfig, ParamSet, RandomDelay
+
+
+def _floats(text):
+    return [float(v) for v in text.split(",") if v.strip()]
+
+
+def _ints(text):
+    return [int(v) for v in text.split(",") if v.strip()]
+
+
+def grid_points(args):
+    """The grid's points in output order (the last option varies fastest)."""
+    keys = ("mean", "variance", "delta", "gamma", "lambda", "target_commit_interval", "drop_per_million")
+    values = (args.mean, args.variance, args.delta, args.gamma, args.lambda_, args.target_commit_interval, args.drop_per_million)
+    return [dict(zip(keys, combo)) for combo in itertools.product(*values)]
+
+
+def set_assignment(points, seeds_per_point, assign):
+    """set_of_instance for `points` points of `seeds_per_point` instances each, and the seed index of every instance."""
+    k = np.arange(points * seeds_per_point)
+    if assign == "blocked":
+        return (k // seeds_per_point).astype(np.uint32), k % seeds_per_point
+    return (k % points).astype(np.uint32), k // points
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m librabft_simulator_amd.grid", description=__doc__.split("\n\n")[0])
+    ap.add_argument("--nodes", type=int, default=4)
+    ap.add_argument("--mean", type=_floats, default=[10.0])
+    ap.add_argument("--variance", type=_floats, default=[4.0])
+    ap.add_argument("--delta", type=_ints, default=[20])
+    ap.add_argument("--gamma", type=_floats, default=[2.0])
+    ap.add_argument("--lambda", dest="lambda_", type=_floats, default=[0.5])
+    ap.add_argument("--target-commit-interval", type=_ints, default=[100000])
+    ap.add_argument("--drop-per-million", type=_ints, default=[0])
+    ap.add_argument("--commands-per-epoch", type=int, default=30000)
+    ap.add_argument("--seeds-per-point", type=int, default=64)
+    ap.add_argument("--first-seed", type=int, default=1)
+    ap.add_argument("--max-clock", type=int, default=1000)
+    ap.add_argument("--assign", choices=("blocked", "interleaved"), default="blocked")
+    ap.add_argument("--device", type=int, default=0)
+    args = ap.parse_args(argv)
+    points = grid_points(args)
+    if not 1 <= len(points) <= MAX_PARAM_SETS:
+        ap.error("the grid has %d points; 1 to %d fit one batch" % (len(points), MAX_PARAM_SETS))
+    if args.seeds_per_point < 1:
+        ap.error("--seeds-per-point must be at least 1")
+    sets = [ParamSet(RandomDelay.new(pt["mean"], pt["variance"]),
+                     NodeConfig(target_commit_interval=pt["target_commit_interval"], delta=pt["delta"], gamma=pt["gamma"], lambda_=pt["lambda"]),
+                     drop_per_million=pt["drop_per_million"]) for pt in points]
+    set_of, seed_index = set_assignment(len(points), args.seeds_per_point, args.assign)
+    seeds = (args.first_seed + seed_index).astype(np.uint64)
+    sim = BatchSimulator.with_param_sets(seeds, args.nodes, sets, set_of, commands_per_epoch=args.commands_per_epoch, device=args.device)
+    try:
+        res = sim.loop_until(args.max_clock, allow_faults=True)
+        for pt, row in zip(points, res.by_param_set()):
+            line = dict(pt, nodes=args.nodes, max_clock=args.max_clock, seeds=args.seeds_per_point, assign=args.assign)
+            line.update(instances=row["instances"], faulted=row["faulted"], commits=row["commits"], rounds=row["rounds"])
+            print(json.dumps(line), flush=True)
+    finally:
+        sim.close()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

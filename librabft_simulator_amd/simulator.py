@@ -85,6 +85,27 @@ class NodeConfig:
         self.lambda_ = float(lambda_)
 
 
+class ParamSet:
+    """One parameter set of a batch (``BatchSimulator.with_param_sets``): the delay, NodeConfig and loss settings its instances run;
+    everything else is the batch's.  ``partition`` = (size of the first side, start, end) as in ``BatchSimulator``."""
+
+    def __init__(self, network_delay=None, node_config=None, drop_per_million=0, partition=None):
+        self.network_delay = network_delay or RandomDelay()
+        self.node_config = node_config or NodeConfig()
+        self.drop_per_million = int(drop_per_million)
+        self.partition = None if partition is None else tuple(int(v) for v in partition)
+
+    def to_struct(self):
+        d, nc = self.network_delay, self.node_config
+        s = _lib.LbftParamSet()
+        s.mean, s.variance, s.uniform_lo, s.uniform_hi = d.mean, d.variance, d.lo, d.hi
+        s.target_commit_interval, s.delta, s.gamma, s.lambda_ = nc.target_commit_interval, nc.delta, nc.gamma, nc.lambda_
+        s.drop_per_million = self.drop_per_million
+        if self.partition is not None:
+            s.partition_size, s.partition_start, s.partition_end = self.partition
+        return s
+
+
 def make_config(num_nodes, network_delay, node_config, commands_per_epoch=30000, voting_rights=None,
                 queue_capacity=0, snapshot_capacity=0, block_capacity=0, log_capacity=0, equivocate_every=0,
                 drop_per_million=0, partition=None, quirks=0, rights_rotation=0):
@@ -248,6 +269,25 @@ class BatchResult:
         rows = [[None if v == lo else int(v) for v in out[r]] for r in range(min(int(mr.value), out.shape[0]))]
         return rows, int(msgs.value)
 
+    def by_param_set(self):
+        """Per parameter set of a ``BatchSimulator.with_param_sets`` batch, in set order: the number of instances, of faulted instances,
+        and mean / min / max over its instances of the commits and of the active round (each instance's minimum over its nodes)."""
+        set_of = getattr(self._sim, "set_of_instance", None)
+        if set_of is None:
+            raise ValueError("by_param_set needs a batch created with BatchSimulator.with_param_sets")
+        commits = self.commit_counts.min(axis=1)
+        rounds = self.active_rounds.min(axis=1)
+        faulted = self.faults != 0
+        out = []
+        for k in range(len(self._sim.param_sets)):
+            sel = set_of == k
+            row = {"set": k, "instances": int(sel.sum()), "faulted": int(faulted[sel].sum())}
+            for name, v in (("commits", commits[sel]), ("rounds", rounds[sel])):
+                row[name] = ({"mean": float(v.mean()), "min": int(v.min()), "max": int(v.max())} if len(v) else
+                             {"mean": None, "min": None, "max": None})
+            out.append(row)
+        return out
+
     def contexts(self, instance=0):
         """The ``Vec<&Context>`` that ``Simulator::loop_until`` returns, for one instance."""
         return [SimulatedContextView(self, instance, n) for n in range(self._sim.num_nodes)]
@@ -276,7 +316,7 @@ class BatchSimulator:
     def __init__(self, rng_seeds, num_nodes, network_delay, node_config=None, commands_per_epoch=30000,
                  voting_rights=None, device=0, queue_capacity=0, snapshot_capacity=0, block_capacity=0,
                  log_capacity=0, max_steps_per_launch=0, lanes_per_wavefront=0, lds_queue_slots=-1, equivocate_every=0, drop_per_million=0, partition=None,
-                 calendar_queue=True, quirks=0, rights_rotation=0, keep_retired_stores=False):
+                 calendar_queue=True, quirks=0, rights_rotation=0, keep_retired_stores=False, _param_sets=None, _set_of_instance=None):
         seeds = np.ascontiguousarray(rng_seeds, dtype=np.uint64)
         self.seeds = seeds
         self.num_instances = int(seeds.shape[0])
@@ -286,8 +326,17 @@ class BatchSimulator:
                                 queue_capacity, snapshot_capacity, block_capacity, log_capacity, equivocate_every, drop_per_million, partition, quirks,
                                 rights_rotation)
         self._h = C.c_void_p()
-        check(_lib.lib().lbft_batch_create(C.byref(self._cfg), seeds.ctypes.data, self.num_instances, self.device,
-                                           C.byref(self._h)))
+        if _param_sets is None:
+            check(_lib.lib().lbft_batch_create(C.byref(self._cfg), seeds.ctypes.data, self.num_instances, self.device,
+                                               C.byref(self._h)))
+        else:
+            self.param_sets = list(_param_sets)
+            self.set_of_instance = np.ascontiguousarray(_set_of_instance, dtype=np.uint32)
+            if self.set_of_instance.shape != seeds.shape:
+                raise ValueError("set_of_instance needs one entry per seed")
+            structs = (_lib.LbftParamSet * max(len(self.param_sets), 1))(*[ps.to_struct() for ps in self.param_sets])
+            check(_lib.lib().lbft_batch_create_param_sets(C.byref(self._cfg), structs, len(self.param_sets), self.set_of_instance.ctypes.data,
+                                                          seeds.ctypes.data, self.num_instances, self.device, C.byref(self._h)))
         if max_steps_per_launch:
             check(_lib.lib().lbft_batch_set_max_steps(self._h, max_steps_per_launch))
         if lanes_per_wavefront:
@@ -302,6 +351,24 @@ class BatchSimulator:
     @classmethod
     def new(cls, rng_seeds, num_nodes, network_delay, node_config=None, **kw):
         return cls(rng_seeds, num_nodes, network_delay, node_config, **kw)
+
+    @classmethod
+    def with_param_sets(cls, rng_seeds, num_nodes, param_sets, set_of_instance, **kw):
+        """One batch over a grid of parameter sets (lbft_batch_create_param_sets): instance i runs ``param_sets[set_of_instance[i]]``
+        (a ``ParamSet``) with seed ``rng_seeds[i]`` and gives what a plain batch of that set and seed gives.  ``kw`` as for ``new`` except
+        the per-set ones (network_delay, node_config, drop_per_million, partition); the sets share one delay model.  At most 256 sets
+        and 32 nodes; the node-level interface is not available on such a batch."""
+        param_sets = list(param_sets)
+        for k in ("network_delay", "node_config", "drop_per_million", "partition"):
+            if k in kw:
+                raise TypeError("%s is set per parameter set (ParamSet), not per batch" % k)
+        if not param_sets:
+            raise ValueError("at least one parameter set")
+        models = {ps.network_delay.model for ps in param_sets}
+        if len(models) != 1:
+            raise ValueError("the parameter sets of one batch share one delay model")
+        first = param_sets[0]
+        return cls(rng_seeds, num_nodes, first.network_delay, first.node_config, _param_sets=param_sets, _set_of_instance=set_of_instance, **kw)
 
     def loop_until(self, max_clock, csv_path=None, allow_faults=False, round_trace=None):
         """Simulator::loop_until for every instance.  ``csv_path`` is the reference's ``Option<String>`` data-files

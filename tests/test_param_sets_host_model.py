@@ -1,0 +1,110 @@
+"""Host build of the parameter-set classes against the oracle: mixed-set batches run through lbft_core.h on the CPU
+(tests/param_sets_host_model.cpp, compiled here with g++), each instance equal to the oracle run of its own set's configuration and seed --
+commit counts, active rounds, last states, histories.  Drawn: network sizes, both delay models, delta / gamma / lambda /
+target_commit_interval, loss and partitions (the mid class), equivocators, blocked and interleaved assignment."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SIZES = (3, 4, 7, 16, 20, 32)
+
+
+@pytest.fixture(scope="module")
+def harness(tmp_path_factory):
+    out = str(tmp_path_factory.mktemp("ps_host") / "libps_hostmodel.so")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-pthread", "-w",
+                           os.path.join(ROOT, "tests", "param_sets_host_model.cpp"), "-o", out])
+    L = C.CDLL(out)
+    vp = C.c_void_p
+    L.ps_hostmodel_run.argtypes = [vp, vp, C.c_uint32, vp, vp, C.c_size_t, C.c_int64, C.c_uint32, vp, vp, vp, vp, C.c_size_t, vp]
+    L.ps_hostmodel_run.restype = C.c_int
+    return L
+
+
+def run_host(L, base, sets, set_of, seeds, max_clock, history_cap):
+    from librabft_simulator_amd import _lib
+    m, n = len(seeds), base.num_nodes
+    arr = (_lib.LbftParamSet * len(sets))(*sets)
+    set_of = np.ascontiguousarray(set_of, dtype=np.uint32)
+    seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+    cc = np.zeros((m, n), dtype=np.uint32)
+    ar = np.zeros((m, n), dtype=np.uint64)
+    ls = np.zeros((m, n), dtype=np.uint64)
+    hist = np.zeros((m, n, history_cap), dtype=_lib.COMMIT_DTYPE)
+    faults = np.zeros(m, dtype=np.uint32)
+    cls = L.ps_hostmodel_run(C.byref(base), arr, len(sets), set_of.ctypes.data, seeds.ctypes.data, m, max_clock, 8, cc.ctypes.data,
+                             ar.ctypes.data, ls.ctypes.data, hist.ctypes.data, history_cap, faults.ctypes.data)
+    assert cls >= 0, cls
+    return cls, {"commit_counts": cc, "active_rounds": ar, "last_states": ls, "histories": hist, "faults": faults}
+
+
+def draw_batch(rng, n):
+    """A base config and 3-8 sets for a network of n nodes."""
+    from librabft_simulator_amd import _lib
+    base = _lib.LbftConfig()
+    base.num_nodes = n
+    base.delay_model = int(rng.random() < 0.35)
+    base.commands_per_epoch = 30000
+    lossy = rng.random() < 0.5
+    base.equivocate_every = int(rng.choice([0, 0, 0, 3])) if n >= 4 else 0
+    base.quirks = int(rng.choice([0, 2]))
+    sets = []
+    for _ in range(int(rng.integers(3, 9))):
+        s = _lib.LbftParamSet()
+        s.mean = float(rng.choice([3.0, 5.0, 10.0, 20.0]))
+        s.variance = float(rng.choice([0.0, 1.0, 4.0, 25.0]))
+        s.uniform_lo = int(rng.integers(1, 8))
+        s.uniform_hi = s.uniform_lo + int(rng.integers(0, 20))
+        s.delta = int(rng.choice([5, 10, 20, 40]))
+        s.gamma = float(rng.choice([1.0, 1.5, 2.0]))
+        s.lambda_ = float(rng.choice([0.25, 0.5, 0.75, 1.0]))
+        s.target_commit_interval = int(rng.choice([100000, 100000, 50, 200]))
+        if lossy and rng.random() < 0.7:
+            s.drop_per_million = int(rng.choice([0, 10000, 50000]))
+            if rng.random() < 0.5:
+                s.partition_size = int(rng.integers(1, n))
+                s.partition_start = int(rng.integers(0, 200))
+                s.partition_end = s.partition_start + int(rng.integers(50, 300))
+        sets.append(s)
+    return base, sets
+
+
+def oracle_cfg(oc, base, s):
+    return oc.make_config(num_nodes=base.num_nodes, mean=s.mean, variance=s.variance, delay_model=base.delay_model, uniform_lo=s.uniform_lo,
+                          uniform_hi=s.uniform_hi, commands_per_epoch=base.commands_per_epoch, target_commit_interval=s.target_commit_interval,
+                          delta=s.delta, gamma=s.gamma, lambda_=s.lambda_, quirks=base.quirks, equivocate_every=base.equivocate_every,
+                          drop_per_million=s.drop_per_million, partition_size=s.partition_size, partition_start=s.partition_start,
+                          partition_end=s.partition_end)
+
+
+def test_mixed_set_batches_equal_the_oracle_per_instance(harness, oracle):
+    rng = np.random.default_rng(20261015)
+    configs = compared = 0
+    classes = set()
+    batch = 0
+    while configs < 300:
+        n = SIZES[batch % len(SIZES)]
+        how = "blocked" if batch % 2 == 0 else "interleaved"
+        batch += 1
+        base, sets = draw_batch(rng, n)
+        per = 2
+        k = np.arange(len(sets) * per)
+        set_of = (k // per if how == "blocked" else k % len(sets)).astype(np.uint32)
+        seeds = rng.integers(1, 1 << 40, size=len(set_of)).astype(np.uint64)
+        max_clock = 400 if n <= 16 else 250
+        cls, got = run_host(harness, base, sets, set_of, seeds, max_clock, 32)
+        classes.add(cls)
+        for j, s in enumerate(sets):
+            idx = np.nonzero(set_of == j)[0]
+            ref = oracle.run_batch(oracle_cfg(oracle, base, s), seeds[idx], max_clock, history_cap=32)
+            ok = got["faults"][idx] == 0  # (capacity faults are the device's, not the protocol's: compared where none was raised)
+            for key in ("commit_counts", "active_rounds", "last_states", "histories"):
+                assert (got[key][idx][ok] == ref[key][ok]).all(), (batch, n, how, j, key)
+            compared += int(ok.sum())
+            configs += 1
+    assert classes == {0, 1}, classes  # both the small and the mid class ran
+    assert compared >= 500, compared
