@@ -20,7 +20,7 @@ extern "C" {
 #endif
 
 #define LBFT_OK 0
-#define LBFT_ERR_INVALID (-1)     /* bad argument (NULL pointer, num_nodes out of range, max_clock >= 2^31-1, ...) */
+#define LBFT_ERR_INVALID (-1)     /* bad argument (NULL pointer, num_nodes out of range, max_clock outside [0, LBFT_MAX_CLOCK], ...) */
 #define LBFT_ERR_HIP (-2)         /* HIP runtime error / no device; see lbft_last_error() */
 #define LBFT_ERR_UNSUPPORTED (-3) /* unknown quirks bits or num_nodes > LBFT_MAX_NODES_SUPPORTED on this kernel family */
 #define LBFT_ERR_STATE (-4)       /* call order violated (e.g. results requested before lbft_batch_run_until) */
@@ -28,6 +28,8 @@ extern "C" {
                                      invariant on which the reference itself would have panicked); see lbft_batch_faults */
 
 #define LBFT_MAX_NODES_SUPPORTED 128
+/* The largest horizon lbft_batch_run_until / _run_steps / lbft_batch_manual_begin accept: 2^31 - 3 (clocks are 32-bit on the device). */
+#define LBFT_MAX_CLOCK 0x7ffffffd
 
 /* Per-instance sticky fault bits (lbft_batch_faults). */
 #define LBFT_FAULT_QUEUE_OVERFLOW (1u << 0)
@@ -150,7 +152,7 @@ int lbft_batch_create_param_sets(const lbft_config* base, const lbft_param_set* 
                                  const uint64_t* seeds, size_t n_instances, int device, lbft_batch** out);
 
 /* Simulator::loop_until(GlobalTime(max_clock), None) for every instance (simulator.rs:380-475), including
- * the initial scheduling done by Simulator::new.  0 <= max_clock < 2^31 - 1.  May be called again after
+ * the initial scheduling done by Simulator::new.  0 <= max_clock <= LBFT_MAX_CLOCK (2^31 - 3).  May be called again after
  * lbft_batch_reset.  Returns LBFT_ERR_FAULT if any instance faulted (results of the others are valid). */
 int lbft_batch_run_until(lbft_batch* b, int64_t max_clock);
 

@@ -1221,7 +1221,7 @@ static int zero_calendar(lbft_batch* b) {
 
 // Capacities, HBM layout, launch geometry (shared by lbft_batch_run_until and lbft_batch_manual_begin).
 static int prepare_run(lbft_batch* b, int64_t max_clock) {
-  if (max_clock < 0 || max_clock >= 0x7ffffffeLL) { g_err = "max_clock out of range"; return LBFT_ERR_INVALID; }
+  if (max_clock < 0 || max_clock > LBFT_MAX_CLOCK) { g_err = "max_clock out of range"; return LBFT_ERR_INVALID; }
   HIP_TRY(hipSetDevice(b->device));
   Params& p = b->p;
   const lbft_config& c = b->cfg;

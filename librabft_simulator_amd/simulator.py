@@ -371,7 +371,7 @@ class BatchSimulator:
         return cls(rng_seeds, num_nodes, first.network_delay, first.node_config, _param_sets=param_sets, _set_of_instance=set_of_instance, **kw)
 
     def loop_until(self, max_clock, csv_path=None, allow_faults=False, round_trace=None):
-        """Simulator::loop_until for every instance.  ``csv_path`` is the reference's ``Option<String>`` data-files
+        """Simulator::loop_until for every instance, ``0 <= max_clock <= 2**31 - 3`` (LBFT_MAX_CLOCK; LbftError -1 outside).  ``csv_path`` is the reference's ``Option<String>`` data-files
         directory (bft-lib/src/simulator.rs:380-381, data_writer.rs): when given, the round-switch trace is recorded on
         the device and ``round_switches.txt`` / ``number_of_messages.txt`` of instance 0 are written there in the
         reference's CSV format.  ``round_trace=N`` only records (N rounds per node) for ``BatchResult.round_switches``."""

@@ -8,6 +8,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "../include/lbft.h"
 #include "../librabft_simulator_amd/csrc/lbft_core.h"
 #include "../librabft_simulator_amd/csrc/lbft_save_node.h"
 #include "../librabft_simulator_amd/csrc/lbft_tables.h"
@@ -55,6 +56,7 @@ int lbft_hostmodel_run_batch(const lbft_oracle_config* cfg, const lbft_hostmodel
                              uint32_t* max_rounds /* [inst] */,
                              uint64_t* record_hashes /* [inst][node][hash_cap][4]: SimT::committed_record_hashes, or NULL */, size_t hash_cap) {
   if ((cfg->quirks & ~3u) != 0 || cfg->num_nodes > LBFT_MAX_NODES) return -10;
+  if (max_clock < 0 || max_clock > LBFT_MAX_CLOCK) return -14;  // (lbft_batch_run_until: LBFT_ERR_INVALID)
   Params p;
   memset(&p, 0, sizeof(p));
   p.n = cfg->num_nodes;

@@ -1,0 +1,220 @@
+"""Device tier of the edge-case table (tests/edge_cases.py): BatchSimulator / with_param_sets on the MI355X against the oracle on every case
+-- commit counts, last states, histories, active rounds, startup times, fault words and the events / rng_draws / events_scheduled counters --
+the kernel class and queue discipline each boundary case must select, and the refused horizons.  Plus SimT::trunc_exp at its decision
+boundary through lbft_device_sample_delays: the device's single-precision exp2 estimate and the 2e-6 margin that decides when it is trusted
+are code the host build never runs."""
+import ctypes
+import math
+import os
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import edge_cases as ec  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+
+def amd():
+    import librabft_simulator_amd as m
+    return m
+
+
+def make_sim(case, seeds=None):
+    m = amd()
+    f = dict(mean=10.0, variance=4.0, delay_model=0, uniform_lo=5, uniform_hi=15, target_commit_interval=100000, delta=20, gamma=2.0,
+             lambda_=0.5, quirks=0, drop_per_million=0)
+    f.update(case["cfg"])
+    delay = m.RandomDelay.uniform(f["uniform_lo"], f["uniform_hi"]) if f["delay_model"] == 1 else m.RandomDelay.new(f["mean"], f["variance"])
+    nc = m.NodeConfig(f["target_commit_interval"], f["delta"], f["gamma"], f["lambda_"])
+    seeds = np.array(case["seeds"] if seeds is None else seeds, dtype=np.uint64)
+    return m.BatchSimulator.new(seeds, case["n"], delay, nc, commands_per_epoch=f.get("commands_per_epoch", 30000), quirks=f["quirks"],
+                                drop_per_million=f["drop_per_million"],
+                                calendar_queue=case.get("calendar_queue", True), block_capacity=case.get("block_capacity", 0))
+
+
+def oracle_runs(oracle, case, seeds):
+    cfg = ec.oracle_config(oracle, case)
+    out = []
+    for s in seeds:
+        o = oracle.OracleSim(cfg, int(s)).run_until(case["max_clock"])
+        out.append({"commit_counts": o.commit_counts(), "active_rounds": o.active_rounds(), "last_states": o.last_committed_states(),
+                    "startup_times": o.startup_times(), "histories": [o.committed_history(k) for k in range(case["n"])],
+                    "counters": o.counters()})
+        o.close()
+    return out
+
+
+def assert_instances_equal(res, idx, refs, name):
+    hist = res.committed_histories(max(1, int(res.commit_counts.max())))
+    for i, r in zip(idx, refs):
+        assert list(res.commit_counts[i]) == r["commit_counts"], (name, i)
+        assert list(res.active_rounds[i]) == r["active_rounds"], (name, i)
+        assert list(res.last_committed_states[i]) == r["last_states"], (name, i)
+        assert list(res.startup_times[i]) == r["startup_times"], (name, i)
+        for k, h in enumerate(r["histories"]):
+            assert (hist[i, k, :len(h)] == h).all(), (name, i, k)
+
+
+def sum_counters(refs):
+    return {k: (np.sum([r["counters"][k] for r in refs], axis=0).tolist() if k == "events" else sum(r["counters"][k] for r in refs))
+            for k in ec.COMPARED_COUNTERS}
+
+
+@pytest.mark.parametrize("case", [c for c in ec.CASES if ec.expected(c)[0] != "refused" and not c.get("host_only")], ids=lambda c: c["name"])
+def test_edge_case_device(oracle, case):
+    kind, arg = ec.expected(case)
+    sim = make_sim(case)
+    res = sim.loop_until(case["max_clock"], allow_faults=True)
+    flags = sim.layout()["kernel_class"]
+    if "kernel_class" in case:
+        assert flags & 0xff == case["kernel_class"], (case["name"], hex(flags))
+    if "calendar" in case:
+        assert bool(flags & ec.LAYOUT_CALENDAR) == case["calendar"], (case["name"], hex(flags))
+    # the CPU tier runs the host build with ec.host_caps, a copy of prepare_run's choices: they must be the device's
+    assert (flags & 0xff, (flags >> 8) & 1, (flags >> 9) & 1, (flags >> 11) & 1) == ec.expected_layout(case), (case["name"], hex(flags))
+    if kind == "fault":
+        assert (res.faults == arg).all(), (case["name"], res.faults)
+        return
+    assert (res.faults == 0).all(), (case["name"], res.faults)
+    refs = oracle_runs(oracle, case, case["seeds"])
+    assert_instances_equal(res, range(len(refs)), refs, case["name"])
+    ctr, want = res.counters, sum_counters(refs)
+    assert list(ctr["events"]) == want["events"], (case["name"], ctr["events"], want["events"])
+    assert ctr["rng_draws"] == want["rng_draws"] and ctr["events_scheduled"] == want["events_scheduled"], (case["name"], ctr, want)
+
+
+def test_calendar_limit_on_the_device(oracle):
+    """16 383 on the calendar and 16 383 with the calendar switched off give the same results instance by instance (the table runs each of
+    them, and 16 384 on the heap, against the oracle)."""
+    runs = []
+    for name in ("calendar_last_horizon", "calendar_last_horizon_heap"):
+        case = ec.by_name(name)
+        sim = make_sim(case)
+        res = sim.loop_until(case["max_clock"])
+        runs.append((res.commit_counts.copy(), res.last_committed_states.copy(), res.active_rounds.copy()))
+    for a, b in zip(*runs):
+        assert (a == b).all()
+
+
+@pytest.mark.parametrize("case", [c for c in ec.CASES if ec.expected(c)[0] == "refused"], ids=lambda c: c["name"])
+def test_refused_on_the_device(case):
+    m = amd()
+    _, code = ec.expected(case)
+    if not case["name"].startswith("max_clock"):
+        with pytest.raises(m.LbftError) as e:
+            make_sim(case)
+        assert e.value.code == code
+        return
+    sim = make_sim(case)
+    assert m._lib.lib().lbft_batch_run_until(sim._h, case["max_clock"]) == code
+    assert m._lib.lib().lbft_batch_run_steps(sim._h, case["max_clock"], 0, ctypes.byref(ctypes.c_uint64())) == code
+    res = sim.loop_until(ec.MAX_CLOCK_LIMIT)  # the same batch takes the largest accepted horizon
+    assert (res.faults == 0).all()
+
+
+@pytest.mark.parametrize("case", ec.PARAM_SET_CASES, ids=lambda c: c["name"])
+def test_param_set_edge_batch_device(oracle, case):
+    m = amd()
+    sets = []
+    for k in range(len(case["sets"])):
+        f = ec.set_fields(case, k)
+        delay = m.RandomDelay.uniform(f["uniform_lo"], f["uniform_hi"]) if case["delay_model"] == 1 else m.RandomDelay.new(f["mean"], f["variance"])
+        sets.append(m.ParamSet(delay, m.NodeConfig(f["target_commit_interval"], f["delta"], f["gamma"], f["lambda_"]),
+                               drop_per_million=f["drop_per_million"]))
+    set_of, seeds = ec.set_layout(case)
+    set_of, seeds = np.array(set_of, dtype=np.uint32), np.array(seeds, dtype=np.uint64)
+    sim = m.BatchSimulator.with_param_sets(seeds, case["n"], sets, set_of)
+    res = sim.loop_until(case["max_clock"], allow_faults=True)
+    flags = sim.layout()["kernel_class"]
+    assert flags & (1 << 16) and flags & 0xff == case["kernel_class"], hex(flags)
+    for k in range(len(sets)):
+        idx = np.nonzero(set_of == k)[0]
+        sub = ec.set_as_case(case, k)
+        kind, arg = ec.expected(sub)
+        if kind == "fault":
+            assert (res.faults[idx] == arg).all(), (k, res.faults[idx])
+            continue
+        assert (res.faults[idx] == 0).all(), (k, res.faults[idx])
+        assert_instances_equal(res, idx, oracle_runs(oracle, sub, seeds[idx]), sub["name"])
+
+
+# ---- SimT::trunc_exp at its decision boundary --------------------------------------------------------------------------------------------
+def _boundary_means():
+    """Means for variance-0 samples (every sample is trunc_exp(ln(mean))): integers of every octave up to 2^20 and their float neighbours,
+    means that put exp(y) just inside / just outside the 2e-6 a margin, means in (0, 1), means where |y log2 e| is close to 20."""
+    rng = np.random.default_rng(20261015)
+    ks = set()
+    for e in range(21):
+        lo, hi = 1 << e, 1 << (e + 1)
+        ks.update(int(v) for v in rng.integers(lo, min(hi, (1 << 20) + 2), size=24))
+        ks.update((lo, lo + 1, hi - 1))
+    means = []
+    for k in sorted(ks):
+        means += [float(k), math.nextafter(float(k), 0.0), math.nextafter(float(k), math.inf)]
+    for k in (3, 17, 1000, 4097, 65537, 300001, 1000003):
+        for r in (1.5e-6, 1.9e-6, 2.1e-6, 2.5e-6, 8e-7, 1e-7):
+            means += [k * (1 + r), k * (1 - r), (k + 1) - k * r, k + k * r]
+    means += [float(v) for v in np.concatenate([rng.uniform(1e-7, 1.0, 64), np.geomspace(1e-7, 1.0, 64)])]
+    for t in (20.0, 19.9999999, 19.999999, 20.000001, -20.0, -19.999999, -20.000001):
+        means += [2.0 ** t, math.nextafter(2.0 ** t, 0.0), math.nextafter(2.0 ** t, math.inf)]
+    return [v for v in means if v > 0.0]
+
+
+def test_trunc_exp_decision_boundary_on_the_device(oracle):
+    m = amd()
+    L, OL = m._lib.lib(), oracle.lib()
+    from librabft_simulator_amd.simulator import make_config
+    means = _boundary_means()
+    got = np.zeros(len(means), dtype=np.int64)
+    one = np.zeros(1, dtype=np.int64)
+    for j, mean in enumerate(means):
+        cfg = make_config(4, m.RandomDelay.new(mean, 0.0), m.NodeConfig())
+        m._lib.check(L.lbft_device_sample_delays(0, ctypes.byref(cfg), 7, one.ctypes.data, 1))
+        got[j] = one[0]
+    want = np.array([int(math.exp(math.log(v))) for v in means], dtype=np.int64)
+    bad = np.nonzero(got != want)[0]
+    assert len(bad) == 0, [(means[i], int(got[i]), int(want[i])) for i in bad[:10]]
+    for mode in (0, 1):
+        for j, mean in enumerate(means):
+            OL.lbft_oracle_sample_delays(ctypes.byref(oracle.make_config(mean=mean, variance=0.0, math_mode=mode)), 7, one.ctypes.data, 1)
+            assert one[0] == got[j], (mode, mean, int(one[0]), int(got[j]))
+    # the sweep does reach the slow path: integers whose float estimate sits inside the margin
+    assert sum(1 for v in means if v >= 1.0 and abs(v - round(v)) < 2e-6 * v) > 500
+    # dense sprays around integers of every octave: y = mu + sigma * N(0, 1) with sigma ~ 1e-6, so exp(y) falls within a few 1e-6 of k,
+    # on both sides of the margin
+    n = 20000
+    a, b = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+    for e in range(1, 21):
+        for k in ((1 << e) - 1, (3 << e) // 2 + 1):
+            if k > 1 << 20:
+                continue
+            for rel in (4e-7, 1.5e-6):
+                cfg = make_config(4, m.RandomDelay.new(float(k), (k * rel) ** 2), m.NodeConfig())
+                m._lib.check(L.lbft_device_sample_delays(0, ctypes.byref(cfg), 1000 + e, b.ctypes.data, n))
+                for mode in (0, 1):
+                    OL.lbft_oracle_sample_delays(ctypes.byref(oracle.make_config(mean=float(k), variance=(k * rel) ** 2, math_mode=mode)),
+                                                 1000 + e, a.ctypes.data, n)
+                    assert (a == b).all(), (k, rel, mode, int((a != b).sum()))
+
+
+def test_headline_kernel_takes_the_samplers_decision(oracle):
+    """A full run on the headline kernel (4 nodes, log-normal delays, > 8 networks per wavefront) with a fixed delay at a mean where
+    exp(ln(mean)) < mean, so every delay is mean - 1 -- decided by the same trunc_exp as the sampler entry point."""
+    m = amd()
+    k = next(k for k in range(9, 100) if math.exp(math.log(k)) < k)
+    seeds = np.arange(1, 32769, dtype=np.uint64)
+    sim = m.BatchSimulator.new(seeds, 4, m.RandomDelay.new(float(k), 0.0))
+    res = sim.loop_until(1000)
+    assert sim.layout()["kernel_class"] & (1 << 14), sim.layout()
+    assert (res.faults == 0).all()
+    idx = np.arange(0, len(seeds), 2048)
+    ref = oracle.run_batch(oracle.make_config(num_nodes=4, mean=float(k), variance=0.0, math_mode=1), seeds[idx], 1000, history_cap=64)
+    assert (res.commit_counts[idx] == ref["commit_counts"]).all()
+    assert (res.last_committed_states[idx] == ref["last_states"]).all()
+    assert (res.committed_histories(64)[idx] == ref["histories"]).all()
+    assert (res.startup_times[idx] == k).all()  # 0 + (k - 1) + 1
