@@ -151,6 +151,31 @@ typedef struct lbft_param_set {
 int lbft_batch_create_param_sets(const lbft_config* base, const lbft_param_set* sets, uint32_t n_sets, const uint32_t* set_of_instance,
                                  const uint64_t* seeds, size_t n_instances, int device, lbft_batch** out);
 
+/* Commit times and commit latency.  A batch that records commit times stores, for every entry it appends to a node's committed history,
+ * the simulator clock of the event during which that node's SimulatedContext::commit appended it (the `clock` of loop_until after
+ * max(event time, clock), simulator.rs:398-400), as a GlobalTime.  Equivalently: the smallest t for which a fresh run of the same seed
+ * to loop_until(t) leaves the node with more than k commits (fresh: loop_until drops the first event past max_clock).  The commit
+ * latency of an entry is commit_time - (startup_time[proposer] + time), with the entry's proposer and time (lbft_commit); it lies in
+ * [0, max_clock].  Entries never recorded read as -1: those past the commit count and those lost to LBFT_FAULT_LOG_OVERFLOW.
+ *
+ * lbft_batch_record_commit_times: call before the batch's first run (LBFT_ERR_STATE after it); plain and parameter-set batches.  Such a
+ * batch runs the commit-time twin of its class's lane-private run kernel (liblbft_commit_times.so beside this library; LBFT_ERR_UNSUPPORTED
+ * naming it when it is missing): class 0 runs lbft_k_run0's twin -- also the batches that would take lbft_k_run0q / 0s / 0u --, class 1
+ * lbft_k_run<1>'s -- also those that would take lbft_k_run1l.  Networks above 32 nodes are LBFT_ERR_UNSUPPORTED, and so are the
+ * node-level interface (lbft_batch_manual_begin, lbft_node_*) and lbft_batch_load_node (a loaded history has no commit times).  Every
+ * run starts from a buffer of -1 (after lbft_batch_reset too); lbft_batch_run_steps works unchanged; a checkpoint of such a batch carries
+ * the buffer and loads only into a batch that records commit times (LBFT_ERR_INVALID otherwise); lbft_batch_device_bytes counts the
+ * buffer ([instance][node][log capacity] int32).  Everything else the batch computes is what it computes without the recording.
+ * lbft_batch_commit_times: out[(inst * num_nodes + node) * cap_per_node + k], aligned with lbft_batch_committed_histories, -1 padded.
+ * lbft_batch_commit_latency_histogram: one sample per (instance, node, committed entry), instances with a non-zero fault word skipped,
+ * per group -- the parameter set, or one group for a plain batch: hist[group * bins + min(latency / bin_width, bins - 1)] (the last bin
+ * also counts everything above it), stats[group * 4 + {0, 1, 2, 3}] = samples, sum, min, max of the latencies (min = max = 0 without
+ * samples).  bin_width >= 1, bins >= 1, groups * bins <= 2^31.  Computed on the device with integer atomics: bit-reproducible.
+ * Both read-back calls return LBFT_ERR_STATE before a finished run, or when the batch does not record commit times. */
+int lbft_batch_record_commit_times(lbft_batch* b, int enable);
+int lbft_batch_commit_times(const lbft_batch* b, int64_t* out, size_t cap_per_node);
+int lbft_batch_commit_latency_histogram(const lbft_batch* b, uint32_t bin_width, uint32_t bins, uint64_t* hist, uint64_t* stats);
+
 /* Simulator::loop_until(GlobalTime(max_clock), None) for every instance (simulator.rs:380-475), including
  * the initial scheduling done by Simulator::new.  0 <= max_clock <= LBFT_MAX_CLOCK (2^31 - 3).  May be called again after
  * lbft_batch_reset.  Returns LBFT_ERR_FAULT if any instance faulted (results of the others are valid). */
@@ -247,7 +272,8 @@ size_t lbft_batch_device_bytes(const lbft_batch* b);
  * of the LDS event queues by all lanes of the wavefront) << 13 | (class-0 kernel with the headline network -- 4 nodes, unit voting rights,
  * log-normal delays -- fixed at compile time, lbft_k_run0q) << 14 | (small-batch kernel with ONE network per wavefront executed as
  * wavefront-uniform code on the scalar unit, lbft_k_run0u -- set together with bit 13) << 15 | (parameter-set batch: lbft_k_ps_run0 /
- * lbft_k_ps_run1 of liblbft_paramsets.so, bits 10-15 clear) << 16. */
+ * lbft_k_ps_run1 of liblbft_paramsets.so, bits 10-15 clear) << 16 | (commit-time twin: lbft_k_ct_run0 / 1 or lbft_k_ct_ps_run0 / 1 of
+ * liblbft_commit_times.so, bits 10-15 clear) << 17. */
 int lbft_batch_layout(const lbft_batch* b, uint32_t* out);
 /* Events processed per run-kernel launch (0 = whole simulation in one launch). */
 int lbft_batch_set_max_steps(lbft_batch* b, uint32_t max_steps);

@@ -1,8 +1,9 @@
-"""Build liblbft_hip.so and liblbft_paramsets.so (hand-written HIP for gfx950) in-tree with hipcc.
+"""Build liblbft_hip.so, liblbft_paramsets.so and liblbft_commit_times.so (hand-written HIP for gfx950) in-tree with hipcc.
 
 `python -m librabft_simulator_amd.build` or `build()`; the libraries are git-ignored build products.
-liblbft_paramsets.so holds the kernels of parameter-set batches (lbft_batch_create_param_sets); liblbft_hip.so
-opens it beside itself on first use, so that its own code object stays as it is.
+liblbft_paramsets.so holds the kernels of parameter-set batches (lbft_batch_create_param_sets), liblbft_commit_times.so those of
+batches that record commit times (lbft_batch_record_commit_times); liblbft_hip.so opens them beside itself on first use, so that its
+own code object stays as it is.
 """
 import os
 import shutil
@@ -11,13 +12,20 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc", "lbft_hip.hip")
 DEPS = [SRC] + [os.path.join(HERE, "csrc", f) for f in ("lbft_core.h", "lbft_math.h", "lbft_tables.h", "lbft_save_node.h", "lbft_launch.h",
-                                                         "lbft_paramsets.h")] + [
+                                                         "lbft_paramsets.h", "lbft_commit_times.h")] + [
     os.path.join(HERE, "..", "include", "lbft.h")]
 OUT = os.path.join(HERE, "liblbft_hip.so")
 PS_SRC = os.path.join(HERE, "csrc", "lbft_paramsets.hip")
-PS_DEPS = [PS_SRC] + [os.path.join(HERE, "csrc", f) for f in ("lbft_core.h", "lbft_math.h", "lbft_launch.h", "lbft_paramsets.h")] + [
+PS_DEPS = [PS_SRC] + [os.path.join(HERE, "csrc", f) for f in ("lbft_core.h", "lbft_math.h", "lbft_launch.h", "lbft_paramsets.h",
+                                                               "lbft_lane_run.h")] + [
     os.path.join(HERE, "..", "include", "lbft.h")]
 PS_OUT = os.path.join(HERE, "liblbft_paramsets.so")
+CT_SRC = os.path.join(HERE, "csrc", "lbft_commit_times.hip")
+CT_DEPS = [CT_SRC] + [os.path.join(HERE, "csrc", f) for f in ("lbft_core.h", "lbft_math.h", "lbft_launch.h", "lbft_commit_times.h",
+                                                               "lbft_lane_run.h")] + [
+    os.path.join(HERE, "..", "include", "lbft.h")]
+CT_OUT = os.path.join(HERE, "liblbft_commit_times.so")
+LIBS = ((SRC, OUT, DEPS), (PS_SRC, PS_OUT, PS_DEPS), (CT_SRC, CT_OUT, CT_DEPS))
 
 # -ffp-contract=off: Rust never fuses; every fused multiply-add in lbft_math.h is explicit.
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wno-unused-value"]
@@ -92,12 +100,12 @@ def _stale(out, deps):
 
 
 def is_stale():
-    return _stale(OUT, DEPS) or _stale(PS_OUT, PS_DEPS)
+    return any(_stale(out, deps) for _src, out, deps in LIBS)
 
 
 def build(force=False, verbose=False):
-    """Both libraries, each with exactly HIPCC_FLAGS (the two compile in parallel)."""
-    jobs = [(src, out) for src, out, deps in ((SRC, OUT, DEPS), (PS_SRC, PS_OUT, PS_DEPS)) if force or _stale(out, deps)]
+    """The three libraries, each with exactly HIPCC_FLAGS (they compile in parallel)."""
+    jobs = [(src, out) for src, out, deps in LIBS if force or _stale(out, deps)]
     procs = []
     for src, out in jobs:
         cmd = [hipcc_path()] + HIPCC_FLAGS + [src, "-o", out]

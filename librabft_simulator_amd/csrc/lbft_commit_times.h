@@ -1,0 +1,29 @@
+// lbft_commit_times.h -- the interface between liblbft_hip.so and liblbft_commit_times.so (the kernels of batches that record commit
+// times, lbft_batch_record_commit_times).  As liblbft_paramsets.so, the second library is a code object of its own so that the machine code
+// of the first stays exactly what it was; liblbft_hip.so opens it on first use (dlopen beside itself) and calls these launchers on the
+// batch's stream.
+#ifndef LBFT_COMMIT_TIMES_H
+#define LBFT_COMMIT_TIMES_H
+
+#include <hip/hip_runtime.h>
+
+#include "lbft_core.h"
+
+#define LBFT_COMMIT_TIMES_LIB "liblbft_commit_times.so"
+
+extern "C" {
+// One launch of the commit-time twin of the run kernel of class `cls` (K_SMALL: lbft_k_run0's geometry, K_MID: lbft_k_run<1>'s) with the
+// geometry prepare_run chose.  sets / set_of: a parameter-set batch's (both NULL for a plain batch).  ctimes: the batch's commit-time
+// buffer, [instance][node][p->lcap] i32.
+typedef hipError_t (*lbft_ct_run_fn)(int cls, const lbft::Params* p, lbft::u32* state, lbft::u32* unfinished, const lbft::ParamSetDev* sets,
+                                     const lbft::u8* set_of, lbft::i32* ctimes, lbft::u32 grid, lbft::u32 block, size_t lds_bytes,
+                                     hipStream_t stream);
+// Commit-latency histogram of a finished run, accumulated into hist[group * bins + bin] and stats[group * 4 + {samples, sum, ~min, max}]
+// (both zeroed by the caller; the minimum is accumulated as the maximum of its complement).  Groups: grp_inst lists the instances of
+// group g at [grp_off[g], grp_off[g + 1]); grp_inst == NULL = one group of every instance.  max_group: instances of the largest group.
+typedef hipError_t (*lbft_ct_hist_fn)(const lbft::Params* p, const lbft::u32* state, const lbft::i32* ctimes, const lbft::u32* grp_inst,
+                                      const lbft::u32* grp_off, lbft::u32 n_groups, lbft::u32 max_group, lbft::u32 bin_width, lbft::u32 bins,
+                                      unsigned long long* hist, unsigned long long* stats, hipStream_t stream);
+}
+
+#endif  // LBFT_COMMIT_TIMES_H

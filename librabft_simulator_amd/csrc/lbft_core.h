@@ -721,6 +721,12 @@ struct ParamSetDev {
 // The step of a K_PARAM_SETS class runs on a SimTSets (below): SimT plus the lane's set.  The plain classes' SimT carries no trace of it
 // (no base, no member: a base class, even an empty one, changed the machine code of lbft_k_run2l).
 template <int KCLS> struct SimTSets;
+// Commit-time batches (lbft_batch_record_commit_times, liblbft_commit_times.so): the flag added to a lane-private class above (with or without
+// K_PARAM_SETS) gives the same step, and commit_block also stores the clock of every commit it appends to a node's log into the batch's
+// commit-time buffer ([instance][node][lcap] i32, SimTTimed::ctimes below).  As for the sets, the plain classes carry no trace of it.
+enum : int { K_COMMIT_TIMES = 64, K_SMALL_TIMED = K_SMALL | K_COMMIT_TIMES, K_MID_TIMED = K_MID | K_COMMIT_TIMES,
+             K_SMALL_SETS_TIMED = K_SMALL_SETS | K_COMMIT_TIMES, K_MID_SETS_TIMED = K_MID_SETS | K_COMMIT_TIMES };
+template <int KCLS> struct SimTTimed;
 // ------------------------------------------------------------------------------------------------
 // One simulated network: `tile` is the instance's tile, `lane4` the byte offset of its column in a row.
 // ------------------------------------------------------------------------------------------------
@@ -735,8 +741,9 @@ template <int KCLS> struct SimTSets;
 //      plain large-network path fits 256 registers (21 spilled) and runs two wavefronts per SIMD with half the lanes each
 template <int KCLS>
 struct SimT {
-  static constexpr int CLS = KCLS & ~K_PARAM_SETS;            // the class whose step this is
+  static constexpr int CLS = KCLS & ~(K_PARAM_SETS | K_COMMIT_TIMES);  // the class whose step this is
   static constexpr bool PSET = (KCLS & K_PARAM_SETS) != 0;    // ... with the lane's own parameter set (LBFT_SET below)
+  static constexpr bool CTIME = (KCLS & K_COMMIT_TIMES) != 0;  // ... recording the clock of every commit (commit_block)
   static constexpr bool LEAN2 = CLS == K_LARGE_LEAN || CLS == K_LARGE_EXCHANGE;  // 7 = 5 plus the record exchange of quirks bit 0 (24 spilled registers; a kernel of its own: with
                                                        // that code compiled in, the runs without it lose 10 %)
   static constexpr bool BIG = CLS == K_LARGE || LEAN2;       // multi-word node / author sets
@@ -2277,6 +2284,11 @@ LBFT_UNROLL
       u32 nc = nf(node, NF_NCOMMITS);
       if (LBFT_UNLIKELY(nc >= P.lcap)) { fault |= F_LOG_OVERFLOW; return true; }
       st(P.off_log + node * P.lcap + nc, y);
+      // the commit's time (K_COMMIT_TIMES classes): the clock of the event being processed, at the log entry's index
+      if constexpr (CTIME) {
+        SimTTimed<KCLS>* t = static_cast<SimTTimed<KCLS>*>(this);
+        t->ctimes[(size_t)(t->crow + node) * P.lcap + nc] = clock;
+      }
       nfs(node, NF_NCOMMITS, nc + 1);
       // read_epoch_id (simulated_context.rs:199-207)
       // epoch = depth / commands_per_epoch; the (software) 64-bit division only runs when a boundary is crossed
@@ -4457,6 +4469,16 @@ struct SimTSets : SimT<KCLS> {  // (SimT names it for every class -- LBFT_SET's 
   ParamSetDev ls;
   using SimT<KCLS>::SimT;
   LBFT_HD void load_set(const ParamSetDev& s) { ls = s; }
+};
+// SimT of a K_COMMIT_TIMES class (K_PARAM_SETS or not): the batch's commit-time buffer, [instance][node][lcap] i32, and the lane's first row
+// in it (instance * n), attached at kernel entry.  (The buffer's base stays the kernel argument -- wavefront-uniform, in SGPRs -- and the lane
+// keeps one 32-bit row index: a per-lane pointer took the 257th VGPR of lbft_k_ct_ps_run0 and spilled it.)
+template <int KCLS>
+struct SimTTimed : SimTSets<KCLS> {
+  i32* ctimes;
+  u32 crow;
+  using SimTSets<KCLS>::SimTSets;
+  LBFT_HD void attach_commit_times(i32* base, u32 row) { ctimes = base; crow = row; }
 };
 // The class lbft_k_run (and the host model) executes a batch with.
 inline int sim_class(const Params& p) {

@@ -4,7 +4,9 @@ Comma lists for the reference's study variables (librabft-v2/src/main.rs:73-140)
 ``--lambda``, ``--target-commit-interval`` -- and ``--drop-per-million``; their cross product is the grid, at most 256 points.  Every point
 runs ``--seeds-per-point`` networks of ``--nodes`` nodes to ``--max-clock``, all points in ONE batch (BatchSimulator.with_param_sets).
 ``--assign blocked`` gives point k the instances [k * seeds, (k + 1) * seeds); ``interleaved`` gives it instances k, k + points, ...
-Seeds are first-seed .. first-seed + seeds-per-point - 1 for every point.  Prints one JSON line per grid point.
+Seeds are first-seed .. first-seed + seeds-per-point - 1 for every point.  Prints one JSON line per grid point; with ``--latency`` the
+batch records commit times and each line gains a ``"latency"`` object (BatchResult.latency_by_param_set: samples, mean, min, max and
+the 0.5 / 0.9 / 0.99 quantiles of the commit latency over every node's commits of the point's instances).
 """
 import argparse
 import itertools
@@ -56,6 +58,7 @@ def main(argv=None):
     ap.add_argument("--max-clock", type=int, default=1000)
     ap.add_argument("--assign", choices=("blocked", "interleaved"), default="blocked")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--latency", action="store_true", help="record commit times and add each point's commit-latency summary")
     args = ap.parse_args(argv)
     points = grid_points(args)
     if not 1 <= len(points) <= MAX_PARAM_SETS:
@@ -67,12 +70,16 @@ def main(argv=None):
                      drop_per_million=pt["drop_per_million"]) for pt in points]
     set_of, seed_index = set_assignment(len(points), args.seeds_per_point, args.assign)
     seeds = (args.first_seed + seed_index).astype(np.uint64)
-    sim = BatchSimulator.with_param_sets(seeds, args.nodes, sets, set_of, commands_per_epoch=args.commands_per_epoch, device=args.device)
+    kw = {"commit_times": True} if args.latency else {}
+    sim = BatchSimulator.with_param_sets(seeds, args.nodes, sets, set_of, commands_per_epoch=args.commands_per_epoch, device=args.device, **kw)
     try:
         res = sim.loop_until(args.max_clock, allow_faults=True)
-        for pt, row in zip(points, res.by_param_set()):
+        latency = res.latency_by_param_set() if args.latency else None
+        for k, (pt, row) in enumerate(zip(points, res.by_param_set())):
             line = dict(pt, nodes=args.nodes, max_clock=args.max_clock, seeds=args.seeds_per_point, assign=args.assign)
             line.update(instances=row["instances"], faulted=row["faulted"], commits=row["commits"], rounds=row["rounds"])
+            if latency is not None:
+                line["latency"] = latency[k]
             print(json.dumps(line), flush=True)
     finally:
         sim.close()

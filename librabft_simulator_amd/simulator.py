@@ -153,6 +153,17 @@ def write_data_files(path, rows, messages, num_nodes):
         f.write("%d\n" % messages)
 
 
+def histogram_quantile(hist, width, q):
+    """The q-quantile of the samples binned in ``hist`` (bin k = [k * width, (k + 1) * width)) by the inverted-CDF rule: the lower edge of
+    the first bin whose cumulative count reaches ceil(q * N) (at least 1); None for an empty histogram."""
+    cdf = np.cumsum(np.asarray(hist, dtype=np.uint64))
+    n = int(cdf[-1]) if len(cdf) else 0
+    if n == 0:
+        return None
+    target = max(1, int(np.ceil(q * n)))
+    return int(np.searchsorted(cdf, target, side="left")) * int(width)
+
+
 class BatchResult:
     """Results of ``BatchSimulator.loop_until`` (lazy device read-back through the C ABI)."""
 
@@ -288,6 +299,56 @@ class BatchResult:
             out.append(row)
         return out
 
+    def commit_times(self, cap_per_node=None):
+        """[instance, node, k] int64, aligned with ``committed_histories``: the simulator clock (a GlobalTime) of the event during which the
+        node committed its k-th entry, -1 where nothing was recorded (past the commit count, or lost to a log overflow).  Needs a batch
+        created with ``commit_times=True``.  ``cap_per_node=None``: the width ``committed_histories()`` gives (the largest commit count, at
+        least 1); an explicit 0 gives an empty last axis."""
+        if cap_per_node is None:
+            cap_per_node = max(int(self.commit_counts.max()) if self._sim.num_instances else 0, 1)
+        cap_per_node = int(cap_per_node)
+        if cap_per_node < 0:
+            raise ValueError("cap_per_node must be at least 0")
+        out = np.full((self._sim.num_instances, self._sim.num_nodes, cap_per_node), -1, dtype=np.int64)
+        check(_lib.lib().lbft_batch_commit_times(self._sim._h, out.ctypes.data, cap_per_node))
+        return out
+
+    def latency_histogram(self, bin_width=None, bins=None):
+        """Commit-latency histogram computed on the device, per group (the parameter sets of a ``with_param_sets`` batch, else one group):
+        ``(hist, stats)``, ``hist[group, min(latency // bin_width, bins - 1)]`` (uint64; the last bin also counts everything above it) and
+        ``stats[group] = (samples, sum, min, max)`` (uint64).  One sample per (instance, node, committed entry) of the instances without a
+        fault; latency = commit time - (startup_times[proposer] + time).  The defaults are exact: width 1 and max_clock + 1 bins while
+        that is at most 65 536 bins, above that the smallest width that fits."""
+        if (bin_width is not None and int(bin_width) < 1) or (bins is not None and int(bins) < 1):
+            raise ValueError("bin_width and bins must be at least 1")
+        span = int(self._sim._max_clock) + 1
+        if bin_width is None:
+            bin_width = -(-span // int(bins)) if bins else max(1, -(-span // (1 << 16)))
+        if bins is None:
+            bins = -(-span // int(bin_width))
+        groups = len(self._sim.param_sets) if self._sim.param_sets is not None else 1
+        hist = np.zeros((groups, int(bins)), dtype=np.uint64)
+        stats = np.zeros((groups, 4), dtype=np.uint64)
+        check(_lib.lib().lbft_batch_commit_latency_histogram(self._sim._h, int(bin_width), int(bins), hist.ctypes.data, stats.ctypes.data))
+        return hist, stats
+
+    def latency_by_param_set(self, quantiles=(0.5, 0.9, 0.99)):
+        """Per group of ``latency_histogram`` (parameter set, or the one group of a plain batch), in set order: ``samples``, ``mean``,
+        ``min``, ``max`` and ``quantiles`` ({str(q): latency}), from the device histogram with its default (exact) binning.  Quantiles use
+        the inverted-CDF rule -- the smallest L with count(<= L) >= ceil(q * samples), numpy's ``method="inverted_cdf"`` -- and are exact
+        with bins of width 1; ``None`` without samples."""
+        span = int(self._sim._max_clock) + 1
+        width = max(1, -(-span // (1 << 16)))
+        hist, stats = self.latency_histogram()
+        out = []
+        for g in range(hist.shape[0]):
+            n = int(stats[g, 0])
+            row = {"set": g, "samples": n, "mean": float(stats[g, 1]) / n if n else None, "min": int(stats[g, 2]) if n else None,
+                   "max": int(stats[g, 3]) if n else None}
+            row["quantiles"] = {str(q): histogram_quantile(hist[g], width, q) for q in quantiles}
+            out.append(row)
+        return out
+
     def contexts(self, instance=0):
         """The ``Vec<&Context>`` that ``Simulator::loop_until`` returns, for one instance."""
         return [SimulatedContextView(self, instance, n) for n in range(self._sim.num_nodes)]
@@ -316,7 +377,8 @@ class BatchSimulator:
     def __init__(self, rng_seeds, num_nodes, network_delay, node_config=None, commands_per_epoch=30000,
                  voting_rights=None, device=0, queue_capacity=0, snapshot_capacity=0, block_capacity=0,
                  log_capacity=0, max_steps_per_launch=0, lanes_per_wavefront=0, lds_queue_slots=-1, equivocate_every=0, drop_per_million=0, partition=None,
-                 calendar_queue=True, quirks=0, rights_rotation=0, keep_retired_stores=False, _param_sets=None, _set_of_instance=None):
+                 calendar_queue=True, quirks=0, rights_rotation=0, keep_retired_stores=False, commit_times=False, _param_sets=None,
+                 _set_of_instance=None):
         seeds = np.ascontiguousarray(rng_seeds, dtype=np.uint64)
         self.seeds = seeds
         self.num_instances = int(seeds.shape[0])
@@ -326,6 +388,8 @@ class BatchSimulator:
                                 queue_capacity, snapshot_capacity, block_capacity, log_capacity, equivocate_every, drop_per_million, partition, quirks,
                                 rights_rotation)
         self._h = C.c_void_p()
+        self.param_sets = None
+        self._max_clock = 0
         if _param_sets is None:
             check(_lib.lib().lbft_batch_create(C.byref(self._cfg), seeds.ctypes.data, self.num_instances, self.device,
                                                C.byref(self._h)))
@@ -347,6 +411,8 @@ class BatchSimulator:
             check(_lib.lib().lbft_batch_set_lds_queue_slots(self._h, lds_queue_slots))
         if keep_retired_stores:  # past_record_stores (node.rs:43) in full: save_node then also serves nodes that have changed epoch
             check(_lib.lib().lbft_batch_keep_retired_stores(self._h, 1))
+        if commit_times:  # the commit-time twin kernels (lbft_batch_record_commit_times): BatchResult.commit_times, latency_histogram
+            check(_lib.lib().lbft_batch_record_commit_times(self._h, 1))
 
     @classmethod
     def new(cls, rng_seeds, num_nodes, network_delay, node_config=None, **kw):
@@ -386,6 +452,7 @@ class BatchSimulator:
         if round_trace:
             check(_lib.lib().lbft_batch_enable_round_trace(self._h, int(round_trace)))
         self._mutated()
+        self._max_clock = int(max_clock)
         rc = check(_lib.lib().lbft_batch_run_until(self._h, int(max_clock)), allow_fault=allow_faults or auto)
         if auto and rc == _lib.LBFT_ERR_FAULT:
             if round_trace < worst and (BatchResult(self).faults & _lib.LBFT_FAULT_TRACE_OVERFLOW).any():
@@ -412,6 +479,7 @@ class BatchSimulator:
         or None); the result is available once nothing is left to process."""
         left = C.c_uint64()
         self._mutated()
+        self._max_clock = int(max_clock)
         check(_lib.lib().lbft_batch_run_steps(self._h, int(max_clock), int(steps), C.byref(left)), allow_fault=allow_faults)
         return int(left.value), (BatchResult(self) if left.value == 0 else None)
 
