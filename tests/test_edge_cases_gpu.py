@@ -1,6 +1,8 @@
 """Device tier of the edge-case table (tests/edge_cases.py): BatchSimulator / with_param_sets on the MI355X against the oracle on every case
 -- commit counts, last states, histories, active rounds, startup times, fault words and the events / rng_draws / events_scheduled counters --
-the kernel class and queue discipline each boundary case must select, and the refused horizons.  Plus SimT::trunc_exp at its decision
+the kernel class and queue discipline each boundary case must select, and the refused horizons.  Every case of at most 32 nodes and every
+parameter-set batch again with commit times recorded (the twins of liblbft_commit_times.so): the untimed outcome and results, commit times
+equal to the oracle-derived ones, the default latency histogram equal to numpy.  Plus SimT::trunc_exp at its decision
 boundary through lbft_device_sample_delays: the device's single-precision exp2 estimate and the 2e-6 margin that decides when it is trusted
 are code the host build never runs."""
 import ctypes
@@ -14,6 +16,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import commit_times_oracle as cto  # noqa: E402
 import edge_cases as ec  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -24,7 +27,7 @@ def amd():
     return m
 
 
-def make_sim(case, seeds=None):
+def make_sim(case, seeds=None, **kw):
     m = amd()
     f = dict(mean=10.0, variance=4.0, delay_model=0, uniform_lo=5, uniform_hi=15, target_commit_interval=100000, delta=20, gamma=2.0,
              lambda_=0.5, quirks=0, drop_per_million=0)
@@ -34,7 +37,7 @@ def make_sim(case, seeds=None):
     seeds = np.array(case["seeds"] if seeds is None else seeds, dtype=np.uint64)
     return m.BatchSimulator.new(seeds, case["n"], delay, nc, commands_per_epoch=f.get("commands_per_epoch", 30000), quirks=f["quirks"],
                                 drop_per_million=f["drop_per_million"],
-                                calendar_queue=case.get("calendar_queue", True), block_capacity=case.get("block_capacity", 0))
+                                calendar_queue=case.get("calendar_queue", True), block_capacity=case.get("block_capacity", 0), **kw)
 
 
 def oracle_runs(oracle, case, seeds):
@@ -117,8 +120,7 @@ def test_refused_on_the_device(case):
     assert (res.faults == 0).all()
 
 
-@pytest.mark.parametrize("case", ec.PARAM_SET_CASES, ids=lambda c: c["name"])
-def test_param_set_edge_batch_device(oracle, case):
+def make_param_set_sim(case, **kw):
     m = amd()
     sets = []
     for k in range(len(case["sets"])):
@@ -128,11 +130,16 @@ def test_param_set_edge_batch_device(oracle, case):
                                drop_per_million=f["drop_per_million"]))
     set_of, seeds = ec.set_layout(case)
     set_of, seeds = np.array(set_of, dtype=np.uint32), np.array(seeds, dtype=np.uint64)
-    sim = m.BatchSimulator.with_param_sets(seeds, case["n"], sets, set_of)
+    return m.BatchSimulator.with_param_sets(seeds, case["n"], sets, set_of, **kw), set_of, seeds
+
+
+@pytest.mark.parametrize("case", ec.PARAM_SET_CASES, ids=lambda c: c["name"])
+def test_param_set_edge_batch_device(oracle, case):
+    sim, set_of, seeds = make_param_set_sim(case)
     res = sim.loop_until(case["max_clock"], allow_faults=True)
     flags = sim.layout()["kernel_class"]
     assert flags & (1 << 16) and flags & 0xff == case["kernel_class"], hex(flags)
-    for k in range(len(sets)):
+    for k in range(len(case["sets"])):
         idx = np.nonzero(set_of == k)[0]
         sub = ec.set_as_case(case, k)
         kind, arg = ec.expected(sub)
@@ -141,6 +148,60 @@ def test_param_set_edge_batch_device(oracle, case):
             continue
         assert (res.faults[idx] == 0).all(), (k, res.faults[idx])
         assert_instances_equal(res, idx, oracle_runs(oracle, sub, seeds[idx]), sub["name"])
+
+
+# ---- the same cases on the commit-time twins (lbft_k_ct_*) -------------------------------------------------------------------------------
+HOST_THREADS = min(os.cpu_count() or 8, 16)
+
+
+@pytest.mark.parametrize("case", [c for c in ec.CASES if ec.expected(c)[0] != "refused" and not c.get("host_only") and c["n"] <= 32],
+                         ids=lambda c: c["name"])
+def test_edge_case_with_commit_times(oracle, case):
+    """Every case again on a batch that records commit times: the untimed outcome and results, commit times equal to the ones derived
+    from fresh oracle runs, and the default latency histogram (at the largest horizon: width 32 768, 65 536 bins, 8 passes) equal to numpy."""
+    kind, arg = ec.expected(case)
+    mc = case["max_clock"]
+    plain = make_sim(case)
+    rp = plain.loop_until(mc, allow_faults=True)
+    timed = make_sim(case, commit_times=True)
+    rt = timed.loop_until(mc, allow_faults=True)
+    flags = timed.layout()["kernel_class"]
+    assert flags & (1 << 17) and flags & 0xff == ec.expected_layout(case)[0], (case["name"], hex(flags))
+    assert (rt.faults == (arg if kind == "fault" else 0)).all(), (case["name"], rt.faults)
+    cto.same_results(rt, rp)
+    ct = rt.commit_times()
+    assert ((ct >= 0).sum(axis=2) == rt.commit_counts).all()
+    if kind == "equal":
+        ref = cto.commit_times(oracle, ec.oracle_config(oracle, case), np.array(case["seeds"], dtype=np.uint64), mc, ct.shape[2], HOST_THREADS)
+        assert (ct == ref).all(), case["name"]
+    cto.check_default_latency(rt, mc)
+    plain.close()
+    timed.close()
+
+
+@pytest.mark.parametrize("case", ec.PARAM_SET_CASES, ids=lambda c: c["name"])
+def test_param_set_edge_batch_with_commit_times(oracle, case):
+    mc = case["max_clock"]
+    plain, set_of, seeds = make_param_set_sim(case)
+    rp = plain.loop_until(mc, allow_faults=True)
+    timed, _, _ = make_param_set_sim(case, commit_times=True)
+    rt = timed.loop_until(mc, allow_faults=True)
+    flags = timed.layout()["kernel_class"]
+    assert flags & (1 << 16) and flags & (1 << 17) and flags & 0xff == case["kernel_class"], hex(flags)
+    cto.same_results(rt, rp)
+    ct = rt.commit_times()
+    assert ((ct >= 0).sum(axis=2) == rt.commit_counts).all()
+    for k in range(len(case["sets"])):
+        idx = np.nonzero(set_of == k)[0]
+        sub = ec.set_as_case(case, k)
+        kind, arg = ec.expected(sub)
+        assert (rt.faults[idx] == (arg if kind == "fault" else 0)).all(), (k, rt.faults[idx])
+        if kind == "equal":
+            ref = cto.commit_times(oracle, ec.oracle_config(oracle, sub), seeds[idx], mc, ct.shape[2], HOST_THREADS)
+            assert (ct[idx] == ref).all(), sub["name"]
+    cto.check_default_latency(rt, mc, set_of, len(case["sets"]))
+    plain.close()
+    timed.close()
 
 
 # ---- SimT::trunc_exp at its decision boundary --------------------------------------------------------------------------------------------
