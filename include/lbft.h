@@ -227,7 +227,8 @@ int lbft_batch_save_node(const lbft_batch* b, size_t inst, uint32_t node, void* 
  * another batch run with the same seed and configuration, or by the reference / the oracle for the same run loads; an image that names
  * a record the pool does not hold is LBFT_ERR_UNSUPPORTED (and so is an image with retired record stores loaded into a batch created without
  * lbft_batch_keep_retired_stores: they would be dropped silently and the node could not be saved again), one saved under another configuration (nodes, voting rights, NodeConfig) or
- * malformed is LBFT_ERR_INVALID -- in every failing case the node is left untouched.  Written: the NodeState (record store with the
+ * malformed is LBFT_ERR_INVALID -- in every failing case the node is left untouched.  `node_time` is only compared with the image's times, never
+ * stored, so any int64_t is accepted (unlike the node-level calls below).  Written: the NodeState (record store with the
  * node's blocks / certificates / timeouts / votes / election, pacemaker, epoch, voting constraints, commit tracker, retired record
  * stores).  Not written: what the reference keeps outside NodeState -- the simulator's timer bookkeeping and startup time
  * (SimulatedNode, bft-lib/src/simulator.rs:53-59) and the SmrContext (ledger and pending states, simulated_context.rs:75-83), which its
@@ -334,7 +335,11 @@ typedef struct lbft_node_view { /* RecordStoreState / PacemakerState / NodeState
 /* NodeState::make_initial_state for every node of every instance (node.rs:87-114), no events are processed. */
 int lbft_batch_manual_begin(lbft_batch* b, int64_t max_clock);
 int lbft_batch_manual_finalize(lbft_batch* b);
-/* ConsensusNode::update_node(&mut self, &mut Context, clock: NodeTime) -> NodeUpdateActions (interfaces.rs:37-49, node.rs:240-304) */
+/* Node times: the `node_time` of lbft_node_update, lbft_node_handle_response and of the UPDATE_NODE / HANDLE_RESPONSE entries of
+ * lbft_node_calls (the other calls ignore it) lies in [0, LBFT_MAX_CLOCK]: the device keeps clocks as 32 bits where the reference uses
+ * i64.  Any time in that range is accepted, also past the session's max_clock; outside it the call is LBFT_ERR_INVALID before any launch
+ * and the node is untouched.
+ * ConsensusNode::update_node(&mut self, &mut Context, clock: NodeTime) -> NodeUpdateActions (interfaces.rs:37-49, node.rs:240-304) */
 int lbft_node_update(lbft_batch* b, size_t inst, uint32_t node, int64_t node_time, lbft_actions* out);
 /* DataSyncNode::create_notification (interfaces.rs:62-64, data_sync.rs:82-111): *handle names the notification
  * until lbft_node_release_notification; it may be delivered to any number of receivers. */

@@ -395,76 +395,8 @@ __global__ void lbft_k_export_histories(Params p, const u32* __restrict__ state,
   }
 }
 
-// Node-level interface (include/lbft.h lbft_node_*): one lane applies one trait call to one node.
-enum NodeOp : u32 { OP_UPDATE = 0, OP_CREATE_NOTIFICATION, OP_HANDLE_NOTIFICATION, OP_RELEASE_NOTIFICATION, OP_VIEW,
-                    OP_CREATE_REQUEST, OP_HANDLE_REQUEST, OP_HANDLE_RESPONSE };
-__device__ __forceinline__ void node_op_body(const Params& p, u32* __restrict__ state, u32 op, u32 inst, u32 node, u32 arg0, u32 arg1, i64 node_time,
-                                             unsigned long long* __restrict__ out) {
-  Sim s(p, state, inst);
-  s.load_scalars();
-  if (op == OP_UPDATE) {
-    s.begin_node(node);
-    Actions a = s.update_node(node, node_time);
-    s.end_node(node);
-    out[0] = (unsigned long long)a.next;
-    out[1] = out[2] = 0;
-    if (a.send_to >= 0) out[1 + (a.send_to >> 6)] = 1ULL << (a.send_to & 63);
-    out[3] = a.broadcast ? 1 : 0;
-    out[4] = a.query_all ? 1 : 0;
-  } else if (op == OP_CREATE_NOTIFICATION) {
-    s.begin_node(node);
-    i32 slot = s.snap_alloc();
-    if (slot >= 0) { s.write_snapshot(node, (u32)slot); s.snap_set_refs((u32)slot, 1, s.nf(node, NF_EPOCH)); }
-    out[0] = (unsigned long long)(long long)slot;
-  } else if (op == OP_HANDLE_NOTIFICATION) {
-    s.begin_node(node);
-    auto sn = s.load_snapshot(arg1);
-    bool sync = s.handle_notification(node, arg0, arg1, sn);
-    s.end_node(node);
-    out[0] = sync ? 1 : 0;
-  } else if (op == OP_RELEASE_NOTIFICATION) {
-    s.snap_release(arg1);
-  } else if (op == OP_CREATE_REQUEST) {  // DataSyncNode::create_request (data_sync.rs:66-71,179-181): epoch + the chains' heads
-    s.begin_node(node);
-    i32 slot = s.make_request_slot(s.nf(node, NF_EPOCH), s.nf(node, NF_HCC_BLK) | (s.nf(node, NF_HQC_BLK) << 16));
-    if (slot >= 0) s.snap_set_refs((u32)slot, 1, s.nf(node, NF_EPOCH));
-    out[0] = (unsigned long long)(long long)slot;
-  } else if (op == OP_HANDLE_REQUEST) {  // DataSyncNode::handle_request on `node` (data_sync.rs:183-207): its store now + the request
-    s.begin_node(node);
-    u32 qb = s.sfw(arg1, 0);
-    u32 req_epoch = s.ld(qb + S_EPOCH), req_certs = s.ld(qb + S_CERTS);
-    if (s.refpack()) req_epoch &= 0xffffu;  // (large networks: the slot's reference count rides in the upper half of this word)
-    i32 slot = s.snap_alloc();
-    if (slot >= 0) {
-      u32 rb = s.sfw((u32)slot, 0);
-      s.write_store_snapshot(node, rb);
-      s.st(s.sqw(rb, 0), req_epoch); s.st(s.sqw(rb, 1), req_certs);
-      s.snap_set_refs((u32)slot, 1, s.nf(node, NF_EPOCH));
-    }
-    out[0] = (unsigned long long)(long long)slot;
-  } else if (op == OP_HANDLE_RESPONSE) {  // DataSyncNode::handle_response(response from peer arg0, clock) (data_sync.rs:209-240)
-    s.begin_node(node);
-    s.handle_response(node, arg0, arg1, node_time);
-    s.end_node(node);
-  } else {  // OP_VIEW
-    s.begin_node(node);
-    out[0] = s.nf(node, NF_EPOCH); out[1] = s.nf(node, NF_CUR_ROUND); out[2] = s.nf(node, NF_HQC_ROUND);
-    out[3] = s.nf(node, NF_HTC_ROUND); out[4] = s.nf(node, NF_HC_ROUND); out[5] = s.nf(node, NF_PM_ROUND);
-    out[6] = s.nf(node, NF_LVR); out[7] = s.nf(node, NF_LOCKED); out[8] = s.nf(node, NF_NCOMMITS);
-    u32 leader = s.nf(node, NF_PM_LEADER);
-    out[9] = leader == LBFT_NO_LEADER ? 0xffffffffULL : leader;
-    out[10] = s.nf(node, NF_ELECTION) & 0xff;
-    u32 nt = 0, nv = 0;
-    for (u32 k = 0; k < p.mw; k++) {
-      nt += (u32)__popc(s.am_word(node, NF_TO_MASK, k));
-      nv += (u32)__popc(s.am_word(node, NF_BAL0_AUTHORS, k)) + (u32)__popc(s.am_word(node, NF_BAL1_AUTHORS, k));
-    }
-    out[11] = nt; out[12] = nv;
-    out[13] = s.nf(node, NF_PROPOSED_BLK) ? 1 : 0;
-    out[14] = s.nf(node, NF_HTC_ROUND) ? 1 : 0;
-  }
-  s.store_scalars(s.ld(I_DONE) != 0);
-}
+// Node-level interface (include/lbft.h lbft_node_*): node_op_body (lbft_node_ops.h) on one lane per call.
+#include "lbft_node_ops.h"
 __global__ void lbft_k_node_op(Params p, u32* __restrict__ state, u32 op, u32 inst, u32 node, u32 arg0, u32 arg1, i64 node_time,
                                unsigned long long* __restrict__ out) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
@@ -989,6 +921,8 @@ static int node_op(lbft_batch* b, u32 op, size_t inst, u32 node, u32 arg0, u32 a
 }
 
 static bool exchange_layout(const lbft_batch* b);
+// The node times a driver may pass (include/lbft.h): the device keeps clocks as 32 bits, the reference as i64.  Refused before any launch.
+static bool node_time_ok(int64_t t) { return t >= 0 && t <= LBFT_MAX_CLOCK; }
 // Many trait calls in ONE launch and ONE synchronisation (a host that drives thousands of simulators -- the Rust `Simulator<GpuNode, ..>`
 // of bindings/rust -- is otherwise bound by ~10-20 us of launch + sync per call).  Every call of a batch must address another
 // instance (calls on one instance are ordered by the protocol; they go into successive batches).
@@ -1009,13 +943,17 @@ int lbft_node_calls(lbft_batch* b, const lbft_node_call* calls, size_t n, lbft_n
     seen[c.instance] = 1;
     u32 op;
     switch (c.op) {
-      case LBFT_CALL_UPDATE_NODE: op = OP_UPDATE; break;
+      case LBFT_CALL_UPDATE_NODE: op = OP_UPDATE; if (!node_time_ok(c.node_time)) { g_err = "node_time outside [0, LBFT_MAX_CLOCK]"; return LBFT_ERR_INVALID; } break;
       case LBFT_CALL_CREATE_NOTIFICATION: op = OP_CREATE_NOTIFICATION; break;
       case LBFT_CALL_HANDLE_NOTIFICATION: op = OP_HANDLE_NOTIFICATION; if (c.peer >= b->p.n || c.handle >= b->p.scap) return LBFT_ERR_INVALID; break;
       case LBFT_CALL_RELEASE_NOTIFICATION: op = OP_RELEASE_NOTIFICATION; if (c.handle >= b->p.scap) return LBFT_ERR_INVALID; break;
       case LBFT_CALL_CREATE_REQUEST: op = OP_CREATE_REQUEST; break;
       case LBFT_CALL_HANDLE_REQUEST: op = OP_HANDLE_REQUEST; if (c.handle >= b->p.scap) return LBFT_ERR_INVALID; break;
-      case LBFT_CALL_HANDLE_RESPONSE: op = OP_HANDLE_RESPONSE; if (c.peer >= b->p.n || c.handle >= b->p.scap) return LBFT_ERR_INVALID; break;
+      case LBFT_CALL_HANDLE_RESPONSE:
+        op = OP_HANDLE_RESPONSE;
+        if (c.peer >= b->p.n || c.handle >= b->p.scap) return LBFT_ERR_INVALID;
+        if (!node_time_ok(c.node_time)) { g_err = "node_time outside [0, LBFT_MAX_CLOCK]"; return LBFT_ERR_INVALID; }
+        break;
       default: g_err = "unknown call"; return LBFT_ERR_INVALID;
     }
     if (!exchange && (op == OP_CREATE_REQUEST || op == OP_HANDLE_REQUEST || op == OP_HANDLE_RESPONSE)) {
@@ -1065,6 +1003,7 @@ int lbft_node_calls(lbft_batch* b, const lbft_node_call* calls, size_t n, lbft_n
 
 int lbft_node_update(lbft_batch* b, size_t inst, uint32_t node, int64_t node_time, lbft_actions* out) {
   if (!out) return LBFT_ERR_INVALID;
+  if (!node_time_ok(node_time)) { g_err = "node_time outside [0, LBFT_MAX_CLOCK]"; return LBFT_ERR_INVALID; }
   unsigned long long h[5];
   int rc = node_op(b, OP_UPDATE, inst, node, 0, 0, node_time, h, 5);
   if (rc != LBFT_OK) return rc;
@@ -1134,6 +1073,7 @@ int lbft_node_handle_request(lbft_batch* b, size_t inst, uint32_t node, uint32_t
   return LBFT_OK;
 }
 int lbft_node_handle_response(lbft_batch* b, size_t inst, uint32_t node, uint32_t peer, uint32_t response, int64_t node_time) {
+  if (!node_time_ok(node_time)) { g_err = "node_time outside [0, LBFT_MAX_CLOCK]"; return LBFT_ERR_INVALID; }
   if (!exchange_layout(b)) {
     if (!b || inst >= b->m || node >= b->p.n || peer >= b->p.n || (response & 0xffff0000u) != LBFT_TOKEN_RESPONSE) return LBFT_ERR_INVALID;
     if (!b->manual) { g_err = "lbft_batch_manual_begin first"; return LBFT_ERR_STATE; }

@@ -590,13 +590,15 @@ class NodeHandle:
     """One node of one instance behind the reference's trait surface (bft-lib/src/interfaces.rs): ``ConsensusNode::
     update_node`` and ``DataSyncNode::{create_notification, handle_notification}``, each executed on the GPU by
     ``lbft_node_*``.  Obtained from ``BatchSimulator.manual(...)``; the caller owns time and message delivery (the role
-    of ``Simulator::loop_until`` or of bft-driver's ``CoreDriver``)."""
+    of ``Simulator::loop_until`` or of bft-driver's ``CoreDriver``).  The clocks of ``update_node`` and ``handle_response`` lie in
+    ``[0, 2**31 - 3]`` (LBFT_MAX_CLOCK), also past the session's ``max_clock``: the device keeps clocks as 32 bits; outside that
+    range the call raises LbftError -1 and leaves the node untouched."""
 
     def __init__(self, sim, instance, node):
         self._sim, self.instance, self.author = sim, int(instance), int(node)
 
     def update_node(self, clock):
-        """ConsensusNode::update_node(clock: NodeTime) -> NodeUpdateActions (librabft-v2/src/node.rs:240-304)."""
+        """ConsensusNode::update_node(clock: NodeTime) -> NodeUpdateActions (librabft-v2/src/node.rs:240-304); ``0 <= clock <= 2**31 - 3``."""
         a = LbftActions()
         self._sim._mutated()
         check(_lib.lib().lbft_node_update(self._sim._h, self.instance, self.author, int(clock), C.byref(a)))
@@ -631,7 +633,7 @@ class NodeHandle:
         return (self.author, int(h.value))
 
     def handle_response(self, response, clock):
-        """DataSyncNode::handle_response(response, clock) (data_sync.rs:209-240)."""
+        """DataSyncNode::handle_response(response, clock) (data_sync.rs:209-240); ``0 <= clock <= 2**31 - 3``."""
         peer, handle = response
         self._sim._mutated()
         check(_lib.lib().lbft_node_handle_response(self._sim._h, self.instance, self.author, peer, handle, int(clock)))
@@ -646,7 +648,7 @@ class NodeHandle:
 
     def load_node(self, image, clock):
         """ConsensusNode::load_node (node.rs:211-231): restore this node's NodeState from a save_node image; `clock` = the node's time
-        (the reference refuses "saved state from the future")."""
+        (the reference refuses "saved state from the future"); only compared with the image's times, so any integer is accepted."""
         self._sim.load_node(self.instance, self.author, image, clock)
 
     def view(self):

@@ -16,6 +16,8 @@
 
 using namespace lbft;
 
+#include "../librabft_simulator_amd/csrc/lbft_node_ops.h"
+
 static const u64 ZX[257] = LBFT_ZIG_NORM_X_BITS_INIT;
 static const u64 ZF[257] = LBFT_ZIG_NORM_F_BITS_INIT;
 static const u64 ET[256] = LBFT_EXP_TAB_INIT;
@@ -47,17 +49,19 @@ typedef struct lbft_hostmodel_caps {
   uint32_t keep_stores;    // lbft_batch_keep_retired_stores: the retired record stores are archived in full
 } lbft_hostmodel_caps;
 
-// Same outputs as lbft_oracle_run_batch, plus per-instance fault words and max queue/snapshot use.
-int lbft_hostmodel_run_batch(const lbft_oracle_config* cfg, const lbft_hostmodel_caps* caps, const uint64_t* seeds,
-                             size_t n_instances, int64_t max_clock, uint32_t threads, uint32_t* commit_counts,
-                             uint64_t* active_rounds, uint64_t* last_states, lbft_oracle_commit* histories,
-                             size_t history_cap, lbft_oracle_counters* counters, uint32_t* faults,
-                             uint32_t* maxq_out, uint32_t* maxsnap_out, int64_t* round_switches /* [inst][rcap][n], INT64_MIN = none */,
-                             uint32_t* max_rounds /* [inst] */,
-                             uint64_t* record_hashes /* [inst][node][hash_cap][4]: SimT::committed_record_hashes, or NULL */, size_t hash_cap) {
+// The Params of a host-model batch and the tables they point into.  `manual`: the capacities of a node-level session
+// (lbft_batch_manual_begin) rather than of a run.
+struct HostParams {
+  Params p;
+  std::vector<u32> weights;
+  std::vector<i64> dur;
+  std::vector<u8> leaders;
+};
+static int setup_params(const lbft_oracle_config* cfg, const lbft_hostmodel_caps* caps, size_t n_instances, int64_t max_clock, bool manual,
+                        HostParams& hp) {
   if ((cfg->quirks & ~3u) != 0 || cfg->num_nodes > LBFT_MAX_NODES) return -10;
   if (max_clock < 0 || max_clock > LBFT_MAX_CLOCK) return -14;  // (lbft_batch_run_until: LBFT_ERR_INVALID)
-  Params p;
+  Params& p = hp.p;
   memset(&p, 0, sizeof(p));
   p.n = cfg->num_nodes;
   p.m = (u32)n_instances;
@@ -74,7 +78,8 @@ int lbft_hostmodel_run_batch(const lbft_oracle_config* cfg, const lbft_hostmodel
   {  // as the device host code: epochs a node can go through are bounded by its commits
     u64 eauto = (u64)caps->bcap / (cfg->commands_per_epoch ? cfg->commands_per_epoch : 1) + 2;
     p.ecap = (u32)(eauto > 4096 ? 4096 : eauto);
-    if (p.ecap < 64) p.ecap = 64;
+    if (manual) { if (!(cfg->quirks & 1u) && !caps->keep_stores) p.ecap = 0; }  // (lbft_batch_manual_begin: exactly the device's archive)
+    else if (p.ecap < 64) p.ecap = 64;
   }
   p.qcal = caps->qcal;
   p.rarch_words = caps->keep_stores ? 1u : 0u;  // (compute_layout turns the flag into the entry size)
@@ -97,23 +102,41 @@ int lbft_hostmodel_run_batch(const lbft_oracle_config* cfg, const lbft_hostmodel
   p.part_end = (i32)(cfg->partition_end < 0 ? 0 : (cfg->partition_end > 0x7fffffff ? 0x7fffffff : cfg->partition_end));
   p.rot = cfg->rights_rotation % p.n;
   p.total_votes = 0;
-  std::vector<u32> weights(p.n);
+  std::vector<u32>& weights = hp.weights;
+  weights.resize(p.n);
   for (u32 i = 0; i < p.n; i++) { weights[i] = cfg->voting_rights ? (u32)cfg->voting_rights[i] : 1; p.total_votes += weights[i]; }
   p.weights = weights.data();
   p.quorum = 2 * p.total_votes / 3 + 1;
   p.unit_weights = 1;
   for (u32 i = 0; i < p.n; i++) if (p.weights[i] != 1) p.unit_weights = 0;
   if (p.unit_weights) p.rot = 0;
-  std::vector<i64> dur(4096);
+  std::vector<i64>& dur = hp.dur;
+  dur.resize(4096);
   for (size_t k = 0; k < dur.size(); k++) dur[k] = f64_to_i64_sat((double)cfg->delta * std::pow((double)k, cfg->gamma));
   const u32 leader_len = 4096, leader_tables = p.rot ? p.n : 1;  // one table per shift of the rotating voting rights
-  std::vector<u8> leaders((size_t)leader_len * leader_tables);
+  std::vector<u8>& leaders = hp.leaders;
+  leaders.resize((size_t)leader_len * leader_tables);
   for (u32 k = 0; k < leader_tables; k++)
     for (u32 r = 0; r < leader_len; r++) leaders[(size_t)k * leader_len + r] = (u8)compute_leader(p.weights, p.n, p.total_votes, r, k);
   p.dur_tab = dur.data(); p.dur_len = (u32)dur.size();
   p.leader_tab = leaders.data(); p.leader_len = leader_len;
   p.exp_tab = ET; p.zig_x = ZX; p.zig_f = ZF;
   compute_layout(p);
+  return 0;
+}
+
+// Same outputs as lbft_oracle_run_batch, plus per-instance fault words and max queue/snapshot use.
+int lbft_hostmodel_run_batch(const lbft_oracle_config* cfg, const lbft_hostmodel_caps* caps, const uint64_t* seeds,
+                             size_t n_instances, int64_t max_clock, uint32_t threads, uint32_t* commit_counts,
+                             uint64_t* active_rounds, uint64_t* last_states, lbft_oracle_commit* histories,
+                             size_t history_cap, lbft_oracle_counters* counters, uint32_t* faults,
+                             uint32_t* maxq_out, uint32_t* maxsnap_out, int64_t* round_switches /* [inst][rcap][n], INT64_MIN = none */,
+                             uint32_t* max_rounds /* [inst] */,
+                             uint64_t* record_hashes /* [inst][node][hash_cap][4]: SimT::committed_record_hashes, or NULL */, size_t hash_cap) {
+  HostParams host;
+  if (int rc = setup_params(cfg, caps, n_instances, max_clock, false, host)) return rc;
+  Params& p = host.p;
+  std::vector<u32>& weights = host.weights;
   std::vector<u32> state(state_words(p), 0);
 
   if (threads == 0) threads = 1;
@@ -272,6 +295,102 @@ int lbft_hostmodel_run_batch(const lbft_oracle_config* cfg, const lbft_hostmodel
     }
   }
   return rc;
+}
+
+// ---- Node-level sessions (tests/test_node_level_fuzz.py): lbft_batch_manual_begin and the lbft_node_* calls on the host.  Every call
+// runs node_op_body (csrc/lbft_node_ops.h), the body of the device's lbft_k_node_op / lbft_k_node_ops, on the state rows of the session.
+struct HostSession {
+  HostParams hp;
+  std::vector<u32> state;
+  i64 delta, tci;
+  double gamma, lambda;
+};
+
+// Instances with the capacities `caps` (the device's for the same batch: oracle_ctypes.manual_caps), each initialised as
+// lbft_batch_manual_begin does (NodeState::make_initial_state, no events processed).
+int lbft_hostmodel_session_create(const lbft_oracle_config* cfg, const lbft_hostmodel_caps* caps, const uint64_t* seeds, size_t n_instances,
+                                  int64_t max_clock, void** out) {
+  HostSession* hs = new HostSession;
+  if (int rc = setup_params(cfg, caps, n_instances, max_clock, true, hs->hp)) { delete hs; return rc; }
+  const Params& p = hs->hp.p;
+  if (!layout_fits(p.total_words)) { delete hs; return -15; }  // (lbft_batch_manual_begin: LBFT_ERR_INVALID)
+  hs->state.assign(state_words(p), 0);
+  for (size_t i = 0; i < n_instances; i++) { Sim s(p, hs->state.data(), (u32)i); s.init(seeds[i]); }
+  hs->delta = cfg->delta; hs->tci = cfg->target_commit_interval; hs->gamma = cfg->gamma; hs->lambda = cfg->lambda;
+  *out = hs;
+  return 0;
+}
+
+void lbft_hostmodel_session_destroy(void* h) { delete static_cast<HostSession*>(h); }
+
+// One trait call (op = NodeOp of lbft_node_ops.h) -> its 16 result words.  Arguments are checked as the device's host code checks them.
+int lbft_hostmodel_session_op(void* h, uint32_t op, uint32_t inst, uint32_t node, uint32_t arg0, uint32_t arg1, int64_t node_time, uint64_t* out) {
+  HostSession* hs = static_cast<HostSession*>(h);
+  const Params& p = hs->hp.p;
+  if (inst >= p.m || node >= p.n || op > OP_HANDLE_RESPONSE || arg0 >= p.n) return -1;
+  if ((op == OP_HANDLE_NOTIFICATION || op == OP_RELEASE_NOTIFICATION || op == OP_HANDLE_REQUEST || op == OP_HANDLE_RESPONSE) && arg1 >= p.scap) return -1;
+  if ((op == OP_CREATE_REQUEST || op == OP_HANDLE_REQUEST || op == OP_HANDLE_RESPONSE) && !(p.quirks & 1u)) return -3;
+  memset(out, 0, 16 * sizeof(uint64_t));
+  node_op_body(p, hs->state.data(), op, inst, node, arg0, arg1, node_time, reinterpret_cast<unsigned long long*>(out));
+  return 0;
+}
+
+// The instance's fault word and its snapshot slots: live now and the most ever live.
+uint32_t lbft_hostmodel_session_fault(void* h, uint32_t inst, uint32_t* live_slots, uint32_t* max_slots) {
+  HostSession* hs = static_cast<HostSession*>(h);
+  Sim s(hs->hp.p, hs->state.data(), inst);
+  s.load_scalars();
+  if (live_slots) *live_slots = hs->hp.p.scap - (s.mask_slots() ? s.popc64(s.snap_mask) : s.snap_free);
+  if (max_slots) *max_slots = s.maxsnap;
+  return s.fault;
+}
+
+// Committed history of (inst, node) (up to `cap` entries) and the Sip13 State over it, as lbft_k_finalize computes it -> commit count.
+size_t lbft_hostmodel_session_history(void* h, uint32_t inst, uint32_t node, lbft_oracle_commit* out, size_t cap, uint64_t* last_state) {
+  HostSession* hs = static_cast<HostSession*>(h);
+  const Params& p = hs->hp.p;
+  Sim s(p, hs->state.data(), inst);
+  s.load_scalars();
+  u32 nc = s.nfm(node, NF_NCOMMITS);
+  Sip13 sh;
+  sh.init();
+  sh.word(nc);
+  for (u32 k = 0; k < nc; k++) {
+    u32 b = s.ld(p.off_log + node * p.lcap + k);
+    u64 proposer = s.blk_author(b), index = s.bf(b, B_CMD);
+    i64 time = (i64)(i32)s.bf(b, B_TIME);
+    sh.word(proposer); sh.word(index); sh.word((u64)time);
+    if (out && k < cap) out[k] = lbft_oracle_commit{proposer, index, time};
+  }
+  if (last_state) *last_state = sh.finish();
+  return nc;
+}
+
+// SimT::committed_record_hashes of (inst, node): [cap][4] words -> entries written.
+uint32_t lbft_hostmodel_session_record_hashes(void* h, uint32_t inst, uint32_t node, uint64_t* out, uint32_t cap) {
+  HostSession* hs = static_cast<HostSession*>(h);
+  Sim s(hs->hp.p, hs->state.data(), inst);
+  s.load_scalars();
+  return s.committed_record_hashes(node, out, cap);
+}
+
+// ConsensusNode::save_node of (inst, node) through lbft_save_node.h (what lbft_batch_save_node runs): 0 and *len = the image's length
+// (written when it fits `cap`), or the builder's code.
+int lbft_hostmodel_session_save_node(void* h, uint32_t inst, uint32_t node, uint8_t* buf, size_t cap, size_t* len) {
+  HostSession* hs = static_cast<HostSession*>(h);
+  const Params& p = hs->hp.p;
+  std::vector<u32> hw;  // (instance-major rows are the instance's words as they stand)
+  if (p.tw != 1) {
+    hw.resize(p.total_words);
+    for (u32 w = 0; w < p.total_words; w++) hw[w] = hs->state[word_offset(p, inst, w)];
+  }
+  std::vector<uint8_t> image;
+  std::string err;
+  int rc = build_node_image(p, p.tw == 1 ? &hs->state[word_offset(p, inst, 0)] : hw.data(), node, hs->hp.weights.data(), hs->delta, hs->gamma, hs->lambda, hs->tci, image, err);
+  if (rc != 0) return rc;
+  *len = image.size();
+  if (buf && image.size() <= cap) memcpy(buf, image.data(), image.size());
+  return 0;
 }
 
 }  // extern "C"

@@ -442,3 +442,139 @@ def hostmodel_run_batch(cfg, seeds, max_clock, threads=1, history_cap=0, qcap=25
     return {"commit_counts": commit_counts, "active_rounds": active_rounds, "last_states": last_states,
             "histories": hist, "counters": ctr.as_dict(), "faults": faults, "maxq": maxq, "maxsnap": maxsnap,
             "round_switches": rs, "max_rounds": mr, "record_hashes": rh}
+
+
+def manual_caps(num_nodes, quirks, max_clock, snapshot_capacity=0, keep_stores=0, block_capacity=0):
+    """The capacities lbft_batch_manual_begin gives a node-level session (lbft_hip.hip prepare_run, every capacity on auto but the
+    snapshot pool), as HostSession takes them."""
+    n = num_nodes
+    qauto = 16 * n * n if n <= 16 else 8 * n * n
+    qcap = max(qauto, 128)
+    sauto = max(n * n + 8 * n, 64 * n) if quirks & 1 else 8 * n
+    scap = snapshot_capacity or min(max(sauto, 32), 65535)
+    bcap = block_capacity or min(max_clock + 64 if n <= 2 else max_clock // 10 + 64, 65534)
+    # (instance-major rows, tw = 1, as the device lays out large networks: the image builder then reads them in place)
+    return dict(qcap=qcap, scap=scap, bcap=bcap, lcap=bcap, qheap=int(qcap > 256 or n > 32), tw=1, keep_stores=int(bool(keep_stores)))
+
+
+class HostSession:
+    """A node-level session on the host build of the kernel logic: lbft_batch_manual_begin, then the lbft_node_* calls, each one
+    node_op_body (csrc/lbft_node_ops.h, the body of the device's lbft_k_node_op / lbft_k_node_ops) on these state rows.  ``call`` takes
+    and returns what ``BatchSimulator.node_calls`` does for one call; in reference mode (quirks bit 0 clear) request / response
+    handles are the payload-free tokens of the device's host code (lbft_hip.hip lbft_node_create_request ...)."""
+    # LBFT_CALL_* (include/lbft.h) -> NodeOp (lbft_node_ops.h)
+    _OPS = {0: 0, 1: 1, 2: 2, 3: 3, 4: 5, 5: 6, 6: 7}
+    OP_VIEW = 4
+    VIEW_FIELDS = ("epoch_id", "current_round", "highest_quorum_certificate_round", "highest_timeout_certificate_round",
+                   "highest_committed_round", "active_round", "latest_voted_round", "locked_round", "commit_count", "active_leader",
+                   "election", "num_current_timeouts", "num_current_votes", "has_proposed_block", "has_timeout_certificate")
+
+    def __init__(self, cfg, seeds, max_clock, caps):
+        L = hostmodel_lib()
+        if not hasattr(L, "_session_bound"):
+            vp = C.c_void_p
+            L.lbft_hostmodel_session_create.argtypes = [C.POINTER(OracleConfig), C.POINTER(HostModelCaps), vp, C.c_size_t, C.c_int64, C.POINTER(vp)]
+            L.lbft_hostmodel_session_create.restype = C.c_int
+            L.lbft_hostmodel_session_destroy.argtypes = [vp]
+            L.lbft_hostmodel_session_destroy.restype = None
+            L.lbft_hostmodel_session_op.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int64, vp]
+            L.lbft_hostmodel_session_op.restype = C.c_int
+            L.lbft_hostmodel_session_fault.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+            L.lbft_hostmodel_session_fault.restype = C.c_uint32
+            L.lbft_hostmodel_session_history.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_size_t, C.POINTER(C.c_uint64)]
+            L.lbft_hostmodel_session_history.restype = C.c_size_t
+            L.lbft_hostmodel_session_record_hashes.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_uint32]
+            L.lbft_hostmodel_session_record_hashes.restype = C.c_uint32
+            L.lbft_hostmodel_session_save_node.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+            L.lbft_hostmodel_session_save_node.restype = C.c_int
+            L._session_bound = True
+        self._L = L
+        self.cfg = cfg
+        self.quirks = cfg.quirks
+        self.caps = dict(caps)
+        hc = HostModelCaps(caps["qcap"], caps["scap"], caps["bcap"], caps["lcap"], 0, caps.get("qheap", 0), 0, 0, 0, 0, 0, caps.get("tw", 0), caps.get("keep_stores", 0))
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+        self.m = len(seeds)
+        self.h = C.c_void_p()
+        rc = L.lbft_hostmodel_session_create(C.byref(cfg), C.byref(hc), seeds.ctypes.data, self.m, int(max_clock), C.byref(self.h))
+        if rc != 0:
+            raise RuntimeError("host session: %d" % rc)
+        self._out = np.zeros(16, dtype=np.uint64)
+
+    def _op(self, op, inst, node, arg0, arg1, t):
+        rc = self._L.lbft_hostmodel_session_op(self.h, op, inst, node, arg0, arg1, int(t), self._out.ctypes.data)
+        if rc != 0:
+            raise RuntimeError("host session op %d: %d" % (op, rc))
+        return [int(v) for v in self._out]
+
+    def call(self, op, inst, node, peer, handle, t):
+        """One LBFT_CALL_* -> {"actions", "handle", "should_sync", "status"} (status -5 = LBFT_ERR_FAULT: no free snapshot slot)."""
+        r = {"actions": None, "handle": 0, "should_sync": False, "status": 0}
+        if not self.quirks & 1 and op in (4, 5, 6):  # reference mode: tokens, no launch
+            if op == 4:
+                r["handle"] = 0xffff0000 | node
+            elif op == 5:
+                assert handle == 0xffff0000 | node
+                r["handle"] = 0xfffe0000 | node
+            else:
+                assert handle == 0xfffe0000 | node
+            return r
+        if op == 3 and not self.quirks & 1 and handle & 0xfffe0000 == 0xfffe0000:
+            return r
+        o = self._op(self._OPS[op], inst, node, peer, handle, t)
+        if op == 0:
+            bits = o[1] | (o[2] << 64)
+            r["actions"] = {"next_scheduled_update": o[0] - (1 << 64) if o[0] >= 1 << 63 else o[0],
+                            "should_send": [a for a in range(128) if (bits >> a) & 1],
+                            "should_broadcast": bool(o[3]), "should_query_all": bool(o[4])}
+        elif op == 2:
+            r["should_sync"] = bool(o[0])
+        elif op in (1, 4, 5):
+            if o[0] >= 1 << 63:
+                r["status"] = -5  # LBFT_ERR_FAULT
+            else:
+                r["handle"] = o[0]
+        return r
+
+    def view(self, inst, node):
+        o = self._op(self.OP_VIEW, inst, node, 0, 0, 0)
+        return dict(zip(self.VIEW_FIELDS, o))
+
+    def fault(self, inst):
+        """(fault word, live snapshot slots, most slots ever live)"""
+        live, most = C.c_uint32(), C.c_uint32()
+        f = self._L.lbft_hostmodel_session_fault(self.h, inst, C.byref(live), C.byref(most))
+        return int(f), int(live.value), int(most.value)
+
+    def committed_history(self, inst, node):
+        """(history as COMMIT_DTYPE, last committed State)"""
+        st = C.c_uint64()
+        n = self._L.lbft_hostmodel_session_history(self.h, inst, node, None, 0, C.byref(st))
+        out = np.zeros(n, dtype=COMMIT_DTYPE)
+        self._L.lbft_hostmodel_session_history(self.h, inst, node, out.ctypes.data, n, C.byref(st))
+        return out, int(st.value)
+
+    def committed_record_hashes(self, inst, node, cap):
+        out = np.zeros((max(cap, 1), 4), dtype=np.uint64)
+        k = self._L.lbft_hostmodel_session_record_hashes(self.h, inst, node, out.ctypes.data, cap)
+        return out[:k]
+
+    def save_node(self, inst, node):
+        """The save_node image (bytes), or None where the product library refuses it (a node past epoch 0 without keep_stores)."""
+        ln = C.c_size_t()
+        if self._L.lbft_hostmodel_session_save_node(self.h, inst, node, None, 0, C.byref(ln)) != 0:
+            return None
+        buf = np.zeros(ln.value, dtype=np.uint8)
+        assert self._L.lbft_hostmodel_session_save_node(self.h, inst, node, buf.ctypes.data, ln.value, C.byref(ln)) == 0
+        return buf.tobytes()
+
+    def close(self):
+        if self.h:
+            self._L.lbft_hostmodel_session_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
