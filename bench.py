@@ -10,8 +10,13 @@ synthetic input: Simulator::new + loop_until(max_clock) for every instance of th
 resident in HBM), including the device-side reduction and the D2H copy of the counters.  Rank 0 prints
 ONE JSON line.  Instances shard across ranks with no data-path collective (weak scaling: 65 536 instances
 per GPU -> `value`); ONE collective (an all-gather of one counter row per rank, reduced locally) aggregates the throughput counters.
-For N > 1 the same command also times BASELINE config 3 as it is named -- ONE 65 536-instance batch split over the N GPUs (strong
-scaling) -- in a second leg and reports it as `config3_strong` in the same line; `scaling` names which of the two `value` is.
+
+A plain run does only what `value` needs: it sets up, runs W untimed and K timed steps, writes --dump-outputs if given and prints the
+line (its roofline figures come from the timed steps' counters and kernel times, and from the committed profile of the same kernels).
+`--full` adds, after the timed steps, what else the benchmark measures or checks: the parity gate (--parity-instances of the timed batch
+re-run on the CPU oracle), the CPU oracle's baseline, the run kernel's HBM traffic measured in two rocprofv3 child runs (headline workload
+on one GPU) and, for N > 1, BASELINE config 3 as it is named -- ONE 65 536-instance batch split over the N GPUs (strong scaling) -- timed
+in a second leg and reported as `config3_strong` in the same line; `scaling` names which of the two `value` is.
 """
 import argparse
 import json
@@ -23,6 +28,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s peak
+FULL_PARITY_INSTANCES = 16384
 
 
 def parse():
@@ -34,21 +40,25 @@ def parse():
     ap.add_argument("--instances", type=int, default=65536, help="instances per GPU (weak scaling: the default mode)")
     ap.add_argument("--total-instances", type=int, default=0,
                     help="strong scaling: this many instances in total, sharded over the ranks (BASELINE.json config 3 read as ONE 65 536-instance batch on 1..8 GPUs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need (see the module docstring): parity gate, CPU baseline, traffic measured in "
+                         "child runs, and for N > 1 the strong-scaling leg of BASELINE config 3")
     ap.add_argument("--no-config3-strong", action="store_true",
-                    help="(N > 1, weak mode) skip the second timed leg: BASELINE config 3 read as ONE batch of --instances instances split over the ranks")
-    ap.add_argument("--parity-instances", type=int, default=16384, help="instances of the timed batch (strided) re-run on the CPU oracle and compared (0 = no gate)")
+                    help="(--full, N > 1, weak mode) skip the second timed leg: BASELINE config 3 read as ONE batch of --instances instances split over the ranks")
+    ap.add_argument("--parity-instances", type=int, default=None,
+                    help="instances of the timed batch (strided) re-run on the CPU oracle and compared (default: %d with --full, else 0 = no gate)" % FULL_PARITY_INSTANCES)
     ap.add_argument("--nodes", type=int, default=4)
     ap.add_argument("--max-clock", type=int, default=1000)
     ap.add_argument("--base-seed", type=int, default=1)
     ap.add_argument("--lpw", type=int, default=0, help="lanes per wavefront carrying an instance (0 = auto)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU oracle's baseline")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only to rehearse the N > 1 path)")
     ap.add_argument("--single-device", action="store_true", help="rehearsal: every rank uses HIP device 0")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU work for the oracle sample")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="(--full) target CPU work for the oracle sample")
     ap.add_argument("--measure-traffic", action="store_true", default=None,
                     help="(N = 1, rocprofv3 on the box) collect FETCH_SIZE / WRITE_SIZE of the run kernel in two child runs of this command: roofline.traffic is "
-                         "then MEASURED IN THIS RUN (roofline.traffic_measured_here) instead of replayed from the committed profile.  Default since round 6 for "
-                         "the headline workload on one GPU; --no-measure-traffic skips it")
+                         "then MEASURED IN THIS RUN (roofline.traffic_measured_here) instead of replayed from the committed profile.  Default with --full "
+                         "for the headline workload on one GPU; --no-measure-traffic skips it")
     ap.add_argument("--no-measure-traffic", dest="measure_traffic", action="store_false")
     ap.add_argument("--native-collective", action="store_true",
                     help="also aggregate the counters through the C ABI's own collective (lbft_batch_counters_allgather_reduce: ncclAllGather on a "
@@ -59,6 +69,8 @@ def parse():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.parity_instances is None:
+        args.parity_instances = FULL_PARITY_INSTANCES if args.full else 0
     return args
 
 
@@ -77,8 +89,9 @@ def self_launch(args):
 
 def traffic_measured_here(argv):
     """--measure-traffic: FETCH_SIZE and WRITE_SIZE of the run kernel collected NOW, each in its own rocprofv3 child run of this command
-    (--kernel-trace only, as gpurun requires) -- per launch, with MI355X_MICROARCH.md's gfx950 correction (FETCH_SIZE counts a 128-byte
-    request as 64 bytes: doubled).  None when rocprofv3 is not on the box or a pass fails."""
+    as a plain run (no --full, no parity gate; --kernel-trace beside the counter, no other tracing) -- per launch,
+    with MI355X_MICROARCH.md's gfx950 correction (FETCH_SIZE counts a 128-byte request as 64 bytes: doubled).  An {"error": ...} dict when
+    rocprofv3 is not on the machine or a pass fails."""
     import collections
     import csv
     import glob
@@ -94,8 +107,8 @@ def traffic_measured_here(argv):
     if "--dump-outputs" in argv:  # (the profiled children write no outputs: only the parent's run is the one to compare)
         k = argv.index("--dump-outputs")
         del argv[k:k + 2]
-    argv = [a for a in argv if a != "--measure-traffic" and not a.startswith("--dump-outputs=")]
-    child = [sys.executable, os.path.abspath(__file__)] + argv + ["--no-cpu-baseline", "--parity-instances", "0", "--no-measure-traffic"]
+    argv = [a for a in argv if a not in ("--measure-traffic", "--full") and not a.startswith("--dump-outputs=")]
+    child = [sys.executable, os.path.abspath(__file__)] + argv + ["--parity-instances", "0"]
     vals = {}
     for counter in ("FETCH_SIZE", "WRITE_SIZE"):
         d = tempfile.mkdtemp(prefix="lbft_pmc_", dir="/tmp")
@@ -415,10 +428,10 @@ def main():
     res, kernel_ms, elapsed = timed_leg(sim)
     c = res.counters
     # BASELINE config 3 is ONE 65 536-instance batch on 1 -> 8 GPUs, i.e. the STRONG split; the driver's `--gpus N` line reports the weak batch as
-    # `value` (per-GPU work fixed) and, from a second timed leg of the same command, the strong split beside it as `config3_strong`
+    # `value` (per-GPU work fixed) and, with --full, the strong split from a second timed leg of the same command beside it as `config3_strong`
     # (round-5 review): --instances instances in total, contiguous shards of 1/N each
     strong_leg = None
-    if not strong and world > 1 and not args.no_config3_strong:
+    if args.full and not strong and world > 1 and not args.no_config3_strong:
         seeds_s = shard_seeds(args.base_seed, args.instances, rank, world)
         sim_s = BatchSimulator.new(seeds_s, args.nodes, RandomDelay.new(10.0, 4.0), NodeConfig(), device=local_rank, lanes_per_wavefront=args.lpw)
         res_s, kms_s, elapsed_s = timed_leg(sim_s)
@@ -448,9 +461,10 @@ def main():
         headline = (m, args.nodes, args.max_clock) == (65536, 4, 1000)
         traffic = measured_traffic_gb() if headline else None
         issue = measured_issue() if headline else None
-        # PMC counters cannot be read from inside this process: the headline line on one GPU collects them in two rocprofv3 child runs of the same
-        # command (bounded: 240 s each; a box without rocprofv3, or a failing pass, leaves the replayed value and says so)
-        want_here = args.measure_traffic if args.measure_traffic is not None else (headline and world == 1 and not os.environ.get("LBFT_BENCH_CHILD"))
+        # PMC counters cannot be read from inside this process: the --full headline line on one GPU collects them in two rocprofv3 child runs of the
+        # same command (bounded: 240 s each; a machine without rocprofv3, or a failing pass, leaves the replayed value and says so)
+        want_here = args.measure_traffic if args.measure_traffic is not None else (
+            args.full and headline and world == 1 and not os.environ.get("LBFT_BENCH_CHILD"))
         here = traffic_measured_here(sys.argv[1:]) if (want_here and world == 1) else None
         here_ok = bool(here) and "gb_corrected" in here
         local_events = sum(c["events"])
@@ -506,7 +520,7 @@ def main():
                          "layout": layout},
         }
         # BASELINE config 3 (one batch of --instances instances, 1 -> N GPUs: strong scaling) beside the weak `value`; at N = 1 the two coincide
-        if not strong:
+        if args.full and not strong:
             if strong_leg:
                 ps = float(agg["extra_max"][1]) / args.steps
                 sr, sc, se, sf = agg["extra_sum"]
@@ -521,7 +535,7 @@ def main():
             out["native_collective"] = native
         if args.parity_instances > 0:  # (rank 0's shard of the timed batch; oracle = test infrastructure, used only as the checker)
             out["parity"] = parity_gate(args, sim, res, seeds, args.nodes, args.max_clock)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args, args.nodes, args.max_clock)
         if args.dump_outputs:  # (rank 0's shard of the timed batch, as its last timed step left it)
             out["dumped_outputs"] = dump_outputs(args.dump_outputs, res)

@@ -128,6 +128,20 @@ def test_steps_below_one_are_refused(monkeypatch):
         assert e.code == 2
 
 
+def test_only_full_or_an_explicit_count_turns_the_parity_gate_on(monkeypatch):
+    """A plain run (the driver's `--gpus 1 --steps K --warmup W`) re-runs nothing on the oracle; --full gates 16 384 instances of the timed batch, and
+    --parity-instances sets the count with or without --full."""
+    bench = _bench()
+    for argv, full, parity in ((["--gpus", "1", "--steps", "20", "--warmup", "5"], False, 0),
+                               (["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"], True, 16384),
+                               (["--full", "--parity-instances", "0"], True, 0),
+                               (["--parity-instances", "256"], False, 256)):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+        args = bench.parse()
+        assert (args.full, args.parity_instances) == (full, parity), argv
+        assert args.measure_traffic is None  # (decided in main(): on for a --full headline run on one GPU)
+
+
 class _FakeResult:
     """The parts of BatchResult that bench.dump_outputs reads: n instances of `nodes` nodes, seeded."""
 
@@ -193,7 +207,8 @@ def test_dump_outputs_samples_a_large_batch_the_same_way_every_time(tmp_path):
 
 
 def test_traffic_children_do_not_dump_outputs(monkeypatch):
-    """The rocprofv3 child runs of --measure-traffic rebuild the command line: they must not write the parent's outputs (nor see the flag)."""
+    """The rocprofv3 child runs of --measure-traffic rebuild the command line: they must not write the parent's outputs (nor see the flag), and
+    they are plain runs (no --full, no parity gate)."""
     import shutil
     bench = _bench()
     seen = []
@@ -207,12 +222,29 @@ def test_traffic_children_do_not_dump_outputs(monkeypatch):
     monkeypatch.setattr(shutil, "which", lambda name: "/bin/" + name)
     monkeypatch.setattr(subprocess, "run", fake_run)
     monkeypatch.delenv("LBFT_BENCH_CHILD", raising=False)
-    for argv in (["--steps", "3", "--dump-outputs", "outdir", "--measure-traffic"], ["--dump-outputs=outdir", "--steps", "3"]):
+    for argv in (["--steps", "3", "--dump-outputs", "outdir", "--measure-traffic"], ["--dump-outputs=outdir", "--steps", "3", "--full", "--parity-instances", "64"]):
         seen.clear()
         assert "error" in bench.traffic_measured_here(argv)
         child = seen[0][seen[0].index("--") + 1:]
         assert child[2:4] == ["--steps", "3"] and "outdir" not in child and not any(a.startswith("--dump-outputs") for a in child)
-        assert "--measure-traffic" not in child
+        assert "--measure-traffic" not in child and "--full" not in child
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + child[2:])
+        assert bench.parse().parity_instances == 0
+
+
+@pytest.mark.gpu
+def test_a_plain_headline_run_prints_the_line_and_nothing_of_full():
+    """The driver's plain command on the headline workload: the result line with its headline keys, and none of what --full adds (parity gate, CPU
+    baseline, config 3's strong split, traffic measured in child runs)."""
+    import json
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1"],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["unit"] == "rounds/s" and line["higher_is_better"] is True and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["metric"].startswith("simulated consensus rounds/sec") and line["dtype"] and (line["steps"], line["warmup"]) == (2, 1)
+    assert line["faulted_instances"] == 0 and line["config"]["instances_per_gpu"] == 65536
+    assert not {"parity", "cpu_baseline", "config3_strong"} & line.keys() and line["roofline"]["traffic_measured_here"] is None
 
 
 @pytest.mark.gpu

@@ -198,7 +198,7 @@ def test_bench_two_ranks_on_one_device():
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--backend", "gloo", "--single-device", "--instances", "4096",
+           os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--backend", "gloo", "--single-device", "--full", "--instances", "4096",
            "--no-cpu-baseline"]
     # first WITHOUT an external launcher (`python bench.py --gpus 2 ...`: bench.py starts its own two ranks), then under the driver's launcher
     env_bare = {k: v for k, v in env.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
@@ -217,13 +217,13 @@ def test_bench_two_ranks_on_one_device():
     for line_ in (d, db):
         s3 = line_["config3_strong"]
         assert s3["scaling"] == "strong" and s3["total_instances"] == 4096 and s3["instances_per_gpu"] == 2048 and s3["n_gpus"] == 2 and s3["faulted_instances"] == 0
-    one4 = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "0", "--instances", "4096", "--no-cpu-baseline"],
+    one4 = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "0", "--full", "--instances", "4096", "--no-cpu-baseline"],
                           env=env_bare, capture_output=True, text=True, timeout=600, cwd=root)
     assert one4.returncode == 0, one4.stderr[-2000:]
     w4 = json.loads([l for l in one4.stdout.splitlines() if l.startswith("{")][-1])
     assert round(d["config3_strong"]["value"] * d["config3_strong"]["ms_per_step"]) == round(w4["value"] * w4["ms_per_step"])
     assert w4["config3_strong"]["value"] == w4["value"] and w4["config3_strong"]["n_gpus"] == 1  # one GPU: the strong split is the weak batch
-    one = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "0", "--instances", "8192", "--no-cpu-baseline"],
+    one = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "0", "--full", "--instances", "8192", "--no-cpu-baseline"],
                          env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert one.returncode == 0, one.stderr[-2000:]
     w = json.loads([l for l in one.stdout.splitlines() if l.startswith("{")][-1])
@@ -258,7 +258,7 @@ def test_bench_two_ranks_nccl():
         port = sk.getsockname()[1]
     for extra, scaling in ((["--instances", "4096"], "weak"), (["--total-instances", "8192"], "strong")):
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-               os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--native-collective"] + extra
+               os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--native-collective"] + extra
         out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=root)
         assert out.returncode == 0, out.stderr[-2000:]
         d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])

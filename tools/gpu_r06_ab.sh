@@ -30,7 +30,7 @@ for n in ("bench_q64_lpw64", "bench_q64_lpw32"):
         print(n, "failed", e)
 PY
 fi
-timeout 600 python bench.py --steps 20 --warmup 3 > $O/bench_line.json 2> $O/bench.err; tail -2 $O/bench.err
+timeout 600 python bench.py --full --steps 20 --warmup 3 > $O/bench_line.json 2> $O/bench.err; tail -2 $O/bench.err
 python - $O <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1] + "/bench_line.json").read().strip().splitlines()[-1])

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 O=gpurun_out/${1:-r06close}; mkdir -p $O
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.txt 2>&1; tail -1 $O/smoke.txt
 timeout 1500 python -m pytest tests -m gpu -q > $O/pytest_gpu_full_suite_last_session.txt 2>&1; tail -3 $O/pytest_gpu_full_suite_last_session.txt
-timeout 900 python bench.py > $O/bench_line_last_session.json 2> $O/bench.err; python - $O <<'PY'
+timeout 900 python bench.py --full > $O/bench_line_last_session.json 2> $O/bench.err; python - $O <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1] + "/bench_line_last_session.json").read().strip().splitlines()[-1])
 print("bench", round(d["value"] / 1e6, 1), "M rounds/s", d["ms_per_step"], "ms", "kernel", d["roofline"]["kernel_ms"], "frac", round(d["roofline"]["frac"], 4), "traffic", d["roofline"]["traffic"], "parity", d["parity"]["mismatches"], "of", d["parity"]["checked_instances"], "issue", d["roofline"]["issue"].get("source"))

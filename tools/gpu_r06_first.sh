@@ -35,7 +35,7 @@ for f in ("phases_large_networks.jsonl", "large_configs.jsonl"):
         print(f, "failed", e)
 PY
 wait $GEN
-timeout 600 python bench.py --steps 20 --warmup 3 > $O/bench_line.json 2> $O/bench.err; tail -2 $O/bench.err
+timeout 600 python bench.py --full --steps 20 --warmup 3 > $O/bench_line.json 2> $O/bench.err; tail -2 $O/bench.err
 python - $O <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1] + "/bench_line.json").read().strip().splitlines()[-1])
