@@ -176,6 +176,29 @@ int lbft_batch_record_commit_times(lbft_batch* b, int enable);
 int lbft_batch_commit_times(const lbft_batch* b, int64_t* out, size_t cap_per_node);
 int lbft_batch_commit_latency_histogram(const lbft_batch* b, uint32_t bin_width, uint32_t bins, uint64_t* hist, uint64_t* stats);
 
+/* Commit timelines: commits over time, stalls and recovery, per group, from the recorded commit times alone.  Both calls apply to a batch
+ * that records commit times, after a finished run (LBFT_ERR_STATE otherwise); max_clock is the horizon of that run; groups are those of
+ * the latency histogram (the parameter sets, or one group for a plain batch); instances with a non-zero fault word are skipped.
+ * For a node (i, j): nc = min(commit count, log capacity); c[0 .. nc) are its recorded commit times, non-negative and non-decreasing (the
+ * event clock never goes back); its commit instants t_1 < ... < t_r are the distinct values of c; they cut [0, max_clock] into r + 1
+ * intervals.
+ * lbft_batch_commit_series: one sample per committed entry, series[g * bins + min(c[k] / bin_width, bins - 1)] += 1.  A group's row sums
+ * to stats[g * 4 + 0] of lbft_batch_commit_latency_histogram.
+ * lbft_batch_commit_stalls: four sample families per group, each reported as stats[g * LBFT_STALL_STATS + 4 * family + {0, 1, 2, 3}] =
+ * samples, sum, min, max (min = max = 0 without samples).  since[g] lies in [0, max_clock] (outside: LBFT_ERR_INVALID, nothing is
+ * written); since == NULL means 0 for every group.
+ *   family 0, gaps:    t_{s+1} - t_s for s = 1 .. r - 1 (each >= 1), one sample per inner interval; also binned,
+ *                      hist[g * bins + min(gap / bin_width, bins - 1)]
+ *   family 1, first:   t - since[g] for the smallest instant t >= since[g], one sample per node that has such an instant (since = 0: the
+ *                      time to the first commit; since = the end of a partition: the recovery time)
+ *   family 2, tail:    max_clock - t_r, or max_clock when r = 0, one sample per node
+ *   family 3, longest: the longest of the node's r + 1 intervals, max(t_1, gaps, tail), or max_clock when r = 0, one sample per node
+ * bin_width >= 1, bins >= 1, groups * bins <= 2^31 (LBFT_ERR_INVALID otherwise, and for NULL arguments, before any HIP call).  Computed
+ * on the device (lbft_k_ct_timeline, liblbft_commit_times.so); every accumulation is an integer add, min or max: bit-reproducible. */
+#define LBFT_STALL_STATS 16
+int lbft_batch_commit_series(const lbft_batch* b, uint32_t bin_width, uint32_t bins, uint64_t* series);
+int lbft_batch_commit_stalls(const lbft_batch* b, const int64_t* since, uint32_t bin_width, uint32_t bins, uint64_t* hist, uint64_t* stats);
+
 /* Simulator::loop_until(GlobalTime(max_clock), None) for every instance (simulator.rs:380-475), including
  * the initial scheduling done by Simulator::new.  0 <= max_clock <= LBFT_MAX_CLOCK (2^31 - 3).  May be called again after
  * lbft_batch_reset.  Returns LBFT_ERR_FAULT if any instance faulted (results of the others are valid). */

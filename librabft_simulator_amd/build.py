@@ -12,7 +12,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc", "lbft_hip.hip")
 DEPS = [SRC] + [os.path.join(HERE, "csrc", f) for f in ("lbft_core.h", "lbft_math.h", "lbft_tables.h", "lbft_save_node.h", "lbft_launch.h",
-                                                         "lbft_paramsets.h", "lbft_commit_times.h", "lbft_node_ops.h")] + [
+                                                         "lbft_paramsets.h", "lbft_commit_times.h", "lbft_commit_timeline.h", "lbft_node_ops.h")] + [
     os.path.join(HERE, "..", "include", "lbft.h")]
 OUT = os.path.join(HERE, "liblbft_hip.so")
 PS_SRC = os.path.join(HERE, "csrc", "lbft_paramsets.hip")
@@ -22,7 +22,7 @@ PS_DEPS = [PS_SRC] + [os.path.join(HERE, "csrc", f) for f in ("lbft_core.h", "lb
 PS_OUT = os.path.join(HERE, "liblbft_paramsets.so")
 CT_SRC = os.path.join(HERE, "csrc", "lbft_commit_times.hip")
 CT_DEPS = [CT_SRC] + [os.path.join(HERE, "csrc", f) for f in ("lbft_core.h", "lbft_math.h", "lbft_launch.h", "lbft_commit_times.h",
-                                                               "lbft_lane_run.h")] + [
+                                                               "lbft_commit_timeline.h", "lbft_lane_run.h")] + [
     os.path.join(HERE, "..", "include", "lbft.h")]
 CT_OUT = os.path.join(HERE, "liblbft_commit_times.so")
 LIBS = ((SRC, OUT, DEPS), (PS_SRC, PS_OUT, PS_DEPS), (CT_SRC, CT_OUT, CT_DEPS))

@@ -24,6 +24,14 @@ typedef hipError_t (*lbft_ct_run_fn)(int cls, const lbft::Params* p, lbft::u32* 
 typedef hipError_t (*lbft_ct_hist_fn)(const lbft::Params* p, const lbft::u32* state, const lbft::i32* ctimes, const lbft::u32* grp_inst,
                                       const lbft::u32* grp_off, lbft::u32 n_groups, lbft::u32 max_group, lbft::u32 bin_width, lbft::u32 bins,
                                       unsigned long long* hist, unsigned long long* stats, hipStream_t stream);
+// Commit timelines of a finished run (lbft_k_ct_timeline; groups as above, hist and stats zeroed by the caller).  stalls == 0: the
+// series, hist[group * bins + bin of the commit time] per committed entry (since_of and stats unused).  stalls != 0: the histogram of
+// the gaps between a node's commit instants and stats[group * LBFT_STALL_STATS + family * 4 + {samples, sum, ~min, max}] of the gaps /
+// first / tail / longest families (lbft_commit_timeline.h); since_of[group] in [0, p->max_clock], NULL = 0 for every group.
+typedef hipError_t (*lbft_ct_timeline_fn)(const lbft::Params* p, const lbft::u32* state, const lbft::i32* ctimes, const lbft::u32* grp_inst,
+                                          const lbft::u32* grp_off, lbft::u32 n_groups, lbft::u32 max_group, int stalls,
+                                          const lbft::i32* since_of, lbft::u32 bin_width, lbft::u32 bins, unsigned long long* hist,
+                                          unsigned long long* stats, hipStream_t stream);
 }
 
 #endif  // LBFT_COMMIT_TIMES_H

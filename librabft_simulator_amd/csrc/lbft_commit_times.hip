@@ -4,7 +4,8 @@
 // their K_PARAM_SETS forms) with K_COMMIT_TIMES added, where commit_block also stores the clock of every commit into the batch's
 // commit-time buffer ([instance][node][lcap] i32, the log's index).  Their run body (lbft_lane_run.h) and LDS layout (lbft_launch.h) are
 // those of lbft_k_run0 / lbft_k_run<1> and the parameter-set kernels, so the host side of liblbft_hip.so sizes them as those.
-// The histogram kernel turns a finished run's logs and commit times into commit-latency histograms per group (parameter set).
+// The histogram kernel turns a finished run's logs and commit times into commit-latency histograms per group (parameter set); the
+// timeline kernel turns the commit times alone into commits over time and the statistics of the commit-free intervals.
 // Built as a library of its own (build.py): the code object of liblbft_hip.so, whose kernels are pinned byte for byte by the codegen
 // manifest, does not change.
 #include <hip/hip_runtime.h>
@@ -12,6 +13,7 @@
 #include "../../include/lbft.h"
 #include "lbft_core.h"
 #include "lbft_commit_times.h"
+#include "lbft_commit_timeline.h"
 
 using namespace lbft;
 
@@ -99,6 +101,124 @@ __global__ __launch_bounds__(LBFT_HIST_BLOCK) void lbft_k_ct_latency_hist(Params
   }
 }
 
+// Commit timelines (lbft_batch_commit_series / lbft_batch_commit_stalls): the commit-time rows alone -- no log, no block pool.  A row
+// (one node of one instance, lcap i32) is read by a segment of LBFT_TL_SEG consecutive lanes, entry k by lane k % LBFT_TL_SEG, so a
+// load instruction of a wavefront reads two runs of 128 contiguous bytes, not 64 lines (lbft_k_ct_latency_hist's lane per row), and
+// only the nc recorded entries of a row are read.  A lane takes its predecessor's entry by __shfl_up -- lane 0 of the segment the last
+// entry of the row's previous chunk -- and lbft_commit_timeline.h turns (entry, predecessor) into samples; the per-row quantities
+// (longest interval, last instant, first instant at or after `since`) are segment reductions by __shfl_xor.
+// grid = (workgroups per group, groups); a workgroup strides over the rows of its group, LBFT_TL_ROWS at a time, and bins into its
+// LDS histogram with integer atomics, in passes of LBFT_HIST_LDS_BINS bins; then one global atomic per non-zero bin per workgroup.
+// The statistics stay in registers over the whole stride, are reduced in the wavefront, then in LDS, then go out once per workgroup.
+// stalls == 0: the series (one sample per entry: its commit time; no statistics).  stalls != 0: the gap histogram and
+// stats[group * 16 + family * 4 + {samples, sum, ~min, max}].  Instances with a non-zero fault word are skipped.
+#define LBFT_TL_BLOCK 256
+#define LBFT_TL_SEG 32
+#define LBFT_TL_ROWS (LBFT_TL_BLOCK / LBFT_TL_SEG)
+#ifndef LBFT_TL_WORKGROUPS  // (a tuning build may set it: EXPERIMENTS.md "Commit timelines")
+#define LBFT_TL_WORKGROUPS 1024u
+#endif
+__global__ __launch_bounds__(LBFT_TL_BLOCK) void lbft_k_ct_timeline(Params p, const u32* __restrict__ state, const i32* __restrict__ ctimes,
+                                                                    const u32* __restrict__ grp_inst, const u32* __restrict__ grp_off, int stalls,
+                                                                    const i32* __restrict__ since_of, u32 bin_width, u32 bins,
+                                                                    unsigned long long* __restrict__ hist, unsigned long long* __restrict__ stats) {
+  __shared__ u32 h[LBFT_HIST_LDS_BINS];
+  __shared__ unsigned long long s_stat[LBFT_STALL_STATS];
+  const u32 g = blockIdx.y;
+  const u32 first = grp_inst ? grp_off[g] : 0u, cnt = grp_inst ? grp_off[g + 1] - first : p.m;
+  const u32 rows = cnt * p.n;  // (< 2^31: lbft_batch_create bounds instances x nodes)
+  if (blockIdx.x * LBFT_TL_ROWS >= rows) return;  // (the whole workgroup: its group has fewer rows)
+  const u32 seg = threadIdx.x / LBFT_TL_SEG, k0 = threadIdx.x % LBFT_TL_SEG;
+  const i32 since = since_of ? since_of[g] : 0;
+  if (threadIdx.x < LBFT_STALL_STATS) s_stat[threadIdx.x] = 0;
+  CtlStat st[CTL_FAMILIES] = {};
+  for (u32 base = 0; base < bins; base += LBFT_HIST_LDS_BINS) {
+    const u32 span = bins - base < LBFT_HIST_LDS_BINS ? bins - base : LBFT_HIST_LDS_BINS;
+    for (u32 k = threadIdx.x; k < span; k += LBFT_TL_BLOCK) h[k] = 0;
+    __syncthreads();
+    // What a row starts from -- its first chunk, the instance's fault word, the node's commit count -- is loaded one row ahead, all
+    // three together (none waits for another), and most rows are one chunk: the loads of the next row are in flight while this one is
+    // turned into samples.
+    const u32 stride = gridDim.x * LBFT_TL_ROWS;
+    const i32* ct_next = nullptr;
+    i32 head_next = -1;
+    u32 fault_next = 1, nc_next = 0;
+    auto fetch = [&](u32 r) {
+      const u32 node = r % p.n, i = grp_inst ? grp_inst[first + r / p.n] : r / p.n;
+      ct_next = ctimes + ((size_t)i * p.n + node) * p.lcap;
+      head_next = k0 < p.lcap ? ct_next[k0] : -1;
+      Sim s(p, const_cast<u32*>(state), i);
+      fault_next = s.ld(I_FAULT);
+      nc_next = s.nfm(node, NF_NCOMMITS);
+    };
+    u32 r = blockIdx.x * LBFT_TL_ROWS + seg;  // (one row per segment: uniform in it)
+    if (r < rows) fetch(r);
+    for (; r < rows; r += stride) {
+      const i32* ct = ct_next;
+      const i32 head = head_next;
+      const u32 fault = fault_next;
+      const u32 nc = nc_next < p.lcap ? nc_next : p.lcap;
+      if (r + stride < rows) fetch(r + stride);
+      if (fault != 0) continue;
+      CtlRow row = ctl_empty();
+      i32 carry = -1;  // the last entry of the row's previous chunk
+      for (u32 c0 = 0; c0 < nc; c0 += LBFT_TL_SEG) {
+        const i32 c = c0 + k0 >= nc ? -1 : c0 ? ct[c0 + k0] : head;
+        i32 prev = __shfl_up(c, 1, LBFT_TL_SEG);
+        if (k0 == 0) prev = carry;
+        carry = __shfl(c, LBFT_TL_SEG - 1, LBFT_TL_SEG);
+        u32 sample = 0;
+        bool have = false;
+        if (stalls) { sample = ctl_entry(row, c, prev, since); have = sample != 0; }
+        else { sample = (u32)c; have = c >= 0; }
+        if (have) {
+          const u32 bin = ctl_bin(sample, bin_width, bins);
+          if (bin >= base && bin - base < span) atomicAdd(&h[bin - base], 1u);
+          if (stalls && base == 0) ctl_stat_add(st[CTL_GAPS], sample);
+        }
+      }
+      if (stalls && base == 0) {
+        for (u32 d = LBFT_TL_SEG / 2; d; d >>= 1) {
+          CtlRow o;
+          o.longest = (u32)__shfl_xor((int)row.longest, (int)d, LBFT_TL_SEG);
+          o.last = __shfl_xor(row.last, (int)d, LBFT_TL_SEG);
+          o.first = (u32)__shfl_xor((int)row.first, (int)d, LBFT_TL_SEG);
+          row = ctl_merge(row, o);
+        }
+        if (k0 == 0) {  // one sample per node
+          if (row.first != LBFT_CTL_NONE) ctl_stat_add(st[CTL_FIRST], row.first);
+          ctl_stat_add(st[CTL_TAIL], ctl_tail(row, p.max_clock));
+          ctl_stat_add(st[CTL_LONGEST], ctl_longest(row, p.max_clock));
+        }
+      }
+    }
+    if (stalls && base == 0) {  // wavefront, then workgroup (LDS), then one global atomic per statistic
+      for (u32 f = 0; f < CTL_FAMILIES; f++) {
+        CtlStat v = st[f];
+        for (int d = 32; d; d >>= 1) {
+          const unsigned long long oc = __shfl_xor((unsigned long long)v.cnt, d, 64), os = __shfl_xor((unsigned long long)v.sum, d, 64);
+          const unsigned long long on = __shfl_xor((unsigned long long)v.nmin, d, 64), om = __shfl_xor((unsigned long long)v.max, d, 64);
+          v.cnt += oc; v.sum += os;
+          v.nmin = on > v.nmin ? on : v.nmin;
+          v.max = om > v.max ? om : v.max;
+        }
+        if (threadIdx.x % 64 == 0 && v.cnt) {
+          atomicAdd(&s_stat[f * 4 + 0], (unsigned long long)v.cnt); atomicAdd(&s_stat[f * 4 + 1], (unsigned long long)v.sum);
+          atomicMax(&s_stat[f * 4 + 2], (unsigned long long)v.nmin); atomicMax(&s_stat[f * 4 + 3], (unsigned long long)v.max);
+        }
+      }
+    }
+    __syncthreads();
+    for (u32 k = threadIdx.x; k < span; k += LBFT_TL_BLOCK)
+      if (h[k]) atomicAdd(&hist[(size_t)g * bins + base + k], (unsigned long long)h[k]);
+    if (stalls && base == 0 && threadIdx.x < LBFT_STALL_STATS && s_stat[threadIdx.x & ~3u]) {
+      if ((threadIdx.x & 3u) < 2u) atomicAdd(&stats[g * LBFT_STALL_STATS + threadIdx.x], s_stat[threadIdx.x]);
+      else atomicMax(&stats[g * LBFT_STALL_STATS + threadIdx.x], s_stat[threadIdx.x]);
+    }
+    __syncthreads();  // (before the next pass clears h)
+  }
+}
+
 extern "C" {
 
 __attribute__((visibility("default"))) hipError_t lbft_ct_launch_run(int cls, const Params* p, u32* state, u32* unfinished, const ParamSetDev* sets,
@@ -122,6 +242,23 @@ __attribute__((visibility("default"))) hipError_t lbft_ct_launch_histogram(const
   if (bin_width == 0 || bins == 0 || n_groups == 0 || max_group == 0) return hipErrorInvalidValue;
   const u32 gx = (u32)(((u64)max_group * p->n + LBFT_HIST_BLOCK - 1) / LBFT_HIST_BLOCK);
   lbft_k_ct_latency_hist<<<dim3(gx, n_groups), LBFT_HIST_BLOCK, 0, stream>>>(*p, state, ctimes, grp_inst, grp_off, bin_width, bins, hist, stats);
+  return hipGetLastError();
+}
+
+__attribute__((visibility("default"))) hipError_t lbft_ct_launch_timeline(const Params* p, const u32* state, const i32* ctimes, const u32* grp_inst,
+                                                                         const u32* grp_off, u32 n_groups, u32 max_group, int stalls,
+                                                                         const i32* since_of, u32 bin_width, u32 bins, unsigned long long* hist,
+                                                                         unsigned long long* stats, hipStream_t stream) {
+  if (bin_width == 0 || bins == 0 || n_groups == 0 || max_group == 0 || (stalls && !stats)) return hipErrorInvalidValue;
+  // about LBFT_TL_WORKGROUPS workgroups in all: each adds its LDS histogram to the global one, so fewer, longer-running workgroups mean
+  // fewer global atomics per bin.  Never so few that one could count 2^32 samples into a bin of its u32 LDS histogram.
+  const u64 rows = (u64)max_group * p->n, steps = (rows + LBFT_TL_ROWS - 1) / LBFT_TL_ROWS;
+  u64 gx = LBFT_TL_WORKGROUPS / n_groups ? LBFT_TL_WORKGROUPS / n_groups : 1;
+  const u64 least = (rows * p->lcap >> 31) + 1;
+  if (gx < least) gx = least;
+  if (gx > steps) gx = steps;
+  lbft_k_ct_timeline<<<dim3((u32)gx, n_groups), LBFT_TL_BLOCK, 0, stream>>>(*p, state, ctimes, grp_inst, grp_off, stalls, since_of, bin_width, bins, hist,
+                                                                          stats);
   return hipGetLastError();
 }
 

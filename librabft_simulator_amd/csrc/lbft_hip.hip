@@ -24,6 +24,7 @@
 #include "lbft_tables.h"
 #include "lbft_paramsets.h"
 #include "lbft_commit_times.h"
+#include "lbft_commit_timeline.h"
 
 using namespace lbft;
 
@@ -765,15 +766,21 @@ static int launch_init(lbft_batch* b, u32 grid_init) {
 static std::mutex g_ct_mutex;
 static lbft_ct_run_fn g_ct_run = nullptr;
 static lbft_ct_hist_fn g_ct_hist = nullptr;
+static lbft_ct_timeline_fn g_ct_timeline = nullptr;
 static int load_commit_times_lib() {
   std::lock_guard<std::mutex> lock(g_ct_mutex);
-  if (g_ct_run && g_ct_hist) return LBFT_OK;
+  if (g_ct_run && g_ct_hist && g_ct_timeline) return LBFT_OK;
   const std::string path = side_lib_path(LBFT_COMMIT_TIMES_LIB);
   void* h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
   if (!h) { const char* e = dlerror(); g_err = "commit times need " + path + " (build it with librabft_simulator_amd.build): " + (e ? e : "not found"); return LBFT_ERR_UNSUPPORTED; }
   g_ct_run = reinterpret_cast<lbft_ct_run_fn>(dlsym(h, "lbft_ct_launch_run"));
   g_ct_hist = reinterpret_cast<lbft_ct_hist_fn>(dlsym(h, "lbft_ct_launch_histogram"));
-  if (!g_ct_run || !g_ct_hist) { g_ct_run = nullptr; g_ct_hist = nullptr; g_err = path + " lacks lbft_ct_launch_run / lbft_ct_launch_histogram"; return LBFT_ERR_UNSUPPORTED; }
+  g_ct_timeline = reinterpret_cast<lbft_ct_timeline_fn>(dlsym(h, "lbft_ct_launch_timeline"));
+  if (!g_ct_run || !g_ct_hist || !g_ct_timeline) {
+    g_ct_run = nullptr; g_ct_hist = nullptr; g_ct_timeline = nullptr;
+    g_err = path + " lacks lbft_ct_launch_run / lbft_ct_launch_histogram / lbft_ct_launch_timeline";
+    return LBFT_ERR_UNSUPPORTED;
+  }
   return LBFT_OK;
 }
 // The run kernels of the side libraries: a parameter-set batch's (lbft_k_ps_run0 / 1) or, recording commit times, a plain or
@@ -1687,18 +1694,15 @@ int lbft_batch_commit_times(const lbft_batch* b, int64_t* out, size_t cap_per_no
   return LBFT_OK;
 }
 
-// Commit-latency histogram per group (the batch's parameter sets, or one group), computed on the device (lbft_k_ct_latency_hist).
-int lbft_batch_commit_latency_histogram(const lbft_batch* b, uint32_t bin_width, uint32_t bins, uint64_t* hist, uint64_t* stats) {
-  if (!b || !hist || !stats || bin_width == 0 || bins == 0) { g_err = "NULL argument, or bin_width / bins of 0"; return LBFT_ERR_INVALID; }
-  const size_t groups = b->psets.empty() ? 1 : b->psets.size();
-  if ((u64)groups * bins > (1ULL << 31)) { g_err = "groups x bins exceeds 2^31"; return LBFT_ERR_INVALID; }
-  if (!b->ctimes) { g_err = "the batch does not record commit times (lbft_batch_record_commit_times)"; return LBFT_ERR_STATE; }
-  if (!b->ran) { g_err = "run the batch first"; return LBFT_ERR_STATE; }
-  HIP_TRY(hipSetDevice(b->device));
-  // the instances of each group, in instance order (a parameter-set batch; a plain batch is one group of every instance)
-  std::vector<u32> off(groups + 1, 0), inst;
-  u32 max_group = (u32)b->m;
-  if (!b->psets.empty()) {
+// The groups of the commit-time statistics: the batch's parameter sets, or one group of every instance for a plain batch (which needs no
+// index: the kernels take NULL).  inst lists the instances of group g, in instance order, at [off[g], off[g + 1]).
+struct GroupIndex {
+  size_t groups;
+  std::vector<u32> off, inst;
+  u32 max_group;  // instances of the largest group
+  u32 *d_inst = nullptr, *d_off = nullptr;
+  explicit GroupIndex(const lbft_batch* b) : groups(b->psets.empty() ? 1 : b->psets.size()), off(groups + 1, 0), max_group((u32)b->m) {
+    if (b->psets.empty()) return;
     for (u8 v : b->set_of) off[v + 1]++;
     for (size_t g = 0; g < groups; g++) off[g + 1] += off[g];
     inst.resize(b->m);
@@ -1707,25 +1711,91 @@ int lbft_batch_commit_latency_histogram(const lbft_batch* b, uint32_t bin_width,
     max_group = 0;
     for (size_t g = 0; g < groups; g++) max_group = std::max(max_group, off[g + 1] - off[g]);
   }
+  GroupIndex(const GroupIndex&) = delete;
+  GroupIndex& operator=(const GroupIndex&) = delete;
+  ~GroupIndex() { hipFree(d_inst); hipFree(d_off); }
+  hipError_t upload(hipStream_t stream) {
+    if (inst.empty()) return hipSuccess;
+    hipError_t e = hipMalloc(&d_inst, inst.size() * sizeof(u32));
+    if (e == hipSuccess) e = hipMalloc(&d_off, off.size() * sizeof(u32));
+    if (e == hipSuccess) e = hipMemcpyAsync(d_inst, inst.data(), inst.size() * sizeof(u32), hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_off, off.data(), off.size() * sizeof(u32), hipMemcpyHostToDevice, stream);
+    return e;
+  }
+};
+static size_t group_count(const lbft_batch* b) { return b->psets.empty() ? 1 : b->psets.size(); }
+
+// Commit-latency histogram per group (the batch's parameter sets, or one group), computed on the device (lbft_k_ct_latency_hist).
+int lbft_batch_commit_latency_histogram(const lbft_batch* b, uint32_t bin_width, uint32_t bins, uint64_t* hist, uint64_t* stats) {
+  if (!b || !hist || !stats || bin_width == 0 || bins == 0) { g_err = "NULL argument, or bin_width / bins of 0"; return LBFT_ERR_INVALID; }
+  const size_t groups = group_count(b);
+  if ((u64)groups * bins > (1ULL << 31)) { g_err = "groups x bins exceeds 2^31"; return LBFT_ERR_INVALID; }
+  if (!b->ctimes) { g_err = "the batch does not record commit times (lbft_batch_record_commit_times)"; return LBFT_ERR_STATE; }
+  if (!b->ran) { g_err = "run the batch first"; return LBFT_ERR_STATE; }
+  HIP_TRY(hipSetDevice(b->device));
+  GroupIndex gi(b);
   const size_t hist_bytes = groups * bins * sizeof(u64), stats_bytes = groups * 4 * sizeof(u64);
   unsigned long long *d_hist = nullptr, *d_stats = nullptr;
-  u32 *d_inst = nullptr, *d_off = nullptr;
   hipError_t e = hipMalloc(&d_hist, hist_bytes);
   if (e == hipSuccess) e = hipMalloc(&d_stats, stats_bytes);
-  if (e == hipSuccess && !inst.empty()) e = hipMalloc(&d_inst, inst.size() * sizeof(u32));
-  if (e == hipSuccess && !inst.empty()) e = hipMalloc(&d_off, off.size() * sizeof(u32));
-  if (e == hipSuccess && d_inst) e = hipMemcpyAsync(d_inst, inst.data(), inst.size() * sizeof(u32), hipMemcpyHostToDevice, b->stream);
-  if (e == hipSuccess && d_off) e = hipMemcpyAsync(d_off, off.data(), off.size() * sizeof(u32), hipMemcpyHostToDevice, b->stream);
+  if (e == hipSuccess) e = gi.upload(b->stream);
   if (e == hipSuccess) e = hipMemsetAsync(d_hist, 0, hist_bytes, b->stream);
   if (e == hipSuccess) e = hipMemsetAsync(d_stats, 0, stats_bytes, b->stream);
-  if (e == hipSuccess) e = g_ct_hist(&b->p, b->d_state, b->d_ctimes, d_inst, d_off, (u32)groups, max_group, bin_width, bins, d_hist, d_stats, b->stream);
+  if (e == hipSuccess) e = g_ct_hist(&b->p, b->d_state, b->d_ctimes, gi.d_inst, gi.d_off, (u32)groups, gi.max_group, bin_width, bins, d_hist, d_stats, b->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(hist, d_hist, hist_bytes, hipMemcpyDeviceToHost, b->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(stats, d_stats, stats_bytes, hipMemcpyDeviceToHost, b->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
-  hipFree(d_hist); hipFree(d_stats); hipFree(d_inst); hipFree(d_off);
+  hipFree(d_hist); hipFree(d_stats);
   if (e != hipSuccess) return hip_fail(e, "commit latency histogram");
   for (size_t g = 0; g < groups; g++) stats[g * 4 + 2] = stats[g * 4] ? ~stats[g * 4 + 2] : 0;  // (the kernel accumulates max(~latency))
   return LBFT_OK;
+}
+
+// Commit timelines per group, computed on the device from the commit-time rows alone (lbft_k_ct_timeline): the series (stats == NULL)
+// or the stall statistics.  Arguments are checked before the first HIP call, `since` before anything is written.
+static int commit_timeline(const lbft_batch* b, const int64_t* since, uint32_t bin_width, uint32_t bins, uint64_t* hist, uint64_t* stats,
+                           const char* what) {
+  const size_t groups = group_count(b);
+  if ((u64)groups * bins > (1ULL << 31)) { g_err = "groups x bins exceeds 2^31"; return LBFT_ERR_INVALID; }
+  if (!b->ctimes) { g_err = "the batch does not record commit times (lbft_batch_record_commit_times)"; return LBFT_ERR_STATE; }
+  if (!b->ran) { g_err = "run the batch first"; return LBFT_ERR_STATE; }
+  std::vector<i32> since_of;
+  if (since) {
+    since_of.resize(groups);
+    for (size_t g = 0; g < groups; g++) {
+      if (since[g] < 0 || since[g] > (int64_t)b->p.max_clock) { g_err = "since[" + std::to_string(g) + "] outside [0, max_clock]"; return LBFT_ERR_INVALID; }
+      since_of[g] = (i32)since[g];
+    }
+  }
+  HIP_TRY(hipSetDevice(b->device));
+  GroupIndex gi(b);
+  const size_t hist_bytes = groups * bins * sizeof(u64), stats_bytes = stats ? groups * LBFT_STALL_STATS * sizeof(u64) : 0;
+  unsigned long long *d_hist = nullptr, *d_stats = nullptr;
+  i32* d_since = nullptr;
+  hipError_t e = hipMalloc(&d_hist, hist_bytes);
+  if (e == hipSuccess && stats) e = hipMalloc(&d_stats, stats_bytes);
+  if (e == hipSuccess && since) e = hipMalloc(&d_since, groups * sizeof(i32));
+  if (e == hipSuccess) e = gi.upload(b->stream);
+  if (e == hipSuccess && since) e = hipMemcpyAsync(d_since, since_of.data(), groups * sizeof(i32), hipMemcpyHostToDevice, b->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(d_hist, 0, hist_bytes, b->stream);
+  if (e == hipSuccess && stats) e = hipMemsetAsync(d_stats, 0, stats_bytes, b->stream);
+  if (e == hipSuccess) e = g_ct_timeline(&b->p, b->d_state, b->d_ctimes, gi.d_inst, gi.d_off, (u32)groups, gi.max_group, stats ? 1 : 0, d_since, bin_width, bins,
+                                         d_hist, d_stats, b->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(hist, d_hist, hist_bytes, hipMemcpyDeviceToHost, b->stream);
+  if (e == hipSuccess && stats) e = hipMemcpyAsync(stats, d_stats, stats_bytes, hipMemcpyDeviceToHost, b->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+  hipFree(d_hist); hipFree(d_stats); hipFree(d_since);
+  if (e != hipSuccess) return hip_fail(e, what);
+  for (size_t q = 0; stats && q < groups * CTL_FAMILIES; q++) stats[q * 4 + 2] = stats[q * 4] ? ~stats[q * 4 + 2] : 0;  // (max(~sample) -> min)
+  return LBFT_OK;
+}
+int lbft_batch_commit_series(const lbft_batch* b, uint32_t bin_width, uint32_t bins, uint64_t* series) {
+  if (!b || !series || bin_width == 0 || bins == 0) { g_err = "NULL argument, or bin_width / bins of 0"; return LBFT_ERR_INVALID; }
+  return commit_timeline(b, nullptr, bin_width, bins, series, nullptr, "commit series");
+}
+int lbft_batch_commit_stalls(const lbft_batch* b, const int64_t* since, uint32_t bin_width, uint32_t bins, uint64_t* hist, uint64_t* stats) {
+  if (!b || !hist || !stats || bin_width == 0 || bins == 0) { g_err = "NULL argument, or bin_width / bins of 0"; return LBFT_ERR_INVALID; }
+  return commit_timeline(b, since, bin_width, bins, hist, stats, "commit stalls");
 }
 
 int lbft_batch_committed_history(const lbft_batch* b, size_t inst, uint32_t node, lbft_commit* out, size_t cap, size_t* len) {

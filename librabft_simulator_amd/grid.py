@@ -7,6 +7,11 @@ runs ``--seeds-per-point`` networks of ``--nodes`` nodes to ``--max-clock``, all
 Seeds are first-seed .. first-seed + seeds-per-point - 1 for every point.  Prints one JSON line per grid point; with ``--latency`` the
 batch records commit times and each line gains a ``"latency"`` object (BatchResult.latency_by_param_set: samples, mean, min, max and
 the 0.5 / 0.9 / 0.99 quantiles of the commit latency over every node's commits of the point's instances).
+``--partition SIZE:START:END[,SIZE:START:END...]`` is one more grid axis (nodes [0, SIZE) are cut off during [START, END); ``none`` is a
+value too); the lines then carry a ``"partition"`` key.  ``--stalls`` records commit times and adds a ``"stalls"`` object
+(BatchResult.stalls_by_param_set with ``since="partition_end"``: gaps between a node's commits, time from the partition's end to the next
+commit, time since the last commit, longest commit-free interval); ``--series WIDTH`` adds ``"series"``, the point's commits per WIDTH
+ticks (BatchResult.commit_series).
 """
 import argparse
 import itertools
@@ -27,10 +32,34 @@ def _ints(text):
     return [int(v) for v in text.split(",") if v.strip()]
 
 
+def _partitions(text):
+    """``SIZE:START:END`` items or ``none``, comma separated: a list of (size, start, end) tuples and None."""
+    out = []
+    for item in text.split(","):
+        item = item.strip()
+        if not item:
+            continue
+        if item.lower() == "none":
+            out.append(None)
+            continue
+        parts = item.split(":")
+        if len(parts) != 3:
+            raise argparse.ArgumentTypeError("a partition is SIZE:START:END or none, not %r" % item)
+        try:
+            out.append(tuple(int(v) for v in parts))
+        except ValueError:
+            raise argparse.ArgumentTypeError("a partition is SIZE:START:END or none, not %r" % item)
+    if not out:
+        raise argparse.ArgumentTypeError("--partition needs at least one value")
+    return out
+
+
 def grid_points(args):
-    """The grid's points in output order (the last option varies fastest)."""
+    """The grid's points in output order (the last option varies fastest).  The partition is an axis, and a key, only when given."""
     keys = ("mean", "variance", "delta", "gamma", "lambda", "target_commit_interval", "drop_per_million")
     values = (args.mean, args.variance, args.delta, args.gamma, args.lambda_, args.target_commit_interval, args.drop_per_million)
+    if getattr(args, "partition", None) is not None:
+        keys, values = keys + ("partition",), values + (args.partition,)
     return [dict(zip(keys, combo)) for combo in itertools.product(*values)]
 
 
@@ -59,7 +88,12 @@ def main(argv=None):
     ap.add_argument("--assign", choices=("blocked", "interleaved"), default="blocked")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--latency", action="store_true", help="record commit times and add each point's commit-latency summary")
+    ap.add_argument("--partition", type=_partitions, default=None, help="grid axis: SIZE:START:END[,...], 'none' allowed as a value")
+    ap.add_argument("--stalls", action="store_true", help="record commit times and add each point's stall / recovery summary")
+    ap.add_argument("--series", type=int, default=None, metavar="WIDTH", help="record commit times and add each point's commits per WIDTH ticks")
     args = ap.parse_args(argv)
+    if args.series is not None and args.series < 1:
+        ap.error("--series WIDTH must be at least 1")
     points = grid_points(args)
     if not 1 <= len(points) <= MAX_PARAM_SETS:
         ap.error("the grid has %d points; 1 to %d fit one batch" % (len(points), MAX_PARAM_SETS))
@@ -67,19 +101,25 @@ def main(argv=None):
         ap.error("--seeds-per-point must be at least 1")
     sets = [ParamSet(RandomDelay.new(pt["mean"], pt["variance"]),
                      NodeConfig(target_commit_interval=pt["target_commit_interval"], delta=pt["delta"], gamma=pt["gamma"], lambda_=pt["lambda"]),
-                     drop_per_million=pt["drop_per_million"]) for pt in points]
+                     drop_per_million=pt["drop_per_million"], partition=pt.get("partition")) for pt in points]
     set_of, seed_index = set_assignment(len(points), args.seeds_per_point, args.assign)
     seeds = (args.first_seed + seed_index).astype(np.uint64)
-    kw = {"commit_times": True} if args.latency else {}
+    kw = {"commit_times": True} if args.latency or args.stalls or args.series is not None else {}
     sim = BatchSimulator.with_param_sets(seeds, args.nodes, sets, set_of, commands_per_epoch=args.commands_per_epoch, device=args.device, **kw)
     try:
         res = sim.loop_until(args.max_clock, allow_faults=True)
         latency = res.latency_by_param_set() if args.latency else None
+        stalls = res.stalls_by_param_set(since="partition_end") if args.stalls else None
+        series = res.commit_series(bin_width=args.series) if args.series is not None else None
         for k, (pt, row) in enumerate(zip(points, res.by_param_set())):
             line = dict(pt, nodes=args.nodes, max_clock=args.max_clock, seeds=args.seeds_per_point, assign=args.assign)
             line.update(instances=row["instances"], faulted=row["faulted"], commits=row["commits"], rounds=row["rounds"])
             if latency is not None:
                 line["latency"] = latency[k]
+            if stalls is not None:
+                line["stalls"] = stalls[k]
+            if series is not None:
+                line["series"] = [int(v) for v in series[k]]
             print(json.dumps(line), flush=True)
     finally:
         sim.close()

@@ -319,17 +319,11 @@ class BatchResult:
         ``stats[group] = (samples, sum, min, max)`` (uint64).  One sample per (instance, node, committed entry) of the instances without a
         fault; latency = commit time - (startup_times[proposer] + time).  The defaults are exact: width 1 and max_clock + 1 bins while
         that is at most 65 536 bins, above that the smallest width that fits."""
-        if (bin_width is not None and int(bin_width) < 1) or (bins is not None and int(bins) < 1):
-            raise ValueError("bin_width and bins must be at least 1")
-        span = int(self._sim._max_clock) + 1
-        if bin_width is None:
-            bin_width = -(-span // int(bins)) if bins else max(1, -(-span // (1 << 16)))
-        if bins is None:
-            bins = -(-span // int(bin_width))
-        groups = len(self._sim.param_sets) if self._sim.param_sets is not None else 1
-        hist = np.zeros((groups, int(bins)), dtype=np.uint64)
+        bin_width, bins = self._binning(bin_width, bins)
+        groups = self._groups()
+        hist = np.zeros((groups, bins), dtype=np.uint64)
         stats = np.zeros((groups, 4), dtype=np.uint64)
-        check(_lib.lib().lbft_batch_commit_latency_histogram(self._sim._h, int(bin_width), int(bins), hist.ctypes.data, stats.ctypes.data))
+        check(_lib.lib().lbft_batch_commit_latency_histogram(self._sim._h, bin_width, bins, hist.ctypes.data, stats.ctypes.data))
         return hist, stats
 
     def latency_by_param_set(self, quantiles=(0.5, 0.9, 0.99)):
@@ -346,6 +340,84 @@ class BatchResult:
             row = {"set": g, "samples": n, "mean": float(stats[g, 1]) / n if n else None, "min": int(stats[g, 2]) if n else None,
                    "max": int(stats[g, 3]) if n else None}
             row["quantiles"] = {str(q): histogram_quantile(hist[g], width, q) for q in quantiles}
+            out.append(row)
+        return out
+
+    def _binning(self, bin_width, bins):
+        """(bin_width, bins) with ``latency_histogram``'s defaults: width 1 and max_clock + 1 bins while that is at most 65 536 bins,
+        above that the smallest width that fits.  ValueError below 1, before any library call."""
+        if (bin_width is not None and int(bin_width) < 1) or (bins is not None and int(bins) < 1):
+            raise ValueError("bin_width and bins must be at least 1")
+        span = int(self._sim._max_clock) + 1
+        if bin_width is None:
+            bin_width = -(-span // int(bins)) if bins else max(1, -(-span // (1 << 16)))
+        if bins is None:
+            bins = -(-span // int(bin_width))
+        return int(bin_width), int(bins)
+
+    def _groups(self):
+        return len(self._sim.param_sets) if self._sim.param_sets is not None else 1
+
+    def _since(self, since):
+        """``since`` of ``stall_histogram`` as one int64 per group (None: every group from clock 0)."""
+        groups, max_clock = self._groups(), int(self._sim._max_clock)
+        if since is None:
+            return None
+        if isinstance(since, str):
+            if since != "partition_end":
+                raise ValueError("since: None, an int, one int per group or 'partition_end'")
+            sets = self._sim.param_sets
+            parts = [ps.partition for ps in sets] if sets is not None else [getattr(self._sim, "partition", None)]
+            return np.array([0 if p is None or p[0] == 0 else min(max(int(p[2]), 0), max_clock) for p in parts], dtype=np.int64)
+        if np.ndim(since) == 0:
+            since = [since] * groups
+        if len(since) != groups:
+            raise ValueError("since needs one entry per group (%d)" % groups)
+        out = np.array([int(v) for v in since], dtype=np.int64).reshape(groups)
+        if ((out < 0) | (out > max_clock)).any():
+            raise ValueError("since must lie in [0, max_clock]")
+        return out
+
+    def commit_series(self, bin_width=None, bins=None):
+        """Commits over time, computed on the device from the recorded commit times: ``[groups, bins]`` uint64,
+        ``series[group, min(commit time // bin_width, bins - 1)]`` counts every committed entry of every node of the group's instances
+        without a fault (a row sums to ``latency_histogram``'s sample count).  Groups and default binning as ``latency_histogram``."""
+        bin_width, bins = self._binning(bin_width, bins)
+        series = np.zeros((self._groups(), bins), dtype=np.uint64)
+        check(_lib.lib().lbft_batch_commit_series(self._sim._h, bin_width, bins, series.ctypes.data))
+        return series
+
+    def stall_histogram(self, since=None, bin_width=None, bins=None):
+        """Commit-free intervals, computed on the device: ``(hist, stats)``.  A node's commit instants are its distinct commit times; they
+        cut [0, max_clock] into intervals.  ``hist[group, min(gap // bin_width, bins - 1)]`` counts the gaps between consecutive instants
+        of a node; ``stats[group]`` (16 uint64) holds ``(samples, sum, min, max)`` of four families: the gaps, ``first`` (per node, from
+        ``since`` to its first instant at or after it, if any), ``tail`` (per node, max_clock - its last instant; max_clock without
+        commits) and ``longest`` (per node, its longest interval, the leading one and the tail included).  ``since``: None (0), one
+        int, one per group, or ``"partition_end"`` -- each set's (or the batch's) partition end clipped to [0, max_clock], 0 without a
+        partition: ``first`` is then the recovery time.  Instances with a fault are skipped; binning as ``latency_histogram``."""
+        bin_width, bins = self._binning(bin_width, bins)
+        since = self._since(since)
+        groups = self._groups()
+        hist = np.zeros((groups, bins), dtype=np.uint64)
+        stats = np.zeros((groups, _lib.STALL_STATS), dtype=np.uint64)
+        check(_lib.lib().lbft_batch_commit_stalls(self._sim._h, None if since is None else since.ctypes.data, bin_width, bins,
+                                                  hist.ctypes.data, stats.ctypes.data))
+        return hist, stats
+
+    def stalls_by_param_set(self, since=None, quantiles=(0.5, 0.9, 0.99)):
+        """Per group of ``stall_histogram`` (default, exact binning), in set order: ``since``, ``gaps`` = samples, mean, min, max and
+        ``quantiles`` ({str(q): gap}, the inverted-CDF rule of ``histogram_quantile``), and ``first`` / ``tail`` / ``longest`` = nodes,
+        mean, min, max.  ``None`` where there are no samples."""
+        width, _ = self._binning(None, None)
+        since = self._since(since)
+        hist, stats = self.stall_histogram(since)
+        out = []
+        for g in range(hist.shape[0]):
+            row = {"set": g, "since": int(since[g]) if since is not None else 0}
+            for f, (name, count) in enumerate((("gaps", "samples"), ("first", "nodes"), ("tail", "nodes"), ("longest", "nodes"))):
+                n, total, lo, hi = (int(v) for v in stats[g, 4 * f:4 * f + 4])
+                row[name] = {count: n, "mean": total / n if n else None, "min": lo if n else None, "max": hi if n else None}
+            row["gaps"]["quantiles"] = {str(q): histogram_quantile(hist[g], width, q) for q in quantiles}
             out.append(row)
         return out
 
@@ -389,6 +461,7 @@ class BatchSimulator:
                                 rights_rotation)
         self._h = C.c_void_p()
         self.param_sets = None
+        self.partition = None if partition is None else tuple(int(v) for v in partition)
         self._max_clock = 0
         if _param_sets is None:
             check(_lib.lib().lbft_batch_create(C.byref(self._cfg), seeds.ctypes.data, self.num_instances, self.device,
