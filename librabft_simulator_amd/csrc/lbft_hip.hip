@@ -1111,7 +1111,8 @@ int lbft_node_view_get(lbft_batch* b, size_t inst, uint32_t node, lbft_node_view
 
 int lbft_batch_enable_round_trace(lbft_batch* b, uint32_t max_rounds) {
   if (!b) return LBFT_ERR_INVALID;
-  if (b->ran || b->manual) { g_err = "enable the round trace before running the batch"; return LBFT_ERR_STATE; }
+  // (a run in pieces counts from its first piece: the trace rows are part of the layout Simulator::new ran on)
+  if (b->ran || b->manual || b->started) { g_err = "enable the round trace before running the batch"; return LBFT_ERR_STATE; }
   b->rcap = max_rounds;
   return LBFT_OK;
 }

@@ -2,7 +2,9 @@
 // for the host so that the compact structural model the HIP kernels execute can be differential-tested
 // against the full-fidelity oracle on CPU-only machines (tests/test_host_model.py).  It is never linked
 // into the product library and never used as a fallback.
+#include <atomic>
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 #include <thread>
 #include <type_traits>
@@ -31,8 +33,12 @@ static size_t* g_image_lens = nullptr;
 // (load_node_image, what lbft_batch_load_node runs): 0 = the second image equals the first byte for byte, 1 = it differs, < 0 = the loader's code
 static int* g_roundtrip = nullptr;
 
+// What the last lbft_hostmodel_run_batch ran as (test hook): the KernelClass of the step | cooperative event loop << 8 | heap << 9 | calendar << 10
+static std::atomic<uint32_t> g_last_class{0};
+
 extern "C" {
 
+uint32_t lbft_hostmodel_last_class(void) { return g_last_class.load(); }
 void lbft_hostmodel_capture_node_images(uint8_t* buf, size_t stride, size_t* lens) { g_image_buf = buf; g_image_stride = stride; g_image_lens = lens; }
 void lbft_hostmodel_roundtrip_node_images(int* results) { g_roundtrip = results; }
 
@@ -47,7 +53,24 @@ typedef struct lbft_hostmodel_caps {
   uint32_t ring_topup;     // draws the generator runs ahead per step
   uint32_t tw;             // tile width of the state layout (0 = 64; the device uses the lanes per wavefront outside kernel class 0)
   uint32_t keep_stores;    // lbft_batch_keep_retired_stores: the retired record stores are archived in full
+  uint32_t state_fill;     // the word the state rows and the emulated LDS hold before Simulator::new runs (0 = fresh pages; anything else stands for a used batch's leftovers)
 } lbft_hostmodel_caps;
+
+// A caller built against an earlier lbft_hostmodel_caps passes a shorter struct: fields past the size it declared (lbft_hostmodel_caps_size; without
+// the call, the struct as it was before state_fill) read as 0 instead of as whatever follows the caller's struct in memory.
+static std::atomic<size_t> g_caps_size{offsetof(lbft_hostmodel_caps, state_fill)};
+static u32 caps_state_fill(const lbft_hostmodel_caps* caps) {
+  return g_caps_size.load() >= offsetof(lbft_hostmodel_caps, state_fill) + sizeof(uint32_t) ? caps->state_fill : 0;
+}
+
+// What the device's memory holds when the init kernel starts: `fill` in every state word -- the leftovers of an earlier run, or of another batch -- except the
+// rows the device's host code clears before every run (lbft_hip.hip zero_calendar: the calendar's head / tail / bitmap rows, off_cal_head .. off_snap).
+static void dirty_state(const Params& p, std::vector<u32>& state, u32 fill) {
+  state.assign(state_words(p), fill);
+  if (!fill || !p.qcal) return;
+  for (u32 i = 0; i < p.stride; i++)
+    for (u32 w = p.off_cal_head; w < p.off_snap; w++) state[word_offset(p, i, w)] = 0;
+}
 
 // The Params of a host-model batch and the tables they point into.  `manual`: the capacities of a node-level session
 // (lbft_batch_manual_begin) rather than of a run.
@@ -126,6 +149,8 @@ static int setup_params(const lbft_oracle_config* cfg, const lbft_hostmodel_caps
 }
 
 // Same outputs as lbft_oracle_run_batch, plus per-instance fault words and max queue/snapshot use.
+void lbft_hostmodel_caps_size(size_t bytes) { g_caps_size.store(bytes); }  // sizeof(lbft_hostmodel_caps) as the caller declares it
+
 int lbft_hostmodel_run_batch(const lbft_oracle_config* cfg, const lbft_hostmodel_caps* caps, const uint64_t* seeds,
                              size_t n_instances, int64_t max_clock, uint32_t threads, uint32_t* commit_counts,
                              uint64_t* active_rounds, uint64_t* last_states, lbft_oracle_commit* histories,
@@ -137,25 +162,31 @@ int lbft_hostmodel_run_batch(const lbft_oracle_config* cfg, const lbft_hostmodel
   if (int rc = setup_params(cfg, caps, n_instances, max_clock, false, host)) return rc;
   Params& p = host.p;
   std::vector<u32>& weights = host.weights;
-  std::vector<u32> state(state_words(p), 0);
+  const u32 fill = caps_state_fill(caps);
+  const u64 fill64 = ((u64)fill << 32) | fill;
+  std::vector<u32> state;
 
   if (threads == 0) threads = 1;
   if (p.n > 32) p.qheap = 1;  // as the device host code does
   // the step runs as the size class the device would pick (SimT<0..2>); init and read-back use the generic class
   auto run_one = [&](auto& s, size_t i) {
-    std::vector<u64> keys(p.ql ? p.ql : 1);
-    std::vector<u32> metas(p.ql ? p.ql : 1);
+    // (the emulated LDS starts as the state does: on the device it holds the previous kernel's leftovers)
+    std::vector<u64> keys(p.ql ? p.ql : 1, fill64);
+    std::vector<u32> metas(p.ql ? p.ql : 1, fill);
     s.attach_queue(keys.data(), metas.data(), 1, p.ql);
-    std::vector<u32> hcbr(32);  // the device's LDS copy of the hcbr buffers (class 0, n <= 4)
+    std::vector<u32> hcbr(32, fill);  // the device's LDS copy of the hcbr buffers (class 0, n <= 4)
     if (p.ql) s.attach_hcbr(hcbr.data());
-    std::vector<u32> window(32 * (1 + BC_WORDS), 0);  // the large-network kernels' LDS window of block records (32 entries, as the device's default)
+    std::vector<u32> window(32 * (1 + BC_WORDS), fill);  // the large-network kernels' LDS window of block records (32 entries, as the device's default)
     if (p.n > 32) s.attach_blk_window(window.data(), 32, 0);
     s.load_scalars();
     s.queue_to_lds();
     s.hcbr_to_lds();
     bool done;
-    if constexpr (std::remove_reference<decltype(s)>::type::COOP) done = p.ring ? s.run_coop(true) : s.run();
+    using S = typename std::remove_reference<decltype(s)>::type;
+    bool coop = false;
+    if constexpr (S::COOP) { coop = p.ring != 0; done = coop ? s.run_coop(true) : s.run(); }
     else done = s.run();
+    g_last_class.store((uint32_t)S::CLS | (coop ? 256u : 0u) | (p.qheap ? 512u : 0u) | (p.qcal ? 1024u : 0u));
     s.queue_from_lds();
     s.hcbr_from_lds();
     s.store_scalars(done);
@@ -166,6 +197,7 @@ int lbft_hostmodel_run_batch(const lbft_oracle_config* cfg, const lbft_hostmodel
     p.rsh = 2;
     while ((1u << p.rsh) < 4u * p.tw) p.rsh++;
   }
+  dirty_state(p, state, fill);
   auto worker = [&](u32 tid) {
     for (size_t i = tid; i < n_instances; i += threads) {
       { Sim s0(p, state.data(), (u32)i); s0.init(seeds[i]); }
@@ -232,7 +264,15 @@ int lbft_hostmodel_run_batch(const lbft_oracle_config* cfg, const lbft_hostmodel
             // (the request words of a response slot -- sqw -- are not part of a store summary; a skipped epoch id has no entry)
             u32 within = q % hp.snap_words;
             if (within >= S_FIXED_WORDS + 2 * hp.n + 2 * (hp.mw - 1)) continue;
-            if (h2[arch0 + q] != hw[arch0 + q]) g_roundtrip[k] = 3;
+            // (an author's hcbr word is written, by the run and by the loader, only when the author is in the entry's set -- the record exchange reads
+            // it through the mask: outside the sets the run's rows keep what the memory held before, and the loader must have left the scrubbed 0)
+            bool in_set = true;
+            if (within >= S_FIXED_WORDS && within < S_FIXED_WORDS + 2 * hp.n) {
+              const u32 e0 = arch0 + q - within, a = (within - S_FIXED_WORDS) % hp.n, to = within >= S_FIXED_WORDS + hp.n ? 1u : 0u, w = a >> 5;
+              const u32 mask = hw[e0 + (w == 0 ? (to ? (u32)S_TO_MASK : (u32)S_TC_MASK) : S_FIXED_WORDS + 2 * hp.n + to * (hp.mw - 1) + (w - 1))];
+              in_set = (mask >> (a & 31u)) & 1u;
+            }
+            if (in_set ? h2[arch0 + q] != hw[arch0 + q] : h2[arch0 + q] != 0) g_roundtrip[k] = 3;
           }
           // ... and the guard of node.rs:219-228: a node time before the image's own times is refused and nothing is written
           std::vector<u32> h3(h2);
@@ -314,7 +354,7 @@ int lbft_hostmodel_session_create(const lbft_oracle_config* cfg, const lbft_host
   if (int rc = setup_params(cfg, caps, n_instances, max_clock, true, hs->hp)) { delete hs; return rc; }
   const Params& p = hs->hp.p;
   if (!layout_fits(p.total_words)) { delete hs; return -15; }  // (lbft_batch_manual_begin: LBFT_ERR_INVALID)
-  hs->state.assign(state_words(p), 0);
+  dirty_state(p, hs->state, caps_state_fill(caps));
   for (size_t i = 0; i < n_instances; i++) { Sim s(p, hs->state.data(), (u32)i); s.init(seeds[i]); }
   hs->delta = cfg->delta; hs->tci = cfg->target_commit_interval; hs->gamma = cfg->gamma; hs->lambda = cfg->lambda;
   *out = hs;

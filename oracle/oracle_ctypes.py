@@ -93,9 +93,9 @@ _lib = None
 
 
 def build(force=False):
-    """Compile the oracle with g++ (Makefile in this directory)."""
-    if force or not os.path.exists(_LIB_PATH):
-        subprocess.check_call(["make", "-C", _HERE, "-s"] + (["-B"] if force else []))
+    """Compile the oracle and the host model with g++ (Makefile in this directory).  make runs every time: it is incremental and
+    lists the headers, so an edited source is never served by a stale library."""
+    subprocess.check_call(["make", "-C", _HERE, "-s"] + (["-B"] if force else []))
     return _LIB_PATH
 
 
@@ -364,7 +364,7 @@ def leader(num_nodes, rnd, weights=None):
 # Host build of the kernel logic (oracle/host_model.cpp) -- CPU-only differential testing.
 # ----------------------------------------------------------------------------------------------
 class HostModelCaps(C.Structure):
-    _fields_ = [("qcap", C.c_uint32), ("scap", C.c_uint32), ("bcap", C.c_uint32), ("lcap", C.c_uint32), ("ql", C.c_uint32), ("qheap", C.c_uint32), ("force_generic", C.c_uint32), ("rcap", C.c_uint32), ("qcal", C.c_uint32), ("ring", C.c_uint32), ("ring_topup", C.c_uint32), ("tw", C.c_uint32), ("keep_stores", C.c_uint32)]
+    _fields_ = [("qcap", C.c_uint32), ("scap", C.c_uint32), ("bcap", C.c_uint32), ("lcap", C.c_uint32), ("ql", C.c_uint32), ("qheap", C.c_uint32), ("force_generic", C.c_uint32), ("rcap", C.c_uint32), ("qcal", C.c_uint32), ("ring", C.c_uint32), ("ring_topup", C.c_uint32), ("tw", C.c_uint32), ("keep_stores", C.c_uint32), ("state_fill", C.c_uint32)]
 
 
 _hm = None
@@ -376,14 +376,16 @@ def hostmodel_lib():
         build()
         # LBFT_HOSTMODEL_LIB: an experimental build of the kernel logic (e.g. liblbft_hostmodel_coop0.so, `make -C oracle coop0`)
         path = os.environ.get("LBFT_HOSTMODEL_LIB") or os.path.join(_HERE, "liblbft_hostmodel.so")
-        if not os.path.exists(path):
-            subprocess.check_call(["make", "-C", _HERE, "-s"])
         L = C.CDLL(path)
         vp = C.c_void_p
         L.lbft_hostmodel_run_batch.argtypes = [
             C.POINTER(OracleConfig), C.POINTER(HostModelCaps), vp, C.c_size_t, C.c_int64, C.c_uint32, vp, vp, vp,
             vp, C.c_size_t, C.POINTER(OracleCounters), vp, vp, vp, vp, vp, vp, C.c_size_t]
         L.lbft_hostmodel_run_batch.restype = C.c_int
+        if hasattr(L, "lbft_hostmodel_caps_size"):  # (the struct grows by appending: the library reads what this binding declares, the rest as 0)
+            L.lbft_hostmodel_caps_size.argtypes = [C.c_size_t]
+            L.lbft_hostmodel_caps_size.restype = None
+            L.lbft_hostmodel_caps_size(C.sizeof(HostModelCaps))
         _hm = L
     return _hm
 
@@ -417,10 +419,12 @@ def hostmodel_node_images(cfg, seed, max_clock, roundtrip=None, **caps):
 
 
 def hostmodel_run_batch(cfg, seeds, max_clock, threads=1, history_cap=0, qcap=256, scap=128, bcap=256, lcap=256, ql=0, qheap=0, force_generic=0, rcap=0, qcal=0,
-                        hash_cap=0, ring=0, ring_topup=0, tw=0, keep_stores=0):
+                        hash_cap=0, ring=0, ring_topup=0, tw=0, keep_stores=0, state_fill=0):
+    """``state_fill``: the word every state row and the emulated LDS hold before Simulator::new runs (the device's leftovers of an earlier
+    run; the calendar's head / tail / bitmap rows are cleared as the device's host code clears them)."""
     seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
     m, nn = len(seeds), cfg.num_nodes
-    caps = HostModelCaps(qcap, scap, bcap, lcap, ql, qheap, force_generic, rcap, qcal, ring, ring_topup, tw, keep_stores)
+    caps = HostModelCaps(qcap, scap, bcap, lcap, ql, qheap, force_generic, rcap, qcal, ring, ring_topup, tw, keep_stores, state_fill)
     rs = np.zeros((m, max(rcap, 1), nn), dtype=np.int64)
     mr = np.zeros(m, dtype=np.uint32)
     commit_counts = np.zeros((m, nn), dtype=np.uint32)
@@ -469,7 +473,7 @@ class HostSession:
                    "highest_committed_round", "active_round", "latest_voted_round", "locked_round", "commit_count", "active_leader",
                    "election", "num_current_timeouts", "num_current_votes", "has_proposed_block", "has_timeout_certificate")
 
-    def __init__(self, cfg, seeds, max_clock, caps):
+    def __init__(self, cfg, seeds, max_clock, caps, state_fill=0):
         L = hostmodel_lib()
         if not hasattr(L, "_session_bound"):
             vp = C.c_void_p
@@ -492,7 +496,7 @@ class HostSession:
         self.cfg = cfg
         self.quirks = cfg.quirks
         self.caps = dict(caps)
-        hc = HostModelCaps(caps["qcap"], caps["scap"], caps["bcap"], caps["lcap"], 0, caps.get("qheap", 0), 0, 0, 0, 0, 0, caps.get("tw", 0), caps.get("keep_stores", 0))
+        hc = HostModelCaps(caps["qcap"], caps["scap"], caps["bcap"], caps["lcap"], 0, caps.get("qheap", 0), 0, 0, 0, 0, 0, caps.get("tw", 0), caps.get("keep_stores", 0), state_fill)
         seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
         self.m = len(seeds)
         self.h = C.c_void_p()

@@ -20,10 +20,11 @@ static const u64 ET[256] = LBFT_EXP_TAB_INIT;
 static i32 clamp_i32(int64_t v) { return (i32)(v < 0 ? 0 : (v > 0x7fffffff ? 0x7fffffff : v)); }
 
 template <class S>
-static void run_one(S& s, const Params& p) {
-  std::vector<u64> keys(p.ql ? p.ql : 1);
-  std::vector<u32> metas(p.ql ? p.ql : 1);
-  std::vector<u32> hcbr(32);
+static void run_one(S& s, const Params& p, u32 fill) {
+  // (the emulated LDS starts as the state rows do: on the device it holds an earlier kernel's leftovers)
+  std::vector<u64> keys(p.ql ? p.ql : 1, ((u64)fill << 32) | fill);
+  std::vector<u32> metas(p.ql ? p.ql : 1, fill);
+  std::vector<u32> hcbr(32, fill);
   s.attach_queue(keys.data(), metas.data(), 1, p.ql);
   if (p.ql) s.attach_hcbr(hcbr.data());
   s.load_scalars();
@@ -36,11 +37,11 @@ static void run_one(S& s, const Params& p) {
 }
 
 template <int KCLS>
-static void run_timed(const Params& p, u32* state, u32 i, const ParamSetDev* set, i32* ctimes) {
+static void run_timed(const Params& p, u32* state, u32 i, const ParamSetDev* set, i32* ctimes, u32 state_fill) {
   SimTTimed<KCLS> s(p, state, i);
   if constexpr (SimT<KCLS>::PSET) s.load_set(*set);
   s.attach_commit_times(ctimes, i * p.n);
-  run_one(s, p);
+  run_one(s, p, state_fill);
 }
 
 extern "C" {
@@ -50,7 +51,7 @@ extern "C" {
 // [instance][node][history_cap], startup times [instance][node], faults [instance].
 int ct_hostmodel_run(const lbft_config* base, const lbft_param_set* sets, uint32_t n_sets, const uint32_t* set_of, const uint64_t* seeds,
                      size_t m, int64_t max_clock, uint32_t threads, uint32_t* commit_counts, int64_t* commit_times, lbft_commit* histories,
-                     int64_t* startup_times, size_t history_cap, uint32_t* faults) {
+                     int64_t* startup_times, size_t history_cap, uint32_t* faults, uint32_t state_fill) {
   const u32 n = base->num_nodes;
   if (n == 0 || n > 32 || n_sets > LBFT_MAX_PARAM_SETS) return -1;
   Params p;
@@ -133,7 +134,9 @@ int ct_hostmodel_run(const lbft_config* base, const lbft_param_set* sets, uint32
   p.rsh = 2;
   while ((1u << p.rsh) < 4u * p.tw) p.rsh++;
   compute_layout(p);
-  std::vector<u32> state(state_words(p), 0);
+  // state_fill: the word the state rows and the emulated LDS hold before Simulator::new runs (0 = fresh pages; these classes never use the
+  // calendar queue, the one region the device's host code clears before a run)
+  std::vector<u32> state(state_words(p), state_fill);
   std::vector<i32> ct((size_t)m * n * p.lcap, -1);
   if (threads == 0) threads = 1;
   auto worker = [&](u32 tid) {
@@ -141,10 +144,10 @@ int ct_hostmodel_run(const lbft_config* base, const lbft_param_set* sets, uint32
       const ParamSetDev* d = &dev[n_sets ? set_of[i] : 0];
       if (n_sets) { SimTSets<K_GENERIC_SETS> s0(p, state.data(), (u32)i); s0.load_set(*d); s0.init(seeds[i]); }
       else { Sim s0(p, state.data(), (u32)i); s0.init(seeds[i]); }
-      if (n_sets && cls == K_SMALL) run_timed<K_SMALL_SETS_TIMED>(p, state.data(), (u32)i, d, ct.data());
-      else if (n_sets) run_timed<K_MID_SETS_TIMED>(p, state.data(), (u32)i, d, ct.data());
-      else if (cls == K_SMALL) run_timed<K_SMALL_TIMED>(p, state.data(), (u32)i, nullptr, ct.data());
-      else run_timed<K_MID_TIMED>(p, state.data(), (u32)i, nullptr, ct.data());
+      if (n_sets && cls == K_SMALL) run_timed<K_SMALL_SETS_TIMED>(p, state.data(), (u32)i, d, ct.data(), state_fill);
+      else if (n_sets) run_timed<K_MID_SETS_TIMED>(p, state.data(), (u32)i, d, ct.data(), state_fill);
+      else if (cls == K_SMALL) run_timed<K_SMALL_TIMED>(p, state.data(), (u32)i, nullptr, ct.data(), state_fill);
+      else run_timed<K_MID_TIMED>(p, state.data(), (u32)i, nullptr, ct.data(), state_fill);
     }
   };
   std::vector<std::thread> ts;

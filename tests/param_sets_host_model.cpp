@@ -20,10 +20,11 @@ static const u64 ET[256] = LBFT_EXP_TAB_INIT;
 static i32 clamp_i32(int64_t v) { return (i32)(v < 0 ? 0 : (v > 0x7fffffff ? 0x7fffffff : v)); }
 
 template <class S>
-static void run_one(S& s, const Params& p) {
-  std::vector<u64> keys(p.ql ? p.ql : 1);
-  std::vector<u32> metas(p.ql ? p.ql : 1);
-  std::vector<u32> hcbr(32);
+static void run_one(S& s, const Params& p, u32 fill) {
+  // (the emulated LDS starts as the state rows do: on the device it holds an earlier kernel's leftovers)
+  std::vector<u64> keys(p.ql ? p.ql : 1, ((u64)fill << 32) | fill);
+  std::vector<u32> metas(p.ql ? p.ql : 1, fill);
+  std::vector<u32> hcbr(32, fill);
   s.attach_queue(keys.data(), metas.data(), 1, p.ql);
   if (p.ql) s.attach_hcbr(hcbr.data());
   s.load_scalars();
@@ -40,7 +41,7 @@ extern "C" {
 // Returns the kernel class the batch ran as (K_SMALL or K_MID), < 0 on a bad argument.  Outputs as lbft_hostmodel_run_batch.
 int ps_hostmodel_run(const lbft_config* base, const lbft_param_set* sets, uint32_t n_sets, const uint32_t* set_of, const uint64_t* seeds,
                      size_t m, int64_t max_clock, uint32_t threads, uint32_t* commit_counts, uint64_t* active_rounds, uint64_t* last_states,
-                     lbft_commit* histories, size_t history_cap, uint32_t* faults) {
+                     lbft_commit* histories, size_t history_cap, uint32_t* faults, uint32_t state_fill) {
   const u32 n = base->num_nodes;
   if (n == 0 || n > 32 || n_sets == 0 || n_sets > LBFT_MAX_PARAM_SETS) return -1;
   Params p;
@@ -104,14 +105,16 @@ int ps_hostmodel_run(const lbft_config* base, const lbft_param_set* sets, uint32
   p.rsh = 2;
   while ((1u << p.rsh) < 4u * p.tw) p.rsh++;
   compute_layout(p);
-  std::vector<u32> state(state_words(p), 0);
+  // state_fill: the word the state rows and the emulated LDS hold before Simulator::new runs (0 = fresh pages; these classes never use the
+  // calendar queue, the one region the device's host code clears before a run)
+  std::vector<u32> state(state_words(p), state_fill);
   if (threads == 0) threads = 1;
   auto worker = [&](u32 tid) {
     for (size_t i = tid; i < m; i += threads) {
       const ParamSetDev& d = dev[set_of[i]];
       { SimTSets<K_GENERIC_SETS> s0(p, state.data(), (u32)i); s0.load_set(d); s0.init(seeds[i]); }
-      if (cls == K_SMALL) { SimTSets<K_SMALL_SETS> s(p, state.data(), (u32)i); s.load_set(d); run_one(s, p); }
-      else { SimTSets<K_MID_SETS> s(p, state.data(), (u32)i); s.load_set(d); run_one(s, p); }
+      if (cls == K_SMALL) { SimTSets<K_SMALL_SETS> s(p, state.data(), (u32)i); s.load_set(d); run_one(s, p, state_fill); }
+      else { SimTSets<K_MID_SETS> s(p, state.data(), (u32)i); s.load_set(d); run_one(s, p, state_fill); }
     }
   };
   std::vector<std::thread> ts;

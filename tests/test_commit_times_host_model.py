@@ -21,17 +21,22 @@ THREADS = min(os.cpu_count() or 8, 16)
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("ct_host") / "libct_hostmodel.so")
+    return load_harness(tmp_path_factory.mktemp("ct_host"))
+
+
+def load_harness(directory):
+    """Compiles the host model into `directory` and binds it."""
+    out = str(directory / "libct_hostmodel.so")
     subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-pthread", "-w",
                            os.path.join(ROOT, "tests", "commit_times_host_model.cpp"), "-o", out])
     L = C.CDLL(out)
     vp = C.c_void_p
-    L.ct_hostmodel_run.argtypes = [vp, vp, C.c_uint32, vp, vp, C.c_size_t, C.c_int64, C.c_uint32, vp, vp, vp, vp, C.c_size_t, vp]
+    L.ct_hostmodel_run.argtypes = [vp, vp, C.c_uint32, vp, vp, C.c_size_t, C.c_int64, C.c_uint32, vp, vp, vp, vp, C.c_size_t, vp, C.c_uint32]
     L.ct_hostmodel_run.restype = C.c_int
     return L
 
 
-def run_host(L, base, sets, set_of, seeds, max_clock, cap):
+def run_host(L, base, sets, set_of, seeds, max_clock, cap, state_fill=0):
     from librabft_simulator_amd import _lib
     m, n = len(seeds), base.num_nodes
     arr = (_lib.LbftParamSet * max(len(sets), 1))(*sets)
@@ -43,7 +48,7 @@ def run_host(L, base, sets, set_of, seeds, max_clock, cap):
     st = np.zeros((m, n), dtype=np.int64)
     faults = np.zeros(m, dtype=np.uint32)
     cls = L.ct_hostmodel_run(C.byref(base), arr, len(sets), set_of.ctypes.data, seeds.ctypes.data, m, max_clock, THREADS, cc.ctypes.data,
-                             ct.ctypes.data, hist.ctypes.data, st.ctypes.data, cap, faults.ctypes.data)
+                             ct.ctypes.data, hist.ctypes.data, st.ctypes.data, cap, faults.ctypes.data, state_fill)
     assert cls >= 0, cls
     return cls, {"commit_counts": cc, "commit_times": ct, "histories": hist, "startup_times": st, "faults": faults}
 

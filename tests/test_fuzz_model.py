@@ -38,6 +38,20 @@ def draw_config(rng):
     return kw
 
 
+def draw_caps(rng, kw):
+    """Capacities, queue discipline and kernel-class switches of the host model for a configuration of draw_config (large enough that
+    the configuration never faults)."""
+    n = kw["num_nodes"]
+    special = any(k in kw for k in ("equivocate_every", "drop_per_million", "partition_size")) or (kw.get("quirks", 0) & 1)
+    big = n > 4
+    qheap = 1 if (big or rng.random() < 0.3) else 0
+    qcal = 1 if (rng.random() < 0.5 and (qheap or special or n > 16)) else 0
+    # <= 64 snapshot slots: the register-resident free mask (what the device picks for small honest networks)
+    scap = 64 if (n <= 4 and not special and rng.random() < 0.5) else max(128, 128 * n)
+    return dict(qcap=max(4096, 24 * n * n), scap=scap, bcap=1024, lcap=1024, ql=int(rng.choice([0, 3, 11, 48])), qheap=qheap, qcal=qcal,
+                force_generic=int(rng.random() < 0.2))
+
+
 @pytest.mark.parametrize("chunk", range(18))
 def test_random_configurations_match_the_oracle(oracle, chunk):
     rng = np.random.default_rng(20240 + chunk)
@@ -49,15 +63,7 @@ def test_random_configurations_match_the_oracle(oracle, chunk):
         seeds = rng.integers(1, 2 ** 62, m, dtype=np.uint64)
         cfg = oracle.make_config(math_mode=1, **kw)
         a = oracle.run_batch(cfg, seeds, max_clock, threads=4, history_cap=96)
-        special = any(k in kw for k in ("equivocate_every", "drop_per_million", "partition_size")) or (kw.get("quirks", 0) & 1)
-        big = n > 4
-        qheap = 1 if (big or rng.random() < 0.3) else 0
-        qcal = 1 if (rng.random() < 0.5 and (qheap or special or n > 16)) else 0
-        # <= 64 snapshot slots: the register-resident free mask (what the device picks for small honest networks)
-        scap = 64 if (n <= 4 and not special and rng.random() < 0.5) else max(128, 128 * n)
-        b = oracle.hostmodel_run_batch(cfg, seeds, max_clock, threads=4, history_cap=96, qcap=max(4096, 24 * n * n), scap=scap,
-                                       bcap=1024, lcap=1024, ql=int(rng.choice([0, 3, 11, 48])), qheap=qheap, qcal=qcal,
-                                       force_generic=int(rng.random() < 0.2), hash_cap=1024 if n <= 16 else 0)
+        b = oracle.hostmodel_run_batch(cfg, seeds, max_clock, threads=4, history_cap=96, hash_cap=1024 if n <= 16 else 0, **draw_caps(rng, kw))
         assert not b["faults"].any(), kw
         for key in ("commit_counts", "active_rounds", "last_states", "histories"):
             assert (a[key] == b[key]).all(), (key, kw)
@@ -90,6 +96,13 @@ def draw_large_config(rng):
     return kw, n, max_clock
 
 
+def draw_large_caps(rng, kw):
+    """The host model's capacities for a configuration of draw_large_config: the calendar queue with a ring of pre-generated draws."""
+    n = kw["num_nodes"]
+    return dict(qcap=max(8192, 32 * n * n), scap=min(65535, 6 * n * n + 16 * n) if kw.get("quirks", 0) & 1 else 128 * n, bcap=512, lcap=512,
+                ql=0, qheap=1, qcal=1, ring=int(rng.choice([128, 256, 512])), ring_topup=int(rng.choice([0, 4, 16])))
+
+
 @pytest.mark.parametrize("chunk", range(8))
 def test_random_large_configurations_on_the_cooperative_loop(oracle, chunk):
     """The same generator for networks of 33..128 nodes, run through the cooperative event loop of the large-network kernels
@@ -101,9 +114,7 @@ def test_random_large_configurations_on_the_cooperative_loop(oracle, chunk):
         seeds = rng.integers(1, 2 ** 62, 1, dtype=np.uint64)
         cfg = oracle.make_config(math_mode=1, **kw)
         a = oracle.run_batch(cfg, seeds, max_clock, threads=4, history_cap=64)
-        b = oracle.hostmodel_run_batch(cfg, seeds, max_clock, threads=4, history_cap=64, qcap=max(8192, 32 * n * n),
-                                       scap=min(65535, 6 * n * n + 16 * n) if kw.get("quirks", 0) & 1 else 128 * n, bcap=512, lcap=512, ql=0, qheap=1, qcal=1,
-                                       ring=int(rng.choice([128, 256, 512])), ring_topup=int(rng.choice([0, 4, 16])))
+        b = oracle.hostmodel_run_batch(cfg, seeds, max_clock, threads=4, history_cap=64, **draw_large_caps(rng, kw))
         assert not b["faults"].any(), (kw, b["faults"])
         for key in ("commit_counts", "active_rounds", "last_states", "histories"):
             assert (a[key] == b[key]).all(), (key, kw)

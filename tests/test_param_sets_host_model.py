@@ -15,17 +15,22 @@ SIZES = (3, 4, 7, 16, 20, 32)
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("ps_host") / "libps_hostmodel.so")
+    return load_harness(tmp_path_factory.mktemp("ps_host"))
+
+
+def load_harness(directory):
+    """Compiles the host model into `directory` and binds it."""
+    out = str(directory / "libps_hostmodel.so")
     subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-pthread", "-w",
                            os.path.join(ROOT, "tests", "param_sets_host_model.cpp"), "-o", out])
     L = C.CDLL(out)
     vp = C.c_void_p
-    L.ps_hostmodel_run.argtypes = [vp, vp, C.c_uint32, vp, vp, C.c_size_t, C.c_int64, C.c_uint32, vp, vp, vp, vp, C.c_size_t, vp]
+    L.ps_hostmodel_run.argtypes = [vp, vp, C.c_uint32, vp, vp, C.c_size_t, C.c_int64, C.c_uint32, vp, vp, vp, vp, C.c_size_t, vp, C.c_uint32]
     L.ps_hostmodel_run.restype = C.c_int
     return L
 
 
-def run_host(L, base, sets, set_of, seeds, max_clock, history_cap):
+def run_host(L, base, sets, set_of, seeds, max_clock, history_cap, state_fill=0):
     from librabft_simulator_amd import _lib
     m, n = len(seeds), base.num_nodes
     arr = (_lib.LbftParamSet * len(sets))(*sets)
@@ -37,7 +42,7 @@ def run_host(L, base, sets, set_of, seeds, max_clock, history_cap):
     hist = np.zeros((m, n, history_cap), dtype=_lib.COMMIT_DTYPE)
     faults = np.zeros(m, dtype=np.uint32)
     cls = L.ps_hostmodel_run(C.byref(base), arr, len(sets), set_of.ctypes.data, seeds.ctypes.data, m, max_clock, 8, cc.ctypes.data,
-                             ar.ctypes.data, ls.ctypes.data, hist.ctypes.data, history_cap, faults.ctypes.data)
+                             ar.ctypes.data, ls.ctypes.data, hist.ctypes.data, history_cap, faults.ctypes.data, state_fill)
     assert cls >= 0, cls
     return cls, {"commit_counts": cc, "active_rounds": ar, "last_states": ls, "histories": hist, "faults": faults}
 
