@@ -11,7 +11,7 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc", "lbft_hip.hip")
-DEPS = [SRC] + [os.path.join(HERE, "csrc", f) for f in ("lbft_core.h", "lbft_math.h", "lbft_tables.h", "lbft_save_node.h", "lbft_launch.h",
+DEPS = [SRC] + [os.path.join(HERE, "csrc", f) for f in ("lbft_core.h", "lbft_math.h", "lbft_tables.h", "lbft_save_node.h", "lbft_launch.h", "lbft_plan.h",
                                                          "lbft_paramsets.h", "lbft_commit_times.h", "lbft_commit_timeline.h", "lbft_node_ops.h")] + [
     os.path.join(HERE, "..", "include", "lbft.h")]
 OUT = os.path.join(HERE, "liblbft_hip.so")

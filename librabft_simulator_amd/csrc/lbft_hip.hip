@@ -34,6 +34,7 @@ static_assert(LBFT_MAX_NODES == LBFT_MAX_NODES_SUPPORTED, "header mismatch");
 // Kernels
 // ------------------------------------------------------------------------------------------------
 #include "lbft_launch.h"
+#include "lbft_plan.h"
 
 // Simulator::new for every instance (simulator.rs:200-250).
 __global__ __launch_bounds__(LBFT_BLOCK) void lbft_k_init(Params p, u32* __restrict__ state, const u64* __restrict__ seeds) {
@@ -283,11 +284,6 @@ void lbft_k_run2q(Params p, u32* __restrict__ state, u32* __restrict__ unfinishe
 // ... and class 1 without them (networks of <= 32 nodes with equivocators, a heap / calendar queue, ...): 22 spilled registers
 __global__ __launch_bounds__(LBFT_RUN_BLOCK) __attribute__((amdgpu_waves_per_eu(LBFT_RUN_WAVES_PER_SIMD, LBFT_RUN_WAVES_PER_SIMD)))
 void lbft_k_run1l(Params p, u32* __restrict__ state, u32* __restrict__ unfinished) { LBFT_DEV_ONLY(K_MID_LEAN) run_body<K_MID_LEAN>(p, state, unfinished); }
-#ifndef LBFT_BIG_WAVES_PER_SIMD
-#define LBFT_BIG_WAVES_PER_SIMD 1  // classes 1-2: wavefronts per SIMD the kernels are compiled for (1 = the whole register file;
-                                   // measured with 2 -- half the lanes per wavefront, 167 spilled registers: 16384 x 64 nodes
-                                   // 1.23 s instead of 1.01 s, 8192 x 100 nodes 7.0 s instead of 5.5 s)
-#endif
 template <int CLS>
 __global__ __launch_bounds__(64 * LBFT_RUN_WAVES_FULL)
 #if LBFT_BIG_WAVES_PER_SIMD > 1
@@ -438,46 +434,17 @@ __global__ void lbft_k_exp_log(const u64* __restrict__ exp_tab, const double* __
 // Host side of the C ABI
 // ------------------------------------------------------------------------------------------------
 static thread_local std::string g_err;
-// Kernel selection.  Large networks without record exchange / round trace / message loss run the two-wavefronts-per-SIMD kernel
-// (`lbft_k_run2l`, 8 lanes per wavefront at 16 384 networks) WITHOUT the register-staged node sets and the calendar fetch-ahead: two
-// wavefronts overlap each other's dependent round trips, and at 256 registers every staged word is a spilled one (16 384 x 64 nodes:
-// 451 ms; with the staging 476-511 ms; the full-register kernel with twice the lanes 503 ms; 8 192 x 100 nodes: 2.49 / 2.75-2.85 / 2.85 s).
-// Tuning knobs: LBFT_NO_LEAN=1 = always the full-register kernels; LBFT_LEAN2=0 = the full-register kernel for large networks.
-// class-0 batches with few networks per wavefront run lbft_k_run0s (wavefront-wide pop); LBFT_NO_POPC=1: lbft_k_run0 for every batch size
-// (one reading of LBFT_NO_UNI for both kernel choices it touches -- round-5 advisor: "LBFT_NO_UNI=0" used to count as set in one of them)
-static bool uni_allowed() { const char* e = getenv("LBFT_NO_UNI"); return !(e && atoi(e)); }
-static bool quad_eligible(const Params& p) {
-  const char* e = getenv("LBFT_NO_QUAD");
-  // (its LDS queue columns are 32 lanes apart at compile time, LBFT_QUAD_STRIDE32: 64 networks per wavefront -- batches beyond 131 072
-  // networks, or a forced lanes_per_wavefront -- run the generic class-0 kernel)
-  // (... except the smallest batches: with one network per wavefront and fewer than 1 024 of them lbft_k_run0u wins -- 256 x 4: 4.77 ms against 7.24 here and
-  // 5.92 on lbft_k_run0s; at 1 024 the two tie (4.89 / 4.91), at 2 048 this kernel leads again: profiles/r05/lds_resident_instance_ab.txt)
-  // (LBFT_NO_UNI=1 sends those tiny batches to lbft_k_run0s -- the kernel lbft_k_run0u replaced there --, not back here)
-  const bool tiny = p.lpw == 1 && p.m < 1024;
-  return LBFT_C0_QUAD && sim_quad(p) && !tiny && !(LBFT_QUAD_STRIDE32 && p.lpw > 32) && !(e && atoi(e));
+// The tuning variables of the environment, read when a run is prepared (DESIGN.md section 4 "Knobs"; what they mean: lbft_plan.h PlanKnobs)
+static PlanKnobs knobs_from_env() {
+  auto set = [](const char* name) { const char* e = getenv(name); return e && atoi(e); };
+  PlanKnobs k;
+  k.no_quad = set("LBFT_NO_QUAD"); k.no_popc = set("LBFT_NO_POPC"); k.no_uni = set("LBFT_NO_UNI"); k.no_lean = set("LBFT_NO_LEAN");
+  if (const char* e = getenv("LBFT_LEAN2")) k.lean2 = atoi(e) != 0;
+  if (const char* e = getenv("LBFT_RING")) { k.ring_set = true; k.ring = (u32)atoi(e); }
+  if (const char* e = getenv("LBFT_RING_TOPUP")) { k.ring_topup_set = true; k.ring_topup = (u32)atoi(e); }
+  if (const char* e = getenv("LBFT_BLK_WINDOW")) k.blk_window = (u32)atoi(e);
+  return k;
 }
-// (round 5: since round 4's work on lbft_k_run0q the lane-private kernel beats the wavefront-wide pop at EVERY batch size of the headline network --
-// 2 048 / 4 096 / 8 192 / 16 384 x 4: 4.78 / 6.48 / 8.23 / 10.36 ms against 4.90 / 7.41 / 9.42 / 12.19 -- so lbft_k_run0s / lbft_k_run0u now serve the
-// class-0 batches that kernel does not take: other sizes, weighted rights, uniform delays -- 4 096 / 8 192 / 16 384 x 4 uniform: 7.23 / 9.40 / 11.94 ms against
-// 8.37 / 10.82 / 13.85 on lbft_k_run0; 1 024 x 4 uniform on lbft_k_run0u: 4.71 against 5.11)
-static bool small_batch_kernel(const Params& p) {
-  const char* e = getenv("LBFT_NO_POPC");
-  return LBFT_C0_POPC && sim_class(p) == K_SMALL && p.lpw <= LBFT_POPC_MAX_LPW && !quad_eligible(p) && !(e && atoi(e));
-}
-// ... and large batches of the headline network (4 nodes, unit rights, log-normal delays) lbft_k_run0q; LBFT_NO_QUAD=1: lbft_k_run0
-// LBFT_BLK_WINDOW=n: entries (a power of two, default 32; 0 = off) of the large-network kernels' LDS window of block records
-static u32 blk_window_max() {
-  const char* e = getenv("LBFT_BLK_WINDOW");
-  u32 v = e ? (u32)atoi(e) : 32u;
-  while (v & (v - 1)) v &= v - 1;  // round down to a power of two
-  return v > 256u ? 256u : v;
-}
-static bool blk_window_allowed() { return blk_window_max() != 0; }
-static bool quad_kernel(const Params& p) { return quad_eligible(p); }
-// ... and among them the batches with ONE network per wavefront lbft_k_run0u (wavefront-uniform code on the scalar unit); LBFT_NO_UNI=1: lbft_k_run0s
-static bool uni_kernel(const Params& p) { return small_batch_kernel(p) && p.lpw == 1 && uni_allowed(); }
-static bool lean_allowed() { const char* e = getenv("LBFT_NO_LEAN"); return !(e && atoi(e)); }
-static bool lean2_allowed() { const char* e = getenv("LBFT_LEAN2"); return lean_allowed() && !(e && !atoi(e)); }
 
 static int hip_fail(hipError_t e, const char* what) {
   g_err = std::string(what) + ": " + hipGetErrorString(e);
@@ -492,9 +459,7 @@ static int hip_fail(hipError_t e, const char* what) {
 static const u64 H_ZX[257] = LBFT_ZIG_NORM_X_BITS_INIT;
 static const u64 H_ZF[257] = LBFT_ZIG_NORM_F_BITS_INIT;
 static const u64 H_ET[256] = LBFT_EXP_TAB_INIT;
-
-#define LBFT_DUR_TABLE_LEN 4096
-#define LBFT_LEADER_TABLE_LEN 8192
+static_assert(sizeof(H_ZX) + sizeof(H_ZF) + sizeof(H_ET) == LBFT_SAMPLER_TABLE_BYTES, "lbft_plan.h table_bytes");
 
 struct lbft_batch {
   lbft_config cfg;
@@ -540,11 +505,10 @@ struct lbft_batch {
   bool keep_stores = false;  // lbft_batch_keep_retired_stores: the record store a node retires at an epoch change is archived in full
   unsigned long long* d_prof = nullptr;
   unsigned long long* h_counters = nullptr;  // pinned: the counter read-back of a run is one asynchronous copy behind the finalize kernel (round 6)
-  size_t lds_bytes = 0;
-  u32 run_waves = LBFT_RUN_WAVES;  // wavefronts per workgroup of the run kernel this batch uses (prepare_run)
+  PlanKnobs knobs;    // the environment's tuning variables as the last prepare_run read them
+  LaunchPlan launch;  // run kernel, wavefronts per workgroup, LDS bytes (prepare_run)
   float init_ms = 0, run_ms = 0;
   lbft_counters counters;
-  size_t table_bytes = 0;
   // parameter-set batches (lbft_batch_create_param_sets; empty psets = a plain batch): the sets, each instance's set, their device form
   // (ParamSetDev: fill_params' derived values + the set's duration table) for the kernels of liblbft_paramsets.so
   std::vector<lbft_param_set> psets;
@@ -558,71 +522,17 @@ struct lbft_batch {
   i32* d_ctimes = nullptr;
   size_t ctimes_bytes = 0;
 };
-// Does the batch run on a lane-private twin kernel of a side library (lbft_k_ps_run0 / 1, lbft_k_ct_*)?  Their geometry is lbft_k_run0's
-// (class 0) or lbft_k_run<1>'s (class 1) -- never a lean, small-batch or headline kernel's.
-static bool twin_kernel(const lbft_batch* b) { return !b->psets.empty() || b->ctimes; }
+// The kernel a plain batch of this shape takes: a twin batch reports ITS node burst (lbft_batch_layout) and lean family (checkpoint
+// header), as it always has.  The knobs are the ones the last prepare_run read, the run's own: both callers come after one
+// (lbft_batch_layout needs a batch that ran, the checkpoint header one that was started or has just been prepared for the load)
+static RunKernel plain_kernel(const lbft_batch* b) { return pick_run_kernel(b->p, false, false, b->knobs); }
 
 static int prepare_run(lbft_batch* b, int64_t max_clock);
 static int finalize_run(lbft_batch* b, u32 grid_full, u64 launches);
 static int launch_run(lbft_batch* b);
 static int zero_calendar(lbft_batch* b);
 static int launch_init(lbft_batch* b, u32 grid_init);
-static int launch_run_twin(lbft_batch* b);
 static int fill_commit_times(lbft_batch* b);
-
-static int fill_params(const lbft_config* cfg, size_t m, Params& p, std::vector<u32>& weights) {
-  memset(&p, 0, sizeof(p));
-  p.n = cfg->num_nodes;
-  p.m = (u32)m;
-  p.stride = (u32)((m + 63) / 64 * 64);
-  p.tw = 64; p.rsh = 8;
-  p.delay_model = cfg->delay_model;
-  // RandomDelay::new (simulator.rs:99-106), computed once on the host with the host libm like the reference
-  p.mu = std::log(cfg->mean / std::sqrt(1.0 + cfg->variance / (cfg->mean * cfg->mean)));
-  p.sigma = std::sqrt(std::log(1.0 + cfg->variance / (cfg->mean * cfg->mean)));
-  p.uni_lo = cfg->uniform_lo;
-  p.uni_span = (u64)(cfg->uniform_hi - cfg->uniform_lo) + 1;
-  p.cpe = cfg->commands_per_epoch;
-  p.tci = cfg->target_commit_interval;
-  p.lambda = cfg->lambda;
-  p.equiv = cfg->equivocate_every;
-  p.quirks = cfg->quirks;
-  p.drop_ppm = cfg->drop_per_million;
-  p.part_size = cfg->partition_size;
-  p.part_start = (i32)(cfg->partition_start < 0 ? 0 : (cfg->partition_start > 0x7fffffff ? 0x7fffffff : cfg->partition_start));
-  p.part_end = (i32)(cfg->partition_end < 0 ? 0 : (cfg->partition_end > 0x7fffffff ? 0x7fffffff : cfg->partition_end));
-  p.rot = cfg->rights_rotation % (cfg->num_nodes ? cfg->num_nodes : 1);
-  p.total_votes = 0;
-  weights.assign(p.n, 1);
-  p.unit_weights = 1;
-  for (u32 i = 0; i < p.n; i++) {
-    u64 w = cfg->voting_rights ? cfg->voting_rights[i] : 1;
-    if (w > 0x00ffffffu) return LBFT_ERR_INVALID;
-    weights[i] = (u32)w;
-    p.total_votes += (u32)w;
-    if (w != 1) p.unit_weights = 0;
-  }
-  if (p.total_votes == 0) return LBFT_ERR_INVALID;
-  if (p.unit_weights) p.rot = 0;  // rotating equal rights changes nothing
-  p.mw = (p.n + 31) / 32;
-  p.quorum = 2 * p.total_votes / 3 + 1;  // quorum_threshold (configuration.rs:52-56)
-  return LBFT_OK;
-}
-
-static int validate(const lbft_config* cfg) {
-  if (!cfg) return LBFT_ERR_INVALID;
-  if (cfg->num_nodes == 0) return LBFT_ERR_INVALID;
-  if (cfg->num_nodes > LBFT_MAX_NODES_SUPPORTED) return LBFT_ERR_UNSUPPORTED;
-  if ((cfg->quirks & ~3u) != 0) return LBFT_ERR_UNSUPPORTED;
-  if (cfg->delay_model > 1) return LBFT_ERR_INVALID;
-  if (cfg->delay_model == 0 && !(cfg->mean > 0.0 && cfg->variance >= 0.0)) return LBFT_ERR_INVALID;
-  if (cfg->delay_model == 1 && !(cfg->uniform_lo >= 0 && cfg->uniform_hi >= cfg->uniform_lo)) return LBFT_ERR_INVALID;
-  if (cfg->commands_per_epoch == 0) return LBFT_ERR_INVALID;
-  // NodeConfig (node.rs:76-81): durations and periods are f64 products truncated to i64; NaN / negative parameters have no meaning
-  if (!(cfg->gamma >= 0.0) || !(cfg->lambda >= 0.0) || cfg->delta < 0 || cfg->target_commit_interval < 0) return LBFT_ERR_INVALID;
-  if (!std::isfinite(cfg->gamma) || !std::isfinite(cfg->lambda) || !std::isfinite(cfg->mean) || !std::isfinite(cfg->variance)) return LBFT_ERR_INVALID;
-  return LBFT_OK;
-}
 
 static void free_batch(lbft_batch* b) {
   if (!b) return;
@@ -645,15 +555,14 @@ static int upload_tables(lbft_batch* b) {
   HIP_TRY(hipMemcpy(b->d_zx, H_ZX, sizeof(H_ZX), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(b->d_zf, H_ZF, sizeof(H_ZF), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(b->d_et, H_ET, sizeof(H_ET), hipMemcpyHostToDevice));
-  // PacemakerState::duration (pacemaker.rs:111-124): delta * n^gamma with the host libm's pow, as the reference
   std::vector<i64> dur(LBFT_DUR_TABLE_LEN);
-  for (size_t k = 0; k < dur.size(); k++) dur[k] = f64_to_i64_sat((double)b->cfg.delta * std::pow((double)k, b->cfg.gamma));
+  fill_duration_table(b->cfg.delta, b->cfg.gamma, dur.data(), dur.size());
   HIP_TRY(hipMalloc(&b->d_dur, dur.size() * sizeof(i64)));
   HIP_TRY(hipMemcpy(b->d_dur, dur.data(), dur.size() * sizeof(i64), hipMemcpyHostToDevice));
   HIP_TRY(hipMalloc(&b->d_weights, b->weights.size() * sizeof(u32)));
   HIP_TRY(hipMemcpy(b->d_weights, b->weights.data(), b->weights.size() * sizeof(u32), hipMemcpyHostToDevice));
   b->p.weights = b->d_weights;
-  u32 leader_tables = b->p.rot ? b->p.n : 1;  // one per shift of the rotating voting rights
+  const u32 leader_tables = lbft::leader_tables(b->p);  // one per shift of the rotating voting rights
   HIP_TRY(hipMalloc(&b->d_leaders, (size_t)leader_tables * LBFT_LEADER_TABLE_LEN));
   b->p.dur_tab = b->d_dur; b->p.dur_len = LBFT_DUR_TABLE_LEN;
   b->p.leader_tab = b->d_leaders; b->p.leader_len = 0;  // table not valid while it is being filled
@@ -662,7 +571,6 @@ static int upload_tables(lbft_batch* b) {
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(b->stream));
   b->p.leader_len = LBFT_LEADER_TABLE_LEN;
-  b->table_bytes = sizeof(H_ZX) + sizeof(H_ZF) + sizeof(H_ET) + dur.size() * sizeof(i64) + (size_t)leader_tables * LBFT_LEADER_TABLE_LEN;
   return LBFT_OK;
 }
 
@@ -743,14 +651,6 @@ static int load_paramsets_lib() {
   if (!g_ps_init || !g_ps_run) { g_ps_init = nullptr; g_ps_run = nullptr; g_err = path + " lacks lbft_ps_launch_init / lbft_ps_launch_run"; return LBFT_ERR_UNSUPPORTED; }
   return LBFT_OK;
 }
-// `base` with one set's fields: the configuration an instance of that set runs (what lbft_batch_create would be given for it)
-static lbft_config config_of_set(const lbft_config& base, const lbft_param_set& s) {
-  lbft_config c = base;
-  c.mean = s.mean; c.variance = s.variance; c.uniform_lo = s.uniform_lo; c.uniform_hi = s.uniform_hi;
-  c.target_commit_interval = s.target_commit_interval; c.delta = s.delta; c.gamma = s.gamma; c.lambda = s.lambda;
-  c.drop_per_million = s.drop_per_million; c.partition_size = s.partition_size; c.partition_start = s.partition_start; c.partition_end = s.partition_end;
-  return c;
-}
 static int launch_init(lbft_batch* b, u32 grid_init) {
   if (b->psets.empty()) {
     lbft_k_init<<<grid_init, LBFT_BLOCK, 0, b->stream>>>(b->p, b->d_state, b->d_seeds);
@@ -783,22 +683,6 @@ static int load_commit_times_lib() {
   }
   return LBFT_OK;
 }
-// The run kernels of the side libraries: a parameter-set batch's (lbft_k_ps_run0 / 1) or, recording commit times, a plain or
-// parameter-set batch's commit-time twin (lbft_k_ct_run0 / 1, lbft_k_ct_ps_run0 / 1).
-static int launch_run_twin(lbft_batch* b) {
-  const Params& p = b->p;
-  const int cls = sim_class(p);  // K_SMALL or K_MID: networks of more than 32 nodes are refused by both
-  const u32 nwaves = b->run_waves, block = 64u * nwaves;
-  u32 grid_run = (u32)((b->m + (size_t)nwaves * p.lpw - 1) / ((size_t)nwaves * p.lpw));
-  HIP_TRY(hipMemsetAsync(b->d_unfinished, 0, sizeof(u32), b->stream));
-  b->generation++;
-  if (b->ctimes)
-    HIP_TRY(g_ct_run(cls, &p, b->d_state, b->d_unfinished, b->psets.empty() ? nullptr : b->d_psets, b->psets.empty() ? nullptr : b->d_set_of,
-                     b->d_ctimes, grid_run, block, b->lds_bytes, b->stream));
-  else
-    HIP_TRY(g_ps_run(cls, &p, b->d_state, b->d_unfinished, b->d_psets, b->d_set_of, grid_run, block, b->lds_bytes, b->stream));
-  return LBFT_OK;
-}
 // A run starts with every entry unrecorded (-1)
 static int fill_commit_times(lbft_batch* b) {
   if (!b->ctimes) return LBFT_OK;
@@ -823,24 +707,18 @@ int lbft_batch_create_param_sets(const lbft_config* base, const lbft_param_set* 
   *out = nullptr;
   // everything is checked before the first HIP call
   if (!base || !sets || !set_of_instance || n_sets == 0 || n_sets > LBFT_MAX_PARAM_SETS) { g_err = "parameter sets: NULL argument or n_sets outside 1..256"; return LBFT_ERR_INVALID; }
-  lbft_config c = config_of_set(*base, sets[0]);
-  u32 drop_any = 0, part_any = 0;
   for (u32 k = 0; k < n_sets; k++) {
     const lbft_config ck = config_of_set(*base, sets[k]);
     int rc = validate(&ck);
     if (rc != LBFT_OK) { g_err = "parameter set " + std::to_string(k) + ": invalid or unsupported configuration"; return rc; }
-    drop_any |= sets[k].drop_per_million;
-    part_any = sets[k].partition_size > part_any ? sets[k].partition_size : part_any;
   }
+  const lbft_config c = config_of_sets(*base, sets, n_sets);  // (the batch-wide Params see the loss of ANY set)
   if (c.num_nodes > 32) { g_err = "parameter sets: networks of at most 32 nodes"; return LBFT_ERR_UNSUPPORTED; }
   if (!seeds || n_instances == 0 || n_instances > 0x7fffffffu / c.num_nodes) { g_err = "bad seeds / n_instances"; return LBFT_ERR_INVALID; }
   for (size_t i = 0; i < n_instances; i++)
     if (set_of_instance[i] >= n_sets) { g_err = "set_of_instance[" + std::to_string(i) + "] >= n_sets"; return LBFT_ERR_INVALID; }
   int rc = load_paramsets_lib();
   if (rc != LBFT_OK) return rc;
-  // the batch-wide Params see the loss of ANY set: the class (and queue discipline) are chosen for the most demanding set
-  c.drop_per_million = drop_any;
-  c.partition_size = part_any;
   rc = lbft_batch_create(&c, seeds, n_instances, device, out);
   if (rc != LBFT_OK) return rc;
   lbft_batch* b = *out;
@@ -853,18 +731,8 @@ int lbft_batch_create_param_sets(const lbft_config* base, const lbft_param_set* 
   do {
     hipError_t e;
     if ((e = hipMalloc(&b->d_ps_dur, dur.size() * sizeof(i64))) != hipSuccess) { frc = hip_fail(e, "hipMalloc(duration tables)"); break; }
-    for (u32 k = 0; k < n_sets; k++) {
-      const lbft_config ck = config_of_set(*base, sets[k]);
-      Params pk;
-      std::vector<u32> wk;
-      fill_params(&ck, n_instances, pk, wk);  // (mu, sigma, uni_*, clamped partition window: exactly as a plain batch of this set)
-      ParamSetDev& d = dev[k];
-      d.mu = pk.mu; d.sigma = pk.sigma; d.uni_lo = pk.uni_lo; d.uni_span = pk.uni_span; d.tci = pk.tci; d.lambda = pk.lambda;
-      d.drop_ppm = pk.drop_ppm; d.part_size = pk.part_size; d.part_start = pk.part_start; d.part_end = pk.part_end;
-      d.dur_tab = b->d_ps_dur + (size_t)k * LBFT_DUR_TABLE_LEN;
-      // PacemakerState::duration (pacemaker.rs:111-124) with the host libm's pow, as upload_tables
-      for (size_t j = 0; j < LBFT_DUR_TABLE_LEN; j++) dur[(size_t)k * LBFT_DUR_TABLE_LEN + j] = f64_to_i64_sat((double)ck.delta * std::pow((double)j, ck.gamma));
-    }
+    for (u32 k = 0; k < n_sets; k++)
+      dev[k] = param_set_dev(config_of_set(*base, sets[k]), n_instances, &dur[(size_t)k * LBFT_DUR_TABLE_LEN], b->d_ps_dur + (size_t)k * LBFT_DUR_TABLE_LEN);
     if ((e = hipMemcpy(b->d_ps_dur, dur.data(), dur.size() * sizeof(i64), hipMemcpyHostToDevice)) != hipSuccess) { frc = hip_fail(e, "hipMemcpy(duration tables)"); break; }
     if ((e = hipMalloc(&b->d_psets, dev.size() * sizeof(ParamSetDev))) != hipSuccess) { frc = hip_fail(e, "hipMalloc(sets)"); break; }
     if ((e = hipMemcpy(b->d_psets, dev.data(), dev.size() * sizeof(ParamSetDev), hipMemcpyHostToDevice)) != hipSuccess) { frc = hip_fail(e, "hipMemcpy(sets)"); break; }
@@ -1181,25 +1049,7 @@ int lbft_batch_phase_cycles(const lbft_batch* b, uint64_t* out) {
 int lbft_batch_layout(const lbft_batch* b, uint32_t* out) {
   if (!b || !out) return LBFT_ERR_INVALID;
   if (!b->ran) { g_err = "run the batch first"; return LBFT_ERR_STATE; }
-  const Params& p = b->p;
-  // what one event moves (the roofline's S_node / S_notif, bench.py, tools/configs.py), not the padded row sizes: a node burst is the
-  // fixed words + the extension words of the four author sets (begin_node / end_node); the hcbr buffers (2n words behind them) are
-  // only touched where a timeout is inserted or copied -- for networks of <= 4 nodes they live in LDS for the whole launch.  A
-  // notification snapshot: its fixed words + set extension words; for <= 4 nodes also its 2n hcbr words (always fetched with it), for
-  // larger networks the hcbr words an event happens to carry are NOT counted (the figure is a lower bound there).
-  // (lbft_k_run0q, LBFT_C0_HCREG: the node's 2n hcbr words ride in its burst -- hc_load / hc_store -- and are counted)
-  out[0] = (NF_FIXED_WORDS + 4 * (p.mw - 1) + ((quad_kernel(p) && LBFT_C0_HCREG) ? 2 * p.n : 0)) * 4;
-  out[1] = (p.qpack ? 8 : p.qcal ? 4 : 12);  // (the calendar keeps no key: an entry is the 4-byte meta word, plus 1/31 of a chunk's link word)
-  out[2] = (S_FIXED_WORDS + 2 * (p.mw - 1) + (p.n <= 4 ? 2 * p.n : 0)) * 4;
-  out[3] = (B_WORDS + 4 * (p.mw - 1)) * 4;   // bytes of one block record
-  out[4] = p.total_words * 4; // HBM bytes per instance
-  out[5] = p.ql;              // event-queue slots per instance resident in LDS
-  out[6] = p.lpw;             // lanes per wavefront carrying an instance
-  out[7] = (uint32_t)sim_class(p) | (p.qheap << 8) | (p.qcal << 9) | ((((sim_lean(p) && lean2_allowed()) || (sim_lean1(p) && lean_allowed())) ? 1u : 0u) << 10) | ((p.ring ? 1u : 0u) << 11) |
-           (((sim_lean_q1(p) && lean2_allowed()) ? 1u : 0u) << 12) | ((small_batch_kernel(p) ? 1u : 0u) << 13) |
-           ((quad_kernel(p) ? 1u : 0u) << 14) | ((uni_kernel(p) ? 1u : 0u) << 15);
-  if (twin_kernel(b))
-    out[7] = (uint32_t)sim_class(p) | (p.qheap << 8) | (p.qcal << 9) | ((b->psets.empty() ? 0u : 1u) << 16) | ((b->ctimes ? 1u : 0u) << 17);
+  layout_words(b->p, b->launch.kernel, plain_kernel(b) == RK_RUN0Q, out);
   return LBFT_OK;
 }
 
@@ -1224,161 +1074,32 @@ static int zero_calendar(lbft_batch* b) {
   return LBFT_OK;
 }
 
-// Capacities, HBM layout, launch geometry (shared by lbft_batch_run_until and lbft_batch_manual_begin).
+// Capacities, HBM layout, launch geometry (shared by lbft_batch_run_until and lbft_batch_manual_begin): the plan is lbft_plan.h's,
+// the memory it asks for is allocated here.
 static int prepare_run(lbft_batch* b, int64_t max_clock) {
   if (max_clock < 0 || max_clock > LBFT_MAX_CLOCK) { g_err = "max_clock out of range"; return LBFT_ERR_INVALID; }
   HIP_TRY(hipSetDevice(b->device));
   Params& p = b->p;
-  const lbft_config& c = b->cfg;
-  u32 n = c.num_nodes;
-  // Capacities (0 = auto).  The queue only ever holds events with time <= max_clock.
-  // (large networks: ~n^2 messages in flight per round; the heap keeps push/pop logarithmic)
-  u32 qauto = n <= 16 ? 16 * n * n : 8 * n * n;
-  u32 qcap = c.queue_capacity ? c.queue_capacity : (qauto < 128 ? 128 : qauto);
-  // (quirks bit 0: every request and response in flight holds a slot as well)
-  // (measured high-water marks with quirks bit 0: ~n^2 -- 400 at n = 20, 1250 at n = 36 -- and flat over the horizon)
-  u32 sauto = (c.quirks & 1u) ? (n * n + 8 * n > 64 * n ? n * n + 8 * n : 64 * n) : 8 * n;
-  u32 scap = c.snapshot_capacity ? c.snapshot_capacity : (sauto < 32 ? 32 : (sauto > 65535 ? 65535 : sauto));
-  // one block per round; a 1- or 2-node network can finish a round per time unit
-  u64 bauto = n <= 2 ? (u64)max_clock + 64 : (u64)max_clock / 10 + 64;
-  u32 bcap = c.block_capacity ? c.block_capacity : (u32)(bauto > 65534 ? 65534 : bauto);
-  if (bcap > 65534 || scap > 65535 || n > 255) { g_err = "capacity out of range"; return LBFT_ERR_INVALID; }
-  u32 lcap = c.log_capacity ? c.log_capacity : bcap;
-  if (lcap > bcap) lcap = bcap;  // a node commits each block at most once
-  // Queue discipline: 4-node honest lossless networks scan an LDS-resident array (kernel class 0); everything else keeps
-  // hundreds to tens of thousands of pending events and uses a calendar of (time, kind) FIFOs when max_clock allows it
-  // (O(1) push and pop), otherwise a binary heap whose top levels are the LDS-resident slots.
-  bool big = qcap > 256 || n > 32;
-  u32 qheap = big ? 1u : 0u;
-  bool class0 = n <= 16 && !qheap && !p.equiv && !b->rcap && !p.drop_ppm && !p.part_size && !(p.quirks & 1u);
-  // epochs a node can go through are bounded by its commits: the archive of retired record stores (quirks bit 0) is exact
-  u64 eauto = (u64)bcap / (c.commands_per_epoch ? c.commands_per_epoch : 1) + 2;
-  u32 ecap = ((p.quirks & 1u) || b->keep_stores) ? (u32)(eauto > 4096 ? 4096 : eauto) : 0;
-  const u32 rarch = b->keep_stores ? 1u : 0u;  // (compute_layout turns the flag into the entry size)
-  // (the calendar replaces the HEAP: a small network outside class 0 -- e.g. 4 nodes with an equivocator -- keeps the LDS-fronted
-  // array; 65536 x 4 nodes with one equivocator each: 28.6 ms on the array, 43.6 ms on the HBM calendar)
-  u32 qcal = (!class0 && big && !b->rcap && b->allow_calendar && max_clock <= LBFT_CAL_MAX_CLOCK) ? 1u : 0u;
-  bool relayout = !(p.qcap == qcap && p.scap == scap && p.bcap == bcap && p.lcap == lcap && p.rcap == b->rcap && p.qcal == qcal && p.ecap == ecap &&
-                    (p.rarch_words != 0) == (rarch != 0) && p.max_clock == (i32)max_clock && b->d_state);
-  p.qcap = qcap; p.scap = scap; p.bcap = bcap; p.lcap = lcap; p.rcap = b->rcap; p.qcal = qcal; p.qheap = qheap; p.ecap = ecap; p.rarch_words = rarch;
-  p.max_clock = (i32)max_clock;
-  p.max_steps = b->max_steps;
-  // Cooperative large-network kernels (class 2 on the calendar queue): ring of pre-generated RNG draws per instance and how far
-  // every network's generator runs ahead per step (tuning knobs: LBFT_RING = entries, a power of two, 0 = lane-per-network
-  // execution as for the small classes; LBFT_RING_TOPUP = draws per step)
-  {
-    u32 ring = 0, topup = 0;
-    if (n > 32 && qcal) {
-      // (round 6, third session: with the runs a large network makes ~15 k loop iterations instead of 215 k, and a bulk send of a 100-node network consumes ~220 draws:
-      // a top-up of 4 per iteration left the bulk's leader lane generating them one at a time -- profiles/r06/ring_topup_after_all_runs.txt)
-      ring = 512; topup = n > 64 ? 128 : 16;
-      if (const char* e = getenv("LBFT_RING")) ring = (u32)atoi(e);
-      if (const char* e = getenv("LBFT_RING_TOPUP")) topup = (u32)atoi(e);
-      if (ring & (ring - 1)) ring = 512;
-      if (ring && ring < 128) ring = 128;
-    }
-    if (p.ring != ring) relayout = true;
-    p.ring = ring; p.ring_topup = ring ? topup : 0;
-  }
-  u64 words = compute_layout(p);
-  if (p.qcal) {  // the calendar's bucket rows grow with the horizon: keep it only while the batch fits comfortably in HBM
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    size_t avail = free_b + (b->d_state ? b->state_bytes : 0);
-    if (!layout_fits(words) || (double)words * p.stride * 4.0 > 0.85 * (double)avail) {
-      qcal = 0; p.qcal = 0;
-      relayout = true;
-      words = compute_layout(p);
-    }
-  }
-  if (!layout_fits(words)) {
-    p.qcap = 0;  // (forces a relayout next time)
-    g_err = "per-instance state exceeds 2^24 rows (64 MiB per instance): lower the capacities / the horizon";
-    return LBFT_ERR_INVALID;
-  }
+  b->knobs = knobs_from_env();
+  bool relayout = false;
+  int rc = plan_capacities(b->cfg, p, max_clock, b->rcap, b->keep_stores, b->allow_calendar, b->max_steps, b->knobs, b->d_state != nullptr, relayout, g_err);
+  if (rc != LBFT_OK) return rc;
+  size_t free_b = 0, total_b = 0;
+  if (p.qcal) HIP_TRY(hipMemGetInfo(&free_b, &total_b));  // (what the calendar may take)
+  rc = plan_rows(p, free_b + (b->d_state ? b->state_bytes : 0), relayout, g_err);
+  if (rc != LBFT_OK) return rc;
   if (relayout) {
     if (b->d_state) { HIP_TRY(hipFree(b->d_state)); b->d_state = nullptr; }
     b->state_bytes = state_words(p) * sizeof(u32);
     HIP_TRY(hipMalloc(&b->d_state, b->state_bytes));
   }
-  if (b->ctimes && b->ctimes_bytes != b->m * n * (size_t)lcap * sizeof(i32)) {  // [instance][node][lcap] i32
+  if (b->ctimes && b->ctimes_bytes != commit_times_bytes(p)) {
     if (b->d_ctimes) { HIP_TRY(hipFree(b->d_ctimes)); b->d_ctimes = nullptr; b->ctimes_bytes = 0; }
-    HIP_TRY(hipMalloc(&b->d_ctimes, b->m * n * (size_t)lcap * sizeof(i32)));
-    b->ctimes_bytes = b->m * n * (size_t)lcap * sizeof(i32);
+    HIP_TRY(hipMalloc(&b->d_ctimes, commit_times_bytes(p)));
+    b->ctimes_bytes = commit_times_bytes(p);
   }
-  // Lanes per wavefront that carry an instance.  The LDS queue front makes residency LDS-bound: one CU holds
-  // 160 KiB / (bytes per instance) instances however they are spread over wavefronts, so prefer full wavefronts
-  // unless the batch is too small to give every SIMD a wavefront.
-  u32 lpw = b->lpw;
-  if (lpw == 0) {
-    // Wavefronts that can be resident at once: 256 CUs x 4 SIMDs, two per SIMD for kernel class 0 (256 registers), one for
-    // the large-network classes.  The fewest lanes per wavefront that still fit the batch in one residency win: a
-    // wavefront-step costs the union of its lanes' paths (65536 x 4 nodes, r01_s3 build: 27.0 ms at 64 lanes = one wavefront
-    // per SIMD, 24.4 ms at 32 = two per SIMD, 40.1 ms at 16 = two rounds; 1024 x 4 nodes: 22.9 ms at 8 lanes, 17.6 at 4,
-    // 13.2 at 2, 9.4 ms at ONE network per wavefront; 8192 x 100 nodes: 9.0 s at 16 lanes, 5.9 s at 8, 7.8 s at 4 = two rounds).
-    const bool lean2k = sim_lean(p) && lean2_allowed();
-    // (parameter-set and commit-time batches: lbft_k_ps_run0 / lbft_k_ct_*run0 have lbft_k_run0's geometry, lbft_k_ps_run1 /
-    // lbft_k_ct_*run1 lbft_k_run<1>'s -- never a lean kernel's)
-    u64 resident = (lean2k || sim_class(p) == K_SMALL || (!twin_kernel(b) && sim_lean1(p) && lean_allowed())) ? 2048 : 1024 * LBFT_BIG_WAVES_PER_SIMD;
-    u64 want = (b->m + resident - 1) / resident;
-    lpw = 1;
-    while (lpw < want && lpw < 32) lpw <<= 1;
-  }
-  p.lpw = lpw;
-  // Tile width of the HBM layout (lbft_core.h "HBM layout"): 64 for the small-network classes 0 and 1, 1 (instance-major) for large networks
-  {
-    // Measured (16 384 x 64 nodes / 8 192 x 100 nodes / c4live): tw = 64: 652 ms / 3.63 s / --; tw = lanes per wavefront: 596 / 3.20 / 4.94 s;
-    // tw = 4: 555 / 3.17 / 4.43; tw = 2: 550 / 3.10 / 4.28; tw = 1: 541 ms / 3.05 s / 4.14 s -- the large-network kernels address tw = 1 at compile time.
-    u32 tw = layout_tile_width(p);
-    // (instance-major rows: a lane addresses its instance through a 32-bit offset from the wavefront's first instance)
-    if (tw == 1 && (u64)lpw * p.total_words * 4ULL >= (1ULL << 32)) {
-      g_err = "lanes per wavefront x per-instance state exceeds 4 GiB: lower the capacities or the lanes per wavefront";
-      return LBFT_ERR_INVALID;
-    }
-    p.tw = tw;
-    p.rsh = 2;
-    while ((4u << (p.rsh - 2)) < 4u * tw) p.rsh++;
-  }
-  // wavefronts per workgroup of the kernel this batch runs on: 8 = both wavefront slots of a CU's four SIMDs for the kernels compiled
-  // for two wavefronts per SIMD, 4 for the full-register ones
-  const bool two_wave_kernel = sim_class(p) == K_SMALL || (sim_lean(p) && lean2_allowed()) || (!twin_kernel(b) && sim_lean1(p) && lean_allowed());
-  const u32 nwaves = two_wave_kernel ? LBFT_RUN_WAVES : LBFT_RUN_WAVES_FULL;
-  b->run_waves = nwaves;
-  // LDS queue slots per instance: what one CU's LDS affords when it hosts 64/lpw workgroups
-  u32 wg_per_cu = (64 / lpw) * 4 / nwaves;  // workgroups that make up a CU's 256 instances
-  if (wg_per_cu < 1) wg_per_cu = 1;
-  if (wg_per_cu > 4) wg_per_cu = 4;
-  // (the kernels compiled for two wavefronts per SIMD run as 8-wavefront workgroups: one of them fills a CU's wavefront slots at 256
-  // registers per lane, so the whole LDS is that one workgroup's whatever its lanes per wavefront -- round 4: with the budget of two the
-  // 16-lane form of lbft_k_run0q kept 24 queue slots in LDS and spilled the rest to HBM)
-  if (two_wave_kernel && nwaves >= 8) wg_per_cu = 1;
-  size_t budget = (160u * 1024u) / wg_per_cu;
-  // 2 KiB slack per workgroup: with less, two workgroups of 32-lane wavefronts do not become co-resident on a CU
-  u32 slot_bytes = p.qpack ? 8u : 12u;  // kernel class 0 keeps one-word entries
-  p.lpw = lpw;
-  const bool quadk = !twin_kernel(b) && quad_kernel(p);  // (the kernel choice only depends on the layout and lpw)
-  const bool hcbr_lds = !(LBFT_C0_IMAJOR && LBFT_C0_HCREG && quadk);
-  const u32 qcols = (quadk && LBFT_QUAD_STRIDE32) ? 32u : lpw;  // queue columns per wavefront in LDS (SimT::QS32)
-  u32 ql_auto = (u32)((budget - run_lds_bytes(0, qcols, n, slot_bytes, nwaves, hcbr_lds) - 2048) / (slot_bytes * nwaves * qcols));  // (run_lds_bytes(0, ..) includes the lane padding)
-  const u32 ql_max = quadk ? LBFT_PACKED_QL_QUAD : LBFT_PACKED_QL_MAX, pop_batch = quadk ? LBFT_POP_BATCH_QUAD : LBFT_POP_BATCH;
-  if (p.qpack && ql_auto > ql_max) ql_auto = ql_max;
-  u32 ql = b->ql < 0 ? ql_auto : (u32)b->ql;
-  if (ql > qcap) ql = qcap;
-  if (p.qpack) ql -= ql % pop_batch;  // scanned in batches (SimT::PB)
-  if (p.qcal) ql = 0;  // the calendar lives in HBM rows
-  if (run_lds_bytes(ql, qcols, n, slot_bytes, nwaves, hcbr_lds) > 160u * 1024u) { g_err = "LDS queue slots do not fit the CU's 160 KiB"; return LBFT_ERR_INVALID; }
-  p.ql = ql;
-  b->lds_bytes = run_lds_bytes(ql, qcols, n, slot_bytes, nwaves, hcbr_lds);
-  // large networks: the LDS that the calendar queue leaves unused holds a window of block records per network (SimT::attach_blk_window)
-  p.blw = 0;
-  // (measured, round 4: c4live 2.77 -> 2.76 s, c5live 4.72 -> 4.60 s with 32 entries, 4.58 s with 64; the kernel without the record exchange
-  // LOSES with it -- c4 346 -> 357 ms, c5 1.90 -> 1.98 s, its three register records already serve it -- and does not get one)
-  if (sim_lean_q1(p) && lean2_allowed() && blk_window_allowed()) {
-    u32 e = blk_window_max();
-    while (e && b->lds_bytes + blk_window_bytes(e, lpw, nwaves) > 150u * 1024u) e >>= 1;
-    p.blw = e;
-    b->lds_bytes += blk_window_bytes(e, lpw, nwaves);
-  }
+  rc = plan_launch(p, b->lpw, b->ql, !b->psets.empty(), b->ctimes, b->knobs, b->launch, g_err);
+  if (rc != LBFT_OK) return rc;
   p.prof = b->d_prof;
   return LBFT_OK;
 }
@@ -1416,33 +1137,43 @@ int lbft_batch_run_until(lbft_batch* b, int64_t max_clock) {
   return finalize_run(b, grid_full, launches);
 }
 
+// One launch of the batch's run kernel (LaunchPlan::kernel): the kernels of this library, or a side library's lane-private twins --
+// a parameter-set batch's (lbft_k_ps_run0 / 1) or, recording commit times, a plain or parameter-set batch's (lbft_k_ct_run0 / 1,
+// lbft_k_ct_ps_run0 / 1).
 static int launch_run(lbft_batch* b) {
-  if (twin_kernel(b)) return launch_run_twin(b);
   Params& p = b->p;
-  int cls = sim_class(p);
-  bool lean = sim_lean(p) && lean2_allowed(), lean1 = sim_lean1(p) && lean_allowed();
-  const bool leanq = lean && sim_lean_q1(p);
-  const bool small0 = small_batch_kernel(p);
-  const bool quad0 = quad_kernel(p);
-  const bool uni0 = cls == K_SMALL && uni_kernel(p);
-  const void* run_fn = leanq ? reinterpret_cast<const void*>(lbft_k_run2q) : lean ? reinterpret_cast<const void*>(lbft_k_run2l) : lean1 ? reinterpret_cast<const void*>(lbft_k_run1l) :
-                       uni0 ? reinterpret_cast<const void*>(lbft_k_run0u) :
-                       (cls == K_SMALL && small0) ? reinterpret_cast<const void*>(lbft_k_run0s) : (cls == K_SMALL && quad0) ? reinterpret_cast<const void*>(lbft_k_run0q) : cls == K_SMALL ? reinterpret_cast<const void*>(lbft_k_run0)
-                     : cls == K_MID ? reinterpret_cast<const void*>(lbft_k_run<K_MID>) : reinterpret_cast<const void*>(lbft_k_run<K_LARGE>);
-  HIP_TRY(hipFuncSetAttribute(run_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_bytes));
-  const u32 nwaves = b->run_waves, block = 64u * nwaves;
+  const size_t lds = b->launch.lds_bytes;
+  const u32 nwaves = b->launch.run_waves, block = 64u * nwaves;
   u32 grid_run = (u32)((b->m + (size_t)nwaves * p.lpw - 1) / ((size_t)nwaves * p.lpw));
   HIP_TRY(hipMemsetAsync(b->d_unfinished, 0, sizeof(u32), b->stream));
   b->generation++;
-  if (leanq) lbft_k_run2q<<<grid_run, block, b->lds_bytes, b->stream>>>(p, b->d_state, b->d_unfinished);
-  else if (lean) lbft_k_run2l<<<grid_run, block, b->lds_bytes, b->stream>>>(p, b->d_state, b->d_unfinished);
-  else if (lean1) lbft_k_run1l<<<grid_run, block, b->lds_bytes, b->stream>>>(p, b->d_state, b->d_unfinished);
-  else if (uni0) lbft_k_run0u<<<grid_run, block, b->lds_bytes, b->stream>>>(p, b->d_state, b->d_unfinished);
-  else if (cls == K_SMALL && small0) lbft_k_run0s<<<grid_run, block, b->lds_bytes, b->stream>>>(p, b->d_state, b->d_unfinished);
-  else if (cls == K_SMALL && quad0) lbft_k_run0q<<<grid_run, block, b->lds_bytes, b->stream>>>(p, b->d_state, b->d_unfinished);
-  else if (cls == K_SMALL) lbft_k_run0<<<grid_run, block, b->lds_bytes, b->stream>>>(p, b->d_state, b->d_unfinished);
-  else if (cls == K_MID) lbft_k_run<K_MID><<<grid_run, block, b->lds_bytes, b->stream>>>(p, b->d_state, b->d_unfinished);
-  else lbft_k_run<K_LARGE><<<grid_run, block, b->lds_bytes, b->stream>>>(p, b->d_state, b->d_unfinished);
+#define LBFT_LAUNCH(kernel)                                                                                                    \
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+  kernel<<<grid_run, block, lds, b->stream>>>(p, b->d_state, b->d_unfinished);                                               \
+  break
+  const int cls = sim_class(p);  // (the twins: K_SMALL or K_MID)
+  switch (b->launch.kernel) {
+    case RK_RUN0: LBFT_LAUNCH(lbft_k_run0);
+    case RK_RUN0Q: LBFT_LAUNCH(lbft_k_run0q);
+    case RK_RUN0S: LBFT_LAUNCH(lbft_k_run0s);
+    case RK_RUN0U: LBFT_LAUNCH(lbft_k_run0u);
+    case RK_RUN1L: LBFT_LAUNCH(lbft_k_run1l);
+    case RK_RUN1: LBFT_LAUNCH(lbft_k_run<K_MID>);
+    case RK_RUN2L: LBFT_LAUNCH(lbft_k_run2l);
+    case RK_RUN2Q: LBFT_LAUNCH(lbft_k_run2q);
+    case RK_RUN2: LBFT_LAUNCH(lbft_k_run<K_LARGE>);
+    case RK_PS_RUN0: case RK_PS_RUN1:
+      HIP_TRY(g_ps_run(cls, &p, b->d_state, b->d_unfinished, b->d_psets, b->d_set_of, grid_run, block, lds, b->stream));
+      break;
+    case RK_CT_RUN0: case RK_CT_RUN1:
+      HIP_TRY(g_ct_run(cls, &p, b->d_state, b->d_unfinished, nullptr, nullptr, b->d_ctimes, grid_run, block, lds, b->stream));
+      break;
+    case RK_CT_PS_RUN0: case RK_CT_PS_RUN1:
+      HIP_TRY(g_ct_run(cls, &p, b->d_state, b->d_unfinished, b->d_psets, b->d_set_of, b->d_ctimes, grid_run, block, lds, b->stream));
+      break;
+    default: g_err = "no launch for this run kernel"; return LBFT_ERR_UNSUPPORTED;
+  }
+#undef LBFT_LAUNCH
   HIP_TRY(hipGetLastError());
   return LBFT_OK;
 }
@@ -1509,7 +1240,7 @@ static void fill_header(const lbft_batch* b, CheckpointHeader& h) {
   h.equiv = p.equiv; h.m = b->m; h.cpe = c.commands_per_epoch; h.max_clock = b->started_max_clock; h.tci = c.target_commit_interval;
   h.delta = c.delta; h.uni_lo = c.uniform_lo; h.uni_hi = c.uniform_hi; h.mean = c.mean; h.variance = c.variance; h.gamma = c.gamma;
   h.lambda = c.lambda; h.delay_model = c.delay_model; h.weights_hash = weights_hash(b->weights) ^ (p.rot * 0x9e3779b9u);
-  h.quirks = p.quirks; h.drop_ppm = p.drop_ppm; h.part_size = p.part_size; h.rot = p.rot; h.sim_class = (u32)sim_class(p) | (((sim_lean(p) && lean2_allowed()) || (sim_lean1(p) && lean_allowed())) ? 256u : 0u);
+  h.quirks = p.quirks; h.drop_ppm = p.drop_ppm; h.part_size = p.part_size; h.rot = p.rot; h.sim_class = (u32)sim_class(p) | ((run_kernel_info(plain_kernel(b)).flags & (1u << 10)) ? 256u : 0u);
   h.qpack = p.qpack; h.qcal = p.qcal; h.qheap = p.qheap; h.ecap = p.ecap; h.tw = p.tw | (p.ring << 8); h.part_start = c.partition_start; h.part_end = c.partition_end;
   if (!b->psets.empty()) {  // (a parameter-set batch: the sets and the instances' assignment, folded into the same header words)
     u32 sh = 2166136261u;
@@ -2014,8 +1745,7 @@ int lbft_batch_last_run_ms(const lbft_batch* b, float* init_ms, float* run_ms) {
 }
 size_t lbft_batch_device_bytes(const lbft_batch* b) {
   if (!b) return 0;
-  return b->state_bytes + b->table_bytes + b->m * sizeof(u64) + b->m * b->p.n * (sizeof(u64) * 2) +
-         b->psets.size() * (sizeof(ParamSetDev) + LBFT_DUR_TABLE_LEN * sizeof(i64)) + (b->psets.empty() ? 0 : b->m) + b->ctimes_bytes;
+  return device_bytes(b->p, b->state_bytes, b->psets.size(), b->ctimes_bytes);
 }
 
 // ---- stand-alone device checks ----

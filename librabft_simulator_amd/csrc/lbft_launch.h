@@ -36,23 +36,19 @@
 #define LBFT_LDS_WEIGHTS LBFT_MAX_NODES  // voting rights (u32)
 #define LBFT_TABLE_U64 (257 + 257 + 256 + LBFT_LDS_DURS + LBFT_LDS_LEADERS / 8 + LBFT_LDS_WEIGHTS / 2)
 
-// [tables][queue keys][queue metas][diagnostics: LBFT_NPHASES u64 per wavefront][n > 16: one 128-byte receiver list per instance]
-// `slot_bytes`: 12 (key + meta) or 8 (packed one-word entries, kernel class 0)
-// `hcbr_lds`: class 0 with networks of <= 4 nodes keeps the nodes' hcbr buffers in LDS -- except lbft_k_run0q, which carries them in
-// registers with the node burst (LBFT_C0_HCREG)
-// the LDS window of block records of the large-network kernels (SimT::attach_blk_window): `entries` records + tags per network
-static inline size_t blk_window_bytes(u32 entries, u32 lpw, u32 nwaves) { return (size_t)nwaves * lpw * entries * (1u + BC_WORDS) * 4u; }
-static inline size_t run_lds_bytes(u32 ql, u32 lpw, u32 n, u32 slot_bytes, u32 nwaves, bool hcbr_lds = true) {
-  return (size_t)LBFT_TABLE_U64 * 8 + (size_t)nwaves * ql * lpw * slot_bytes + (size_t)nwaves * LBFT_NPHASES * 8 + 8 +
-         (n > 16 ? (size_t)nwaves * lpw * LBFT_MAX_NODES : 0) +
-         (n <= 4 && slot_bytes == 8 && hcbr_lds ? (size_t)nwaves * lpw * LBFT_LDS_HCBR_WORDS * 4 : 0);  // class 0, n <= 4: hcbr buffers
-}
-
+// (the host's sizing of this layout: run_lds_bytes, lbft_plan.h)
+#if defined(__HIPCC__)
 __device__ __forceinline__ size_t run_lds_bytes_dev(u32 ql, u32 lpw, u32 slot_bytes, u32 nwaves) {  // = run_lds_bytes(ql, lpw, 0, ..): where the receiver lists start
   return (size_t)LBFT_TABLE_U64 * 8 + (size_t)nwaves * ql * lpw * slot_bytes + (size_t)nwaves * LBFT_NPHASES * 8 + 8;
 }
+#endif
 #ifndef LBFT_RUN_WAVES_PER_SIMD
 #define LBFT_RUN_WAVES_PER_SIMD 2  // register budget of the class-0 run kernel: 512 / 2 = 256 VGPRs + AGPRs per lane (the
                                    // large-network classes run one 8- or 16-lane wavefront per SIMD and may use all 512)
+#endif
+#ifndef LBFT_BIG_WAVES_PER_SIMD
+#define LBFT_BIG_WAVES_PER_SIMD 1  // classes 1-2: wavefronts per SIMD the kernels are compiled for (1 = the whole register file;
+                                   // measured with 2 -- half the lanes per wavefront, 167 spilled registers: 16384 x 64 nodes
+                                   // 1.23 s instead of 1.01 s, 8192 x 100 nodes 7.0 s instead of 5.5 s)
 #endif
 #endif  // LBFT_LAUNCH_H

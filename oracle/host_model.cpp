@@ -10,19 +10,13 @@
 #include <type_traits>
 #include <vector>
 
-#include "../include/lbft.h"
-#include "../librabft_simulator_amd/csrc/lbft_core.h"
+#include "host_model_common.h"
 #include "../librabft_simulator_amd/csrc/lbft_save_node.h"
-#include "../librabft_simulator_amd/csrc/lbft_tables.h"
 #include "lbft_oracle.h"
 
 using namespace lbft;
 
 #include "../librabft_simulator_amd/csrc/lbft_node_ops.h"
-
-static const u64 ZX[257] = LBFT_ZIG_NORM_X_BITS_INIT;
-static const u64 ZF[257] = LBFT_ZIG_NORM_F_BITS_INIT;
-static const u64 ET[256] = LBFT_EXP_TAB_INIT;
 
 // save_node images of instance 0's nodes after the next lbft_hostmodel_run_batch (test hook, not thread-safe): node k's image is written
 // at image_buf + k * image_stride, its length (or (size_t)-1: unsupported) into image_lens[k]
@@ -80,25 +74,35 @@ struct HostParams {
   std::vector<i64> dur;
   std::vector<u8> leaders;
 };
+// The oracle's configuration as the product library's (the same fields under the same names), capacities on auto
+static lbft_config product_config(const lbft_oracle_config* cfg) {
+  lbft_config c;
+  memset(&c, 0, sizeof(c));
+  c.num_nodes = cfg->num_nodes; c.delay_model = cfg->delay_model; c.mean = cfg->mean; c.variance = cfg->variance;
+  c.uniform_lo = cfg->uniform_lo; c.uniform_hi = cfg->uniform_hi; c.commands_per_epoch = cfg->commands_per_epoch;
+  c.target_commit_interval = cfg->target_commit_interval; c.delta = cfg->delta; c.gamma = cfg->gamma; c.lambda = cfg->lambda;
+  c.quirks = cfg->quirks; c.equivocate_every = cfg->equivocate_every; c.voting_rights = cfg->voting_rights;
+  c.drop_per_million = cfg->drop_per_million; c.partition_size = cfg->partition_size; c.partition_start = cfg->partition_start;
+  c.partition_end = cfg->partition_end; c.rights_rotation = cfg->rights_rotation;
+  return c;
+}
 static int setup_params(const lbft_oracle_config* cfg, const lbft_hostmodel_caps* caps, size_t n_instances, int64_t max_clock, bool manual,
                         HostParams& hp) {
   if ((cfg->quirks & ~3u) != 0 || cfg->num_nodes > LBFT_MAX_NODES) return -10;
   if (max_clock < 0 || max_clock > LBFT_MAX_CLOCK) return -14;  // (lbft_batch_run_until: LBFT_ERR_INVALID)
   Params& p = hp.p;
-  memset(&p, 0, sizeof(p));
-  p.n = cfg->num_nodes;
-  p.m = (u32)n_instances;
-  p.stride = (u32)((n_instances + 63) / 64 * 64);
-  p.tw = caps->tw ? caps->tw : 64;
-  if (p.tw > 64 || (p.tw & (p.tw - 1))) return -13;
-  p.rsh = 2;
-  while ((1u << p.rsh) < 4u * p.tw) p.rsh++;
+  const lbft_config c = product_config(cfg);
+  if (fill_params(&c, n_instances, p, hp.weights) != LBFT_OK) return -10;
+  p.weights = hp.weights.data();
+  // the geometry is the caller's: what these tests vary
+  if (caps->tw > 64 || (caps->tw & (caps->tw - 1))) return -13;
+  set_tile_width(p, caps->tw ? caps->tw : 64);
   p.qcap = caps->qcap; p.scap = caps->scap; p.bcap = caps->bcap; p.lcap = caps->lcap;
   p.max_clock = (i32)max_clock;
   p.ql = caps->ql;
   p.qheap = caps->qheap;
   p.rcap = caps->rcap;
-  {  // as the device host code: epochs a node can go through are bounded by its commits
+  {  // epochs a node can go through are bounded by its commits
     u64 eauto = (u64)caps->bcap / (cfg->commands_per_epoch ? cfg->commands_per_epoch : 1) + 2;
     p.ecap = (u32)(eauto > 4096 ? 4096 : eauto);
     if (manual) { if (!(cfg->quirks & 1u) && !caps->keep_stores) p.ecap = 0; }  // (lbft_batch_manual_begin: exactly the device's archive)
@@ -109,41 +113,7 @@ static int setup_params(const lbft_oracle_config* cfg, const lbft_hostmodel_caps
   p.ring = (caps->qcal && p.n > 32) ? caps->ring : 0; p.ring_topup = p.ring ? caps->ring_topup : 0;
   if (p.ring & (p.ring - 1)) return -12;
   if (p.qcal) { if (max_clock > LBFT_CAL_MAX_CLOCK || p.rcap) return -11; p.qheap = 1; p.ql = 0; }
-  p.delay_model = cfg->delay_model;
-  p.mu = std::log(cfg->mean / std::sqrt(1.0 + cfg->variance / (cfg->mean * cfg->mean)));
-  p.sigma = std::sqrt(std::log(1.0 + cfg->variance / (cfg->mean * cfg->mean)));
-  p.uni_lo = cfg->uniform_lo;
-  p.uni_span = (u64)(cfg->uniform_hi - cfg->uniform_lo) + 1;
-  p.cpe = cfg->commands_per_epoch;
-  p.tci = cfg->target_commit_interval;
-  p.lambda = cfg->lambda;
-  p.equiv = cfg->equivocate_every;
-  p.quirks = cfg->quirks;
-  p.drop_ppm = cfg->drop_per_million;
-  p.part_size = cfg->partition_size;
-  p.part_start = (i32)(cfg->partition_start < 0 ? 0 : (cfg->partition_start > 0x7fffffff ? 0x7fffffff : cfg->partition_start));
-  p.part_end = (i32)(cfg->partition_end < 0 ? 0 : (cfg->partition_end > 0x7fffffff ? 0x7fffffff : cfg->partition_end));
-  p.rot = cfg->rights_rotation % p.n;
-  p.total_votes = 0;
-  std::vector<u32>& weights = hp.weights;
-  weights.resize(p.n);
-  for (u32 i = 0; i < p.n; i++) { weights[i] = cfg->voting_rights ? (u32)cfg->voting_rights[i] : 1; p.total_votes += weights[i]; }
-  p.weights = weights.data();
-  p.quorum = 2 * p.total_votes / 3 + 1;
-  p.unit_weights = 1;
-  for (u32 i = 0; i < p.n; i++) if (p.weights[i] != 1) p.unit_weights = 0;
-  if (p.unit_weights) p.rot = 0;
-  std::vector<i64>& dur = hp.dur;
-  dur.resize(4096);
-  for (size_t k = 0; k < dur.size(); k++) dur[k] = f64_to_i64_sat((double)cfg->delta * std::pow((double)k, cfg->gamma));
-  const u32 leader_len = 4096, leader_tables = p.rot ? p.n : 1;  // one table per shift of the rotating voting rights
-  std::vector<u8>& leaders = hp.leaders;
-  leaders.resize((size_t)leader_len * leader_tables);
-  for (u32 k = 0; k < leader_tables; k++)
-    for (u32 r = 0; r < leader_len; r++) leaders[(size_t)k * leader_len + r] = (u8)compute_leader(p.weights, p.n, p.total_votes, r, k);
-  p.dur_tab = dur.data(); p.dur_len = (u32)dur.size();
-  p.leader_tab = leaders.data(); p.leader_len = leader_len;
-  p.exp_tab = ET; p.zig_x = ZX; p.zig_f = ZF;
+  attach_tables(p, cfg->delta, cfg->gamma, hp.dur, hp.leaders);
   compute_layout(p);
   return 0;
 }
@@ -163,53 +133,30 @@ int lbft_hostmodel_run_batch(const lbft_oracle_config* cfg, const lbft_hostmodel
   Params& p = host.p;
   std::vector<u32>& weights = host.weights;
   const u32 fill = caps_state_fill(caps);
-  const u64 fill64 = ((u64)fill << 32) | fill;
   std::vector<u32> state;
 
   if (threads == 0) threads = 1;
   if (p.n > 32) p.qheap = 1;  // as the device host code does
   // the step runs as the size class the device would pick (SimT<0..2>); init and read-back use the generic class
-  auto run_one = [&](auto& s, size_t i) {
-    // (the emulated LDS starts as the state does: on the device it holds the previous kernel's leftovers)
-    std::vector<u64> keys(p.ql ? p.ql : 1, fill64);
-    std::vector<u32> metas(p.ql ? p.ql : 1, fill);
-    s.attach_queue(keys.data(), metas.data(), 1, p.ql);
-    std::vector<u32> hcbr(32, fill);  // the device's LDS copy of the hcbr buffers (class 0, n <= 4)
-    if (p.ql) s.attach_hcbr(hcbr.data());
-    std::vector<u32> window(32 * (1 + BC_WORDS), fill);  // the large-network kernels' LDS window of block records (32 entries, as the device's default)
-    if (p.n > 32) s.attach_blk_window(window.data(), 32, 0);
-    s.load_scalars();
-    s.queue_to_lds();
-    s.hcbr_to_lds();
-    bool done;
+  auto run = [&](auto& s) {
     using S = typename std::remove_reference<decltype(s)>::type;
-    bool coop = false;
-    if constexpr (S::COOP) { coop = p.ring != 0; done = coop ? s.run_coop(true) : s.run(); }
-    else done = s.run();
+    const bool coop = run_one(s, p, fill);
     g_last_class.store((uint32_t)S::CLS | (coop ? 256u : 0u) | (p.qheap ? 512u : 0u) | (p.qcal ? 1024u : 0u));
-    s.queue_from_lds();
-    s.hcbr_from_lds();
-    s.store_scalars(done);
   };
   int cls = caps->force_generic ? 3 : sim_class(p);
-  if (cls <= 2) {  // the tile width each class addresses at compile time (64-wide tiles or instance-major rows)
-    p.tw = layout_tile_width(p);
-    p.rsh = 2;
-    while ((1u << p.rsh) < 4u * p.tw) p.rsh++;
-  }
+  if (cls <= 2) set_tile_width(p, layout_tile_width(p));
   dirty_state(p, state, fill);
   auto worker = [&](u32 tid) {
     for (size_t i = tid; i < n_instances; i += threads) {
       { Sim s0(p, state.data(), (u32)i); s0.init(seeds[i]); }
-      // emulate the device's launch structure: the LDS front of the queue is a cache of the HBM rows
-      if (cls == K_SMALL && LBFT_C0_QUAD && sim_quad(p)) { SimT<K_HEADLINE> s(p, state.data(), (u32)i); run_one(s, i); }  // as the device dispatches (large batches)
-      else if (cls == K_SMALL) { SimT<K_SMALL> s(p, state.data(), (u32)i); run_one(s, i); }
-      else if (cls == K_MID && sim_lean1(p)) { SimT<K_MID_LEAN> s(p, state.data(), (u32)i); run_one(s, i); }  // as the device dispatches
-      else if (cls == K_MID) { SimT<K_MID> s(p, state.data(), (u32)i); run_one(s, i); }
-      else if (cls == K_LARGE && sim_lean_q1(p)) { SimT<K_LARGE_EXCHANGE> s(p, state.data(), (u32)i); run_one(s, i); }  // as the device dispatches
-      else if (cls == K_LARGE && sim_lean(p)) { SimT<K_LARGE_LEAN> s(p, state.data(), (u32)i); run_one(s, i); }
-      else if (cls == K_LARGE) { SimT<K_LARGE> s(p, state.data(), (u32)i); run_one(s, i); }
-      else { Sim s(p, state.data(), (u32)i); run_one(s, i); }
+      if (cls == K_SMALL && LBFT_C0_QUAD && sim_quad(p)) { SimT<K_HEADLINE> s(p, state.data(), (u32)i); run(s); }  // as the device dispatches (large batches)
+      else if (cls == K_SMALL) { SimT<K_SMALL> s(p, state.data(), (u32)i); run(s); }
+      else if (cls == K_MID && sim_lean1(p)) { SimT<K_MID_LEAN> s(p, state.data(), (u32)i); run(s); }  // as the device dispatches
+      else if (cls == K_MID) { SimT<K_MID> s(p, state.data(), (u32)i); run(s); }
+      else if (cls == K_LARGE && sim_lean_q1(p)) { SimT<K_LARGE_EXCHANGE> s(p, state.data(), (u32)i); run(s); }  // as the device dispatches
+      else if (cls == K_LARGE && sim_lean(p)) { SimT<K_LARGE_LEAN> s(p, state.data(), (u32)i); run(s); }
+      else if (cls == K_LARGE) { SimT<K_LARGE> s(p, state.data(), (u32)i); run(s); }
+      else { Sim s(p, state.data(), (u32)i); run(s); }
     }
   };
   std::vector<std::thread> ts;
@@ -308,23 +255,14 @@ int lbft_hostmodel_run_batch(const lbft_oracle_config* cfg, const lbft_hostmodel
     u64 min_round = UINT64_MAX, min_commits = UINT64_MAX;
     for (u32 n = 0; n < p.n; n++) {
       size_t o = i * p.n + n;
-      u32 nc = s.nfm(n, NF_NCOMMITS);
+      u64 last_state = 0;
+      u32 nc = read_history(s, p, n, histories ? histories + o * history_cap : (lbft_oracle_commit*)nullptr, history_cap, &last_state);
       u64 ar = s.nfm(n, NF_PM_ROUND);
       if (commit_counts) commit_counts[o] = nc;
       if (active_rounds) active_rounds[o] = ar;
+      if (last_states) last_states[o] = last_state;
       min_round = ar < min_round ? ar : min_round;
       min_commits = nc < min_commits ? nc : min_commits;
-      Sip13 h;
-      h.init();
-      h.word(nc);
-      for (u32 k = 0; k < nc; k++) {
-        u32 b = s.ld(p.off_log + n * p.lcap + k);
-        u64 proposer = s.blk_author(b), index = s.bf(b, B_CMD);
-        i64 time = (i64)(i32)s.bf(b, B_TIME);
-        h.word(proposer); h.word(index); h.word((u64)time);
-        if (histories && k < history_cap) histories[o * history_cap + k] = lbft_oracle_commit{proposer, index, time};
-      }
-      if (last_states) last_states[o] = h.finish();
     }
     if (counters) {
       counters->events[0] += s.ev0; counters->events[1] += s.ev1; counters->events[2] += s.ev2; counters->events[3] += s.ev3;
@@ -346,7 +284,7 @@ struct HostSession {
   double gamma, lambda;
 };
 
-// Instances with the capacities `caps` (the device's for the same batch: oracle_ctypes.manual_caps), each initialised as
+// Instances with the capacities `caps` (the device's for the same batch: oracle_ctypes.plan / manual_caps), each initialised as
 // lbft_batch_manual_begin does (NodeState::make_initial_state, no events processed).
 int lbft_hostmodel_session_create(const lbft_oracle_config* cfg, const lbft_hostmodel_caps* caps, const uint64_t* seeds, size_t n_instances,
                                   int64_t max_clock, void** out) {
@@ -391,19 +329,7 @@ size_t lbft_hostmodel_session_history(void* h, uint32_t inst, uint32_t node, lbf
   const Params& p = hs->hp.p;
   Sim s(p, hs->state.data(), inst);
   s.load_scalars();
-  u32 nc = s.nfm(node, NF_NCOMMITS);
-  Sip13 sh;
-  sh.init();
-  sh.word(nc);
-  for (u32 k = 0; k < nc; k++) {
-    u32 b = s.ld(p.off_log + node * p.lcap + k);
-    u64 proposer = s.blk_author(b), index = s.bf(b, B_CMD);
-    i64 time = (i64)(i32)s.bf(b, B_TIME);
-    sh.word(proposer); sh.word(index); sh.word((u64)time);
-    if (out && k < cap) out[k] = lbft_oracle_commit{proposer, index, time};
-  }
-  if (last_state) *last_state = sh.finish();
-  return nc;
+  return read_history(s, p, node, out, cap, last_state);
 }
 
 // SimT::committed_record_hashes of (inst, node): [cap][4] words -> entries written.
@@ -430,6 +356,42 @@ int lbft_hostmodel_session_save_node(void* h, uint32_t inst, uint32_t node, uint
   if (rc != 0) return rc;
   *len = image.size();
   if (buf && image.size() <= cap) memcpy(buf, image.data(), image.size());
+  return 0;
+}
+
+// ---- The planner of the device library (csrc/lbft_plan.h: plan_layout + plan_launch with the default knobs) for one batch, so that
+// the CPU tier takes a batch's geometry from the code the device runs.  capacities: queue, snapshot, block, log (0 = auto); lanes: per
+// wavefront, 0 = auto; n_sets: parameter sets of the batch (0 = a plain batch; `cfg` is then the batch-wide configuration);
+// avail_bytes: the device memory the state may take.  The struct is mirrored by oracle_ctypes.HostModelPlan.  -> 0, or the planner's
+// error code.  (The horizon's range is the run's check, not the planner's.)
+typedef struct lbft_hostmodel_plan_out {
+  uint32_t qcap, scap, bcap, lcap, ecap, qheap, qcal, ring, ring_topup, tw, lpw, ql, blw, run_waves, kernel /* RunKernel */, lds_bytes;
+  uint32_t layout[8];  // lbft_batch_layout
+  uint64_t state_bytes, device_bytes;  // lbft_batch_device_bytes
+} lbft_hostmodel_plan_out;
+
+int lbft_hostmodel_plan(const lbft_oracle_config* cfg, const uint32_t* capacities, size_t n_instances, int64_t max_clock, uint32_t lanes,
+                        uint32_t n_sets, int commit_times, int keep_stores, int calendar_queue, uint64_t avail_bytes, lbft_hostmodel_plan_out* out) {
+  lbft_config c = product_config(cfg);
+  c.queue_capacity = capacities[0]; c.snapshot_capacity = capacities[1]; c.block_capacity = capacities[2]; c.log_capacity = capacities[3];
+  if (int rc = validate(&c)) return rc;
+  if (lanes > 64 || (lanes && 64 % lanes != 0) || n_sets > LBFT_MAX_PARAM_SETS) return LBFT_ERR_INVALID;
+  Params p;
+  std::vector<u32> weights;
+  if (int rc = fill_params(&c, n_instances, p, weights)) return rc;
+  const PlanKnobs knobs;
+  bool relayout;
+  std::string err;
+  LaunchPlan launch;
+  if (int rc = plan_layout(c, p, max_clock, 0, keep_stores != 0, calendar_queue != 0, 0, avail_bytes, knobs, false, relayout, err)) return rc;
+  if (int rc = plan_launch(p, lanes, -1, n_sets != 0, commit_times != 0, knobs, launch, err)) return rc;
+  memset(out, 0, sizeof(*out));
+  out->qcap = p.qcap; out->scap = p.scap; out->bcap = p.bcap; out->lcap = p.lcap; out->ecap = p.ecap; out->qheap = p.qheap; out->qcal = p.qcal;
+  out->ring = p.ring; out->ring_topup = p.ring_topup; out->tw = p.tw; out->lpw = p.lpw; out->ql = p.ql; out->blw = p.blw;
+  out->run_waves = launch.run_waves; out->kernel = (uint32_t)launch.kernel; out->lds_bytes = (uint32_t)launch.lds_bytes;
+  layout_words(p, launch.kernel, pick_run_kernel(p, false, false, knobs) == RK_RUN0Q, out->layout);
+  out->state_bytes = state_words(p) * sizeof(u32);
+  out->device_bytes = device_bytes(p, out->state_bytes, n_sets, commit_times ? commit_times_bytes(p) : 0);
   return 0;
 }
 

@@ -448,17 +448,40 @@ def hostmodel_run_batch(cfg, seeds, max_clock, threads=1, history_cap=0, qcap=25
             "round_switches": rs, "max_rounds": mr, "record_hashes": rh}
 
 
+class HostModelPlan(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("qcap", "scap", "bcap", "lcap", "ecap", "qheap", "qcal", "ring", "ring_topup", "tw", "lpw", "ql", "blw",
+                                           "run_waves", "kernel", "lds_bytes")] + \
+               [("layout", C.c_uint32 * 8), ("state_bytes", C.c_uint64), ("device_bytes", C.c_uint64)]
+
+
+def plan(cfg, n_instances, max_clock, queue_capacity=0, snapshot_capacity=0, block_capacity=0, log_capacity=0, lanes_per_wavefront=0,
+         param_sets=0, commit_times=False, keep_stores=False, calendar_queue=True, avail_bytes=1 << 40):
+    """The geometry the device library chooses for a batch of ``cfg`` (an OracleConfig; for a parameter-set batch the batch-wide one and
+    ``param_sets`` = their number): csrc/lbft_plan.h's plan_layout + plan_launch, compiled into the host model -- capacities, queue
+    discipline, ring, tile width, lanes per wavefront, LDS slots, run kernel, the words of lbft_batch_layout, device bytes.
+    ``avail_bytes``: the device memory the state may take.  Raises ValueError with the planner's code on a refused batch."""
+    L = hostmodel_lib()
+    L.lbft_hostmodel_plan.argtypes = [C.POINTER(OracleConfig), C.POINTER(C.c_uint32), C.c_size_t, C.c_int64, C.c_uint32, C.c_uint32, C.c_int,
+                                      C.c_int, C.c_int, C.c_uint64, C.POINTER(HostModelPlan)]
+    L.lbft_hostmodel_plan.restype = C.c_int
+    caps = (C.c_uint32 * 4)(queue_capacity, snapshot_capacity, block_capacity, log_capacity)
+    out = HostModelPlan()
+    rc = L.lbft_hostmodel_plan(C.byref(cfg), caps, n_instances, max_clock, lanes_per_wavefront, param_sets, bool(commit_times), bool(keep_stores),
+                               bool(calendar_queue), avail_bytes, C.byref(out))
+    if rc != 0:
+        raise ValueError("the planner refuses the batch: %d" % rc)
+    d = {n: getattr(out, n) for n, _ in HostModelPlan._fields_}
+    d["layout"] = [int(v) for v in out.layout]
+    return d
+
+
 def manual_caps(num_nodes, quirks, max_clock, snapshot_capacity=0, keep_stores=0, block_capacity=0):
-    """The capacities lbft_batch_manual_begin gives a node-level session (lbft_hip.hip prepare_run, every capacity on auto but the
-    snapshot pool), as HostSession takes them."""
-    n = num_nodes
-    qauto = 16 * n * n if n <= 16 else 8 * n * n
-    qcap = max(qauto, 128)
-    sauto = max(n * n + 8 * n, 64 * n) if quirks & 1 else 8 * n
-    scap = snapshot_capacity or min(max(sauto, 32), 65535)
-    bcap = block_capacity or min(max_clock + 64 if n <= 2 else max_clock // 10 + 64, 65534)
+    """The capacities lbft_batch_manual_begin gives a node-level session (every capacity on auto but the snapshot pool and the blocks),
+    as HostSession takes them."""
+    c = plan(make_config(num_nodes=num_nodes, quirks=quirks), 1, max_clock, snapshot_capacity=snapshot_capacity, block_capacity=block_capacity,
+             keep_stores=keep_stores)
     # (instance-major rows, tw = 1, as the device lays out large networks: the image builder then reads them in place)
-    return dict(qcap=qcap, scap=scap, bcap=bcap, lcap=bcap, qheap=int(qcap > 256 or n > 32), tw=1, keep_stores=int(bool(keep_stores)))
+    return dict(qcap=c["qcap"], scap=c["scap"], bcap=c["bcap"], lcap=c["lcap"], qheap=c["qheap"], tw=1, keep_stores=int(bool(keep_stores)))
 
 
 class HostSession:

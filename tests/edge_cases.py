@@ -204,31 +204,26 @@ def oracle_config(oc, case, math_mode=1):
 
 
 def host_caps(case):
-    """The capacities and queue discipline lbft_batch_run_until's prepare_run (csrc/lbft_hip.hip) chooses for this case, as arguments of
-    oracle_ctypes.hostmodel_run_batch.  This is a copy of prepare_run's rules and must track them: the device tier asserts the choices
-    (kernel class, heap, calendar, cooperative flags of lbft_batch_layout) against expected_layout() on every case."""
-    n, mc, cfg = case["n"], case["max_clock"], case["cfg"]
-    quirks = cfg.get("quirks", 0)
-    qauto = 16 * n * n if n <= 16 else 8 * n * n
-    qcap = max(128, qauto)
-    sauto = max(n * n + 8 * n, 64 * n) if quirks & 1 else 8 * n
-    scap = max(32, min(65535, sauto))
-    bcap = case.get("block_capacity") or min(65534, mc + 64 if n <= 2 else mc // 10 + 64)
-    big = qcap > 256 or n > 32
-    class0 = n <= 16 and not big and not cfg.get("drop_per_million") and not cfg.get("partition_size") and not quirks & 1
-    qcal = int(not class0 and big and case.get("calendar_queue", True) and mc <= CAL_MAX_CLOCK)
-    ring = 512 if n > 32 and qcal else 0
-    return dict(qcap=qcap, scap=scap, bcap=bcap, lcap=bcap, ql=0 if qcal else 16, qheap=int(big), qcal=qcal, ring=ring,
-                ring_topup=(128 if n > 64 else 16) if ring else 0)
+    """The capacities and queue discipline the device library chooses for this case (oracle_ctypes.plan: csrc/lbft_plan.h compiled into
+    the host model), as arguments of oracle_ctypes.hostmodel_run_batch."""
+    import oracle_ctypes as oc
+    c = oc.plan(oracle_config(oc, case), len(case["seeds"]), case["max_clock"], block_capacity=case.get("block_capacity", 0),
+                calendar_queue=case.get("calendar_queue", True))
+    return dict({k: c[k] for k in ("qcap", "scap", "bcap", "lcap", "qheap", "qcal", "ring", "ring_topup")}, ql=0 if c["qcal"] else 16)
 
 
 def expected_layout(case):
-    """(kernel size class, heap flag, calendar flag, cooperative flag) that host_caps implies, as lbft_batch_layout reports them."""
-    c = host_caps(case)
-    n, cfg = case["n"], case["cfg"]
-    small = n <= 16 and not c["qheap"] and not cfg.get("drop_per_million") and not cfg.get("partition_size") and not cfg.get("quirks", 0) & 1
-    cls = 2 if n > 32 else (0 if small and case["max_clock"] < 2 ** QP_TIME_BITS and c["scap"] <= 256 else 1)
-    return cls, c["qheap"], c["qcal"], int(c["ring"] > 0)
+    """(kernel size class, heap flag, calendar flag, cooperative flag) as lbft_batch_layout must report them: stated here from the case
+    alone (every capacity of the table but block_capacity is automatic), independently of the planner the device and host_caps use."""
+    n, mc, cfg = case["n"], case["max_clock"], case["cfg"]
+    q1 = cfg.get("quirks", 0) & 1
+    qcap = max(128, 16 * n * n if n <= 16 else 8 * n * n)
+    scap = max(32, min(65535, max(n * n + 8 * n, 64 * n) if q1 else 8 * n))
+    heap = qcap > 256 or n > 32
+    small = n <= 16 and not heap and not cfg.get("drop_per_million") and not cfg.get("partition_size") and not q1
+    cls = 2 if n > 32 else (0 if small and mc < 2 ** QP_TIME_BITS and scap <= 256 else 1)
+    qcal = int(not small and heap and case.get("calendar_queue", True) and mc <= CAL_MAX_CLOCK)
+    return cls, int(heap), qcal, int(n > 32 and qcal)
 
 
 def lbft_config(case):

@@ -18,6 +18,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import commit_times_oracle as cto  # noqa: E402
 import edge_cases as ec  # noqa: E402
+import plan_batches as pb  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -27,17 +28,8 @@ def amd():
     return m
 
 
-def make_sim(case, seeds=None, **kw):
-    m = amd()
-    f = dict(mean=10.0, variance=4.0, delay_model=0, uniform_lo=5, uniform_hi=15, target_commit_interval=100000, delta=20, gamma=2.0,
-             lambda_=0.5, quirks=0, drop_per_million=0)
-    f.update(case["cfg"])
-    delay = m.RandomDelay.uniform(f["uniform_lo"], f["uniform_hi"]) if f["delay_model"] == 1 else m.RandomDelay.new(f["mean"], f["variance"])
-    nc = m.NodeConfig(f["target_commit_interval"], f["delta"], f["gamma"], f["lambda_"])
-    seeds = np.array(case["seeds"] if seeds is None else seeds, dtype=np.uint64)
-    return m.BatchSimulator.new(seeds, case["n"], delay, nc, commands_per_epoch=f.get("commands_per_epoch", 30000), quirks=f["quirks"],
-                                drop_per_million=f["drop_per_million"],
-                                calendar_queue=case.get("calendar_queue", True), block_capacity=case.get("block_capacity", 0), **kw)
+def make_sim(case, commit_times=False):
+    return pb.make_sim(amd(), pb.edge_batch(case, commit_times=commit_times))
 
 
 def oracle_runs(oracle, case, seeds):
@@ -78,7 +70,7 @@ def test_edge_case_device(oracle, case):
         assert flags & 0xff == case["kernel_class"], (case["name"], hex(flags))
     if "calendar" in case:
         assert bool(flags & ec.LAYOUT_CALENDAR) == case["calendar"], (case["name"], hex(flags))
-    # the CPU tier runs the host build with ec.host_caps, a copy of prepare_run's choices: they must be the device's
+    # the table's own statement of the class and queue discipline (the CPU tier runs the host build with the planner's)
     assert (flags & 0xff, (flags >> 8) & 1, (flags >> 9) & 1, (flags >> 11) & 1) == ec.expected_layout(case), (case["name"], hex(flags))
     if kind == "fault":
         assert (res.faults == arg).all(), (case["name"], res.faults)
@@ -89,6 +81,19 @@ def test_edge_case_device(oracle, case):
     ctr, want = res.counters, sum_counters(refs)
     assert list(ctr["events"]) == want["events"], (case["name"], ctr["events"], want["events"])
     assert ctr["rng_draws"] == want["rng_draws"] and ctr["events_scheduled"] == want["events_scheduled"], (case["name"], ctr, want)
+
+
+@pytest.mark.parametrize("entry", pb.recorded(), ids=lambda e: e["name"])
+def test_recorded_layout_on_the_device(entry):
+    """The library still reports, for every batch of tests/plan_batches.py, what it reported before the planner moved into
+    csrc/lbft_plan.h (tests/golden/plan_layouts.json)."""
+    spec = pb.BATCHES[entry["name"]]
+    sim = pb.make_sim(amd(), spec)
+    sim.loop_until(pb.max_clock_of(spec), allow_faults=True)
+    got = list(sim.layout().values())
+    assert got == entry["layout"], (entry["name"], got, hex(got[7]), hex(entry["layout"][7]))
+    assert sim.device_bytes() == entry["device_bytes"], entry["name"]
+    sim.close()
 
 
 def test_calendar_limit_on_the_device(oracle):
@@ -120,17 +125,10 @@ def test_refused_on_the_device(case):
     assert (res.faults == 0).all()
 
 
-def make_param_set_sim(case, **kw):
-    m = amd()
-    sets = []
-    for k in range(len(case["sets"])):
-        f = ec.set_fields(case, k)
-        delay = m.RandomDelay.uniform(f["uniform_lo"], f["uniform_hi"]) if case["delay_model"] == 1 else m.RandomDelay.new(f["mean"], f["variance"])
-        sets.append(m.ParamSet(delay, m.NodeConfig(f["target_commit_interval"], f["delta"], f["gamma"], f["lambda_"]),
-                               drop_per_million=f["drop_per_million"]))
+def make_param_set_sim(case, commit_times=False):
     set_of, seeds = ec.set_layout(case)
-    set_of, seeds = np.array(set_of, dtype=np.uint32), np.array(seeds, dtype=np.uint64)
-    return m.BatchSimulator.with_param_sets(seeds, case["n"], sets, set_of, **kw), set_of, seeds
+    sim = pb.make_sim(amd(), dict(sets=case["name"], commit_times=commit_times))
+    return sim, np.array(set_of, dtype=np.uint32), np.array(seeds, dtype=np.uint64)
 
 
 @pytest.mark.parametrize("case", ec.PARAM_SET_CASES, ids=lambda c: c["name"])
