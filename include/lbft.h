@@ -335,6 +335,32 @@ int lbft_batch_checkpoint_load(lbft_batch* b, const void* buf, size_t len);
  * round < min(*max_round, cap_rounds); *messages = the value of number_of_messages.txt. */
 int lbft_batch_enable_round_trace(lbft_batch* b, uint32_t max_rounds);
 int lbft_batch_round_switches(const lbft_batch* b, size_t inst, int64_t* out, size_t cap_rounds, uint64_t* max_round, uint64_t* messages);
+/* The same for every instance in one call (a few strided copies and host work, no kernel): out[(inst * cap_rounds + round) * num_nodes +
+ * node], INT64_MIN = empty cell, rows for round < min(max_round[inst], cap_rounds), every other cell of `out` INT64_MIN; max_round[m];
+ * messages[m], may be NULL.  For every instance exactly what lbft_batch_round_switches gives.  cap_rounds == 0 reads max_round and
+ * messages alone (out may then be NULL): the call that sizes `out`.  LBFT_ERR_INVALID for NULL arguments; LBFT_ERR_STATE before a
+ * finished run, or when the trace was not enabled.
+ *
+ * Round statistics: durations, skips and entry skew per group, computed on the device from the trace.  A batch with the round trace
+ * enabled has, per instance i, the table T_i[r][j] that lbft_batch_round_switches returns: rows r in [0, R_i), R_i = max_j max_round[j]
+ * (the row of the highest round reached is not part of the table, data_writer.rs:74-75; the device also stores the cell at r = R_i, which
+ * is ignored here); a cell is the GlobalTime at which node j was first seen in round r, or empty.  Groups are those of the latency
+ * histogram (the parameter sets, or one group for a plain batch); instances with a non-zero fault word are skipped
+ * (LBFT_FAULT_TRACE_OVERFLOW included).  For node j let r_1 < ... < r_q be its non-empty rows.  Four sample families, each reported as
+ * stats[g * LBFT_ROUND_STATS + 4 * family + {0, 1, 2, 3}] = samples, sum, min, max (min = max = 0 without samples):
+ *   family 0, stay:    T[r_{s+1}][j] - T[r_s][j] for s = 1 .. q - 1 (>= 0, and 0 does occur), one sample per consecutive pair of recorded
+ *                      rounds of a node; also binned, stay_hist[g * bins + min(stay / bin_width, bins - 1)]
+ *   family 1, skipped: r_{s+1} - r_s - 1 for the same pairs, the rounds the node jumped over; statistics only
+ *   family 2, skew:    for every row r < R_i with at least two non-empty cells, max - min of those cells, one sample per (instance,
+ *                      round); also binned into skew_hist in the same way
+ *   family 3, reach:   for every row 1 <= r < R_i (row 0 is always empty) the number of non-empty cells, one sample per (instance, round)
+ * bin_width >= 1, bins >= 1, groups * bins <= 2^31 (LBFT_ERR_INVALID otherwise, and for NULL arguments, before any HIP call);
+ * LBFT_ERR_STATE before a finished run, or when the trace was not enabled.  Computed on the device (lbft_k_rs_rounds,
+ * liblbft_round_stats.so beside this library; LBFT_ERR_UNSUPPORTED naming it when it is missing); every accumulation is an integer add,
+ * min or max: bit-reproducible. */
+#define LBFT_ROUND_STATS 16
+int lbft_batch_round_stats(const lbft_batch* b, uint32_t bin_width, uint32_t bins, uint64_t* stay_hist, uint64_t* skew_hist, uint64_t* stats);
+int lbft_batch_round_switches_all(const lbft_batch* b, int64_t* out, size_t cap_rounds, uint64_t* max_round /*[m]*/, uint64_t* messages /*[m], may be NULL*/);
 
 /* ---- Node-level interface: the reference's trait surface for ONE node of ONE instance, without the event loop
  * (bft-lib/src/interfaces.rs:12-86), so that record-store / pacemaker scenarios can be replayed step by step

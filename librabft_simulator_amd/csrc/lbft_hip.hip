@@ -25,6 +25,8 @@
 #include "lbft_paramsets.h"
 #include "lbft_commit_times.h"
 #include "lbft_commit_timeline.h"
+#include "lbft_round_stats.h"
+#include "lbft_round_timeline.h"
 
 using namespace lbft;
 
@@ -1528,6 +1530,101 @@ int lbft_batch_commit_series(const lbft_batch* b, uint32_t bin_width, uint32_t b
 int lbft_batch_commit_stalls(const lbft_batch* b, const int64_t* since, uint32_t bin_width, uint32_t bins, uint64_t* hist, uint64_t* stats) {
   if (!b || !hist || !stats || bin_width == 0 || bins == 0) { g_err = "NULL argument, or bin_width / bins of 0"; return LBFT_ERR_INVALID; }
   return commit_timeline(b, since, bin_width, bins, hist, stats, "commit stalls");
+}
+
+// ---- round statistics (lbft_batch_round_stats) ----
+// The kernel lives in liblbft_round_stats.so (lbft_round_stats.hip), opened beside this library on first use, like the other two side
+// libraries: a traced batch that never asks for the statistics loads nothing.
+static std::mutex g_rs_mutex;
+static lbft_rs_rounds_fn g_rs_rounds = nullptr;
+static int load_round_stats_lib() {
+  std::lock_guard<std::mutex> lock(g_rs_mutex);
+  if (g_rs_rounds) return LBFT_OK;
+  const std::string path = side_lib_path(LBFT_ROUND_STATS_LIB);
+  void* h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
+  if (!h) { const char* e = dlerror(); g_err = "round statistics need " + path + " (build it with librabft_simulator_amd.build): " + (e ? e : "not found"); return LBFT_ERR_UNSUPPORTED; }
+  g_rs_rounds = reinterpret_cast<lbft_rs_rounds_fn>(dlsym(h, "lbft_rs_launch_rounds"));
+  if (!g_rs_rounds) { g_err = path + " lacks lbft_rs_launch_rounds"; return LBFT_ERR_UNSUPPORTED; }
+  return LBFT_OK;
+}
+
+// Round statistics per group, computed on the device from the trace rows (lbft_k_rs_rounds).  Arguments are checked before the first
+// HIP call.
+int lbft_batch_round_stats(const lbft_batch* b, uint32_t bin_width, uint32_t bins, uint64_t* stay_hist, uint64_t* skew_hist, uint64_t* stats) {
+  if (!b || !stay_hist || !skew_hist || !stats || bin_width == 0 || bins == 0) { g_err = "NULL argument, or bin_width / bins of 0"; return LBFT_ERR_INVALID; }
+  const size_t groups = group_count(b);
+  if ((u64)groups * bins > (1ULL << 31)) { g_err = "groups x bins exceeds 2^31"; return LBFT_ERR_INVALID; }
+  if (!b->ran) { g_err = "run the batch first"; return LBFT_ERR_STATE; }
+  if (b->p.rcap == 0) { g_err = "lbft_batch_enable_round_trace was not called"; return LBFT_ERR_STATE; }
+  int rc = load_round_stats_lib();
+  if (rc != LBFT_OK) return rc;
+  HIP_TRY(hipSetDevice(b->device));
+  GroupIndex gi(b);
+  const size_t hist_bytes = groups * bins * sizeof(u64), stats_bytes = groups * LBFT_ROUND_STATS * sizeof(u64);
+  unsigned long long *d_stay = nullptr, *d_skew = nullptr, *d_stats = nullptr;
+  hipError_t e = hipMalloc(&d_stay, hist_bytes);
+  if (e == hipSuccess) e = hipMalloc(&d_skew, hist_bytes);
+  if (e == hipSuccess) e = hipMalloc(&d_stats, stats_bytes);
+  if (e == hipSuccess) e = gi.upload(b->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(d_stay, 0, hist_bytes, b->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(d_skew, 0, hist_bytes, b->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(d_stats, 0, stats_bytes, b->stream);
+  if (e == hipSuccess) e = g_rs_rounds(&b->p, b->d_state, gi.d_inst, gi.d_off, (u32)groups, gi.max_group, bin_width, bins, d_stay, d_skew, d_stats, b->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(stay_hist, d_stay, hist_bytes, hipMemcpyDeviceToHost, b->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(skew_hist, d_skew, hist_bytes, hipMemcpyDeviceToHost, b->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(stats, d_stats, stats_bytes, hipMemcpyDeviceToHost, b->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+  hipFree(d_stay); hipFree(d_skew); hipFree(d_stats);
+  if (e != hipSuccess) return hip_fail(e, "round statistics");
+  for (size_t q = 0; q < groups * RTL_FAMILIES; q++) stats[q * 4 + 2] = stats[q * 4] ? ~stats[q * 4 + 2] : 0;  // (max(~sample) -> min)
+  return LBFT_OK;
+}
+
+// Every instance's round-switch table in one call: out[(inst * cap_rounds + round) * num_nodes + node], what lbft_batch_round_switches
+// gives instance by instance.  The trace words of a tile (tw instances, word-interleaved) are one contiguous range and the tiles lie at
+// a constant pitch, so a chunk of tiles is one strided copy; the host takes the interleaving apart.
+int lbft_batch_round_switches_all(const lbft_batch* b, int64_t* out, size_t cap_rounds, uint64_t* max_round, uint64_t* messages) {
+  if (!b || (!out && cap_rounds) || !max_round) { g_err = "NULL argument"; return LBFT_ERR_INVALID; }
+  if (!b->ran) { g_err = "run the batch first"; return LBFT_ERR_STATE; }
+  if (b->p.rcap == 0) { g_err = "lbft_batch_enable_round_trace was not called"; return LBFT_ERR_STATE; }
+  HIP_TRY(hipSetDevice(b->device));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  const Params& p = b->p;
+  const size_t n = p.n, rcap = p.rcap, tw = p.tw, words = n * rcap + n;  // trace words per instance
+  const size_t tiles = (b->m + tw - 1) / tw, pitch = (size_t)p.total_words * 4 * tw;  // (the state holds whole tiles: m is padded to 64)
+  const size_t w0 = cap_rounds ? 0 : n * rcap;  // (cap_rounds == 0 asks for max_round / messages alone: the cells stay on the device)
+  const size_t tile_bytes = (words - w0) * 4 * tw;
+  const size_t chunk = std::max<size_t>(1, (32u << 20) / tile_bytes);  // tiles per copy
+  std::vector<u32> h, ev;
+  for (size_t t0 = 0; t0 < tiles; t0 += chunk) {
+    const size_t nt = std::min(chunk, tiles - t0);
+    h.resize(nt * (words - w0) * tw);
+    const char* src = reinterpret_cast<const char*>(b->d_state) + t0 * pitch;
+    HIP_TRY(hipMemcpy2D(h.data(), tile_bytes, src + ((size_t)p.off_trace + w0) * 4 * tw, pitch, tile_bytes, nt, hipMemcpyDeviceToHost));
+    if (messages) {
+      ev.resize(nt * 3 * tw);
+      HIP_TRY(hipMemcpy2D(ev.data(), 12 * tw, src + (size_t)I_EV0 * 4 * tw, pitch, 12 * tw, nt, hipMemcpyDeviceToHost));
+    }
+    for (size_t t = 0; t < nt; t++)
+      for (size_t l = 0; l < tw && (t0 + t) * tw + l < b->m; l++) {
+        const size_t inst = (t0 + t) * tw + l;
+        const u32* w = h.data() + t * (words - w0) * tw + l;  // word k of the instance's trace at w[(k - w0) * tw]
+        u32 mr = 0;
+        for (size_t k = 0; k < n; k++) mr = std::max(mr, w[(n * rcap + k - w0) * tw]);
+        max_round[inst] = mr;
+        int64_t* o = out + inst * cap_rounds * n;
+        for (size_t r = 0; r < cap_rounds; r++)
+          for (size_t k = 0; k < n; k++) {
+            const u32 v = r < mr && r < rcap ? w[(k * rcap + r) * tw] : 0xffffffffu;
+            o[r * n + k] = v == 0xffffffffu ? INT64_MIN : (int64_t)(i32)v;
+          }
+        if (messages) {
+          const u32* c = ev.data() + t * 3 * tw + l;
+          messages[inst] = (uint64_t)c[0] + c[tw] + c[2 * tw];  // DataWriter::add_message_counter: every non-timer event
+        }
+      }
+  }
+  return LBFT_OK;
 }
 
 int lbft_batch_committed_history(const lbft_batch* b, size_t inst, uint32_t node, lbft_commit* out, size_t cap, size_t* len) {

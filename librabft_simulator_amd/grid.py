@@ -12,6 +12,10 @@ value too); the lines then carry a ``"partition"`` key.  ``--stalls`` records co
 (BatchResult.stalls_by_param_set with ``since="partition_end"``: gaps between a node's commits, time from the partition's end to the next
 commit, time since the last commit, longest commit-free interval); ``--series WIDTH`` adds ``"series"``, the point's commits per WIDTH
 ticks (BatchResult.commit_series).
+``--rounds`` records the round-switch trace (``--round-trace N`` rounds per node, by default max_clock / 5 + 64, at most 65 536; an
+instance that passes it counts as faulted and gives no sample) and adds a ``"round_stats"`` object (BatchResult.rounds_by_param_set: how
+long nodes stay in a round, how many rounds they jump, how far apart the nodes of a network enter a round and how many of them enter it);
+``"rounds"``, the final active round's mean / min / max, stays as it is.
 """
 import argparse
 import itertools
@@ -71,6 +75,11 @@ def set_assignment(points, seeds_per_point, assign):
     return (k % points).astype(np.uint32), k // points
 
 
+def round_trace_capacity(max_clock, explicit):
+    """Rounds per node the trace of ``--rounds`` keeps: ``--round-trace``, else BatchSimulator.loop_until's own first guess."""
+    return int(explicit) if explicit is not None else min(int(max_clock) // 5 + 64, 1 << 16)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m librabft_simulator_amd.grid", description=__doc__.split("\n\n")[0])
     ap.add_argument("--nodes", type=int, default=4)
@@ -91,7 +100,11 @@ def main(argv=None):
     ap.add_argument("--partition", type=_partitions, default=None, help="grid axis: SIZE:START:END[,...], 'none' allowed as a value")
     ap.add_argument("--stalls", action="store_true", help="record commit times and add each point's stall / recovery summary")
     ap.add_argument("--series", type=int, default=None, metavar="WIDTH", help="record commit times and add each point's commits per WIDTH ticks")
+    ap.add_argument("--rounds", action="store_true", help="record the round-switch trace and add each point's round statistics")
+    ap.add_argument("--round-trace", type=int, default=None, metavar="N", help="with --rounds: rounds per node the trace keeps")
     args = ap.parse_args(argv)
+    if args.round_trace is not None and (args.round_trace < 1 or not args.rounds):
+        ap.error("--round-trace N goes with --rounds and must be at least 1")
     if args.series is not None and args.series < 1:
         ap.error("--series WIDTH must be at least 1")
     points = grid_points(args)
@@ -107,10 +120,11 @@ def main(argv=None):
     kw = {"commit_times": True} if args.latency or args.stalls or args.series is not None else {}
     sim = BatchSimulator.with_param_sets(seeds, args.nodes, sets, set_of, commands_per_epoch=args.commands_per_epoch, device=args.device, **kw)
     try:
-        res = sim.loop_until(args.max_clock, allow_faults=True)
+        res = sim.loop_until(args.max_clock, allow_faults=True, round_trace=round_trace_capacity(args.max_clock, args.round_trace) if args.rounds else None)
         latency = res.latency_by_param_set() if args.latency else None
         stalls = res.stalls_by_param_set(since="partition_end") if args.stalls else None
         series = res.commit_series(bin_width=args.series) if args.series is not None else None
+        round_stats = res.rounds_by_param_set() if args.rounds else None
         for k, (pt, row) in enumerate(zip(points, res.by_param_set())):
             line = dict(pt, nodes=args.nodes, max_clock=args.max_clock, seeds=args.seeds_per_point, assign=args.assign)
             line.update(instances=row["instances"], faulted=row["faulted"], commits=row["commits"], rounds=row["rounds"])
@@ -120,6 +134,8 @@ def main(argv=None):
                 line["stalls"] = stalls[k]
             if series is not None:
                 line["series"] = [int(v) for v in series[k]]
+            if round_stats is not None:
+                line["round_stats"] = round_stats[k]
             print(json.dumps(line), flush=True)
     finally:
         sim.close()

@@ -280,6 +280,60 @@ class BatchResult:
         rows = [[None if v == lo else int(v) for v in out[r]] for r in range(min(int(mr.value), out.shape[0]))]
         return rows, int(msgs.value)
 
+    def round_tables(self, cap_rounds=None):
+        """The DataWriter tables of every instance in one read-back (lbft_batch_round_switches_all): ``(tables, max_rounds, messages)``,
+        ``tables[instance, round, node]`` int64 = the GlobalTime at which the node was first seen in that round, ``INT64_MIN`` = empty
+        cell; instance i's table is the rows below ``min(max_rounds[i], cap_rounds)``, everything past them is empty; ``messages[i]`` is
+        its number_of_messages.  For every instance what ``round_switches(i)`` gives.  ``cap_rounds=None``: as many rows as the longest
+        table has (at least 1).  Needs a run with the round trace (``loop_until(..., round_trace=N)``)."""
+        if cap_rounds is not None and int(cap_rounds) < 0:
+            raise ValueError("cap_rounds must be at least 0")
+        m, n = self._sim.num_instances, self._sim.num_nodes
+        max_rounds = np.zeros(m, dtype=np.uint64)
+        messages = np.zeros(m, dtype=np.uint64)
+        if cap_rounds is None:  # (a call without rows reads max_rounds alone: it sizes the tables)
+            check(_lib.lib().lbft_batch_round_switches_all(self._sim._h, None, 0, max_rounds.ctypes.data, None))
+            cap = max(int(max_rounds.max()) if m else 0, 1)
+        else:
+            cap = int(cap_rounds)
+        tables = np.full((m, cap, n), np.iinfo(np.int64).min, dtype=np.int64)
+        check(_lib.lib().lbft_batch_round_switches_all(self._sim._h, tables.ctypes.data, cap, max_rounds.ctypes.data, messages.ctypes.data))
+        return tables, max_rounds, messages
+
+    def round_histogram(self, bin_width=None, bins=None):
+        """Round statistics computed on the device from the round trace (lbft_batch_round_stats), per group (the parameter sets of a
+        ``with_param_sets`` batch, else one group): ``(stay_hist, skew_hist, stats)``.  ``stay_hist[group, min(stay // bin_width, bins - 1)]``
+        counts, for every node, the times between consecutive rounds it was recorded in; ``skew_hist`` the span between the first and
+        the last node entering a round, per (instance, round) that at least two nodes entered; ``stats[group]`` (16 uint64) holds
+        ``(samples, sum, min, max)`` of four families: ``stay``, ``skipped`` (the rounds a node jumped over between two recorded
+        rounds), ``skew`` and ``reach`` (the number of nodes that entered a round, per (instance, round >= 1)).  Rows are the rounds
+        below the highest round an instance reached (the DataWriter's table); instances with a fault are skipped.  Groups and default
+        binning as ``latency_histogram``.  Needs a run with the round trace (``loop_until(..., round_trace=N)``)."""
+        bin_width, bins = self._binning(bin_width, bins)
+        groups = self._groups()
+        stay = np.zeros((groups, bins), dtype=np.uint64)
+        skew = np.zeros((groups, bins), dtype=np.uint64)
+        stats = np.zeros((groups, _lib.ROUND_STATS), dtype=np.uint64)
+        check(_lib.lib().lbft_batch_round_stats(self._sim._h, bin_width, bins, stay.ctypes.data, skew.ctypes.data, stats.ctypes.data))
+        return stay, skew, stats
+
+    def rounds_by_param_set(self, quantiles=(0.5, 0.9, 0.99)):
+        """Per group of ``round_histogram`` (default, exact binning), in set order: ``stay`` and ``skew`` = samples, mean, min, max and
+        ``quantiles`` ({str(q): ticks}, the inverted-CDF rule of ``histogram_quantile``), ``skipped`` and ``reach`` = samples, mean, min,
+        max.  ``None`` where there are no samples."""
+        width, _ = self._binning(None, None)
+        stay, skew, stats = self.round_histogram()
+        out = []
+        for g in range(stay.shape[0]):
+            row = {"set": g}
+            for f, name in enumerate(("stay", "skipped", "skew", "reach")):
+                n, total, lo, hi = (int(v) for v in stats[g, 4 * f:4 * f + 4])
+                row[name] = {"samples": n, "mean": total / n if n else None, "min": lo if n else None, "max": hi if n else None}
+            row["stay"]["quantiles"] = {str(q): histogram_quantile(stay[g], width, q) for q in quantiles}
+            row["skew"]["quantiles"] = {str(q): histogram_quantile(skew[g], width, q) for q in quantiles}
+            out.append(row)
+        return out
+
     def by_param_set(self):
         """Per parameter set of a ``BatchSimulator.with_param_sets`` batch, in set order: the number of instances, of faulted instances,
         and mean / min / max over its instances of the commits and of the active round (each instance's minimum over its nodes)."""
