@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc", "lbft_hip.hip")
 DEPS = [SRC] + [os.path.join(HERE, "csrc", f) for f in ("lbft_core.h", "lbft_math.h", "lbft_tables.h", "lbft_save_node.h", "lbft_launch.h", "lbft_plan.h",
                                                          "lbft_paramsets.h", "lbft_commit_times.h", "lbft_commit_timeline.h", "lbft_round_stats.h",
-                                                         "lbft_round_timeline.h", "lbft_node_ops.h")] + [
+                                                         "lbft_round_timeline.h", "lbft_group_stats.h", "lbft_node_ops.h")] + [
     os.path.join(HERE, "..", "include", "lbft.h")]
 OUT = os.path.join(HERE, "liblbft_hip.so")
 PS_SRC = os.path.join(HERE, "csrc", "lbft_paramsets.hip")
@@ -24,11 +24,12 @@ PS_DEPS = [PS_SRC] + [os.path.join(HERE, "csrc", f) for f in ("lbft_core.h", "lb
 PS_OUT = os.path.join(HERE, "liblbft_paramsets.so")
 CT_SRC = os.path.join(HERE, "csrc", "lbft_commit_times.hip")
 CT_DEPS = [CT_SRC] + [os.path.join(HERE, "csrc", f) for f in ("lbft_core.h", "lbft_math.h", "lbft_launch.h", "lbft_commit_times.h",
-                                                               "lbft_commit_timeline.h", "lbft_lane_run.h")] + [
+                                                               "lbft_commit_timeline.h", "lbft_group_stats.h", "lbft_lane_run.h")] + [
     os.path.join(HERE, "..", "include", "lbft.h")]
 CT_OUT = os.path.join(HERE, "liblbft_commit_times.so")
 RS_SRC = os.path.join(HERE, "csrc", "lbft_round_stats.hip")
-RS_DEPS = [RS_SRC] + [os.path.join(HERE, "csrc", f) for f in ("lbft_core.h", "lbft_math.h", "lbft_round_stats.h", "lbft_round_timeline.h")] + [
+RS_DEPS = [RS_SRC] + [os.path.join(HERE, "csrc", f) for f in ("lbft_core.h", "lbft_math.h", "lbft_round_stats.h", "lbft_round_timeline.h",
+                                                               "lbft_group_stats.h")] + [
     os.path.join(HERE, "..", "include", "lbft.h")]
 RS_OUT = os.path.join(HERE, "liblbft_round_stats.so")
 LIBS = ((SRC, OUT, DEPS), (PS_SRC, PS_OUT, PS_DEPS), (CT_SRC, CT_OUT, CT_DEPS), (RS_SRC, RS_OUT, RS_DEPS))

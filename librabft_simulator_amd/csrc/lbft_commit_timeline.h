@@ -1,7 +1,7 @@
 // lbft_commit_timeline.h -- the arithmetic of the commit timelines (lbft_batch_commit_series / lbft_batch_commit_stalls, include/lbft.h):
 // how one node's row of recorded commit times turns into samples.  Compiled by the device kernel (lbft_k_ct_timeline,
 // lbft_commit_times.hip) and by a plain C++ host shim (tests/commit_timeline_host.cpp), so the CPU tests check the same code the GPU runs.
-// Needs nothing but <stdint.h>.
+// Needs nothing but <stdint.h> and lbft_group_stats.h, which says what becomes of a sample.
 //
 // A row c[0 .. nc) is non-negative and non-decreasing.  Its commit instants t_1 < ... < t_r are its distinct values; they cut
 // [0, max_clock] into r + 1 intervals: the leading one [0, t_1], the gaps t_{s+1} - t_s, and the tail max_clock - t_r.  Each entry is
@@ -13,22 +13,9 @@
 
 #include <stdint.h>
 
-#ifndef LBFT_HD  // (lbft_math.h's, when that came first)
-#if defined(__HIPCC__)
-#define LBFT_HD __host__ __device__ __forceinline__
-#else
-#define LBFT_HD inline
-#endif
-#endif
+#include "lbft_group_stats.h"  // LBFT_HD; GsStat / gs_bin: what becomes of a sample
 
 #define LBFT_CTL_NONE 0xffffffffu  // "no instant at or after since" (every real distance is <= max_clock < 2^31)
-
-// min(v / bin_width, bins - 1): the last bin also counts everything above it.  bin_width >= 1, bins >= 1.  (Every sample is a clock
-// difference within [0, max_clock] < 2^31: a 32-bit division, which the GPU emulates in a fraction of a 64-bit one's instructions.)
-LBFT_HD uint32_t ctl_bin(uint32_t v, uint32_t bin_width, uint32_t bins) {
-  const uint32_t q = v / bin_width;
-  return q < bins - 1u ? q : bins - 1u;
-}
 
 // What a piece of a row has seen so far.
 struct CtlRow {
@@ -69,16 +56,7 @@ LBFT_HD uint32_t ctl_longest(const CtlRow& r, int32_t max_clock) {
   return r.longest > tail ? r.longest : tail;
 }
 
-// One sample family's statistics as they are accumulated: samples, sum, max(~value) (the minimum's complement: zero-initialised and
-// combined by max like the others) and max.  LBFT_STALL_STATS = 4 families x these 4.
-struct CtlStat {
-  uint64_t cnt, sum, nmin, max;
-};
-LBFT_HD void ctl_stat_add(CtlStat& s, uint32_t v) {
-  s.cnt++; s.sum += v;
-  s.nmin = ~(uint64_t)v > s.nmin ? ~(uint64_t)v : s.nmin;
-  s.max = v > s.max ? v : s.max;
-}
+// The sample families (every sample is a clock difference within [0, max_clock] < 2^31).  LBFT_STALL_STATS = these 4 x GsStat's 4 words.
 enum { CTL_GAPS = 0, CTL_FIRST = 1, CTL_TAIL = 2, CTL_LONGEST = 3, CTL_FAMILIES = 4 };
 
 #endif  // LBFT_COMMIT_TIMELINE_H

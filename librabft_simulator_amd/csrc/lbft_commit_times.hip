@@ -43,10 +43,9 @@ void lbft_k_ct_ps_run1(Params p, u32* __restrict__ state, u32* __restrict__ unfi
 
 // Commit-latency histogram: grid = (lanes of the largest group / LBFT_HIST_BLOCK, groups); one lane per (instance, node) of the
 // workgroup's group walks the node's log -- block id -> author (B_LINK) and proposer time (B_TIME), the author's startup time, the commit
-// time -- and bins latency = commit time - (startup[author] + block time) into the workgroup's LDS histogram with integer atomics.  The
-// LDS histogram is then added into the group's global one, one atomic per non-zero bin per workgroup; samples / sum / min / max likewise
-// (once per workgroup).  Histograms wider than LBFT_HIST_LDS_BINS are binned in passes of that many bins.  Instances with a non-zero
-// fault word are skipped.  Every accumulation is an integer add / max: the result does not depend on the order of the atomics.
+// time -- and accumulates latency = commit time - (startup[author] + block time) by the scheme of lbft_group_stats.h: the workgroup's LDS
+// histogram in passes of LBFT_HIST_LDS_BINS bins, samples / sum / min / max in registers, then wavefront, LDS and one global atomic each
+// per workgroup.  Instances with a non-zero fault word are skipped.
 #define LBFT_HIST_BLOCK 256
 #define LBFT_HIST_LDS_BINS 8192  // 32 KiB of u32 counts (a workgroup counts at most 256 lanes x lcap <= 65 534 samples: no overflow)
 __global__ __launch_bounds__(LBFT_HIST_BLOCK) void lbft_k_ct_latency_hist(Params p, const u32* __restrict__ state, const i32* __restrict__ ctimes,
@@ -54,49 +53,42 @@ __global__ __launch_bounds__(LBFT_HIST_BLOCK) void lbft_k_ct_latency_hist(Params
                                                                           u32 bin_width, u32 bins, unsigned long long* __restrict__ hist,
                                                                           unsigned long long* __restrict__ stats) {
   __shared__ u32 h[LBFT_HIST_LDS_BINS];
-  __shared__ unsigned long long s_cnt, s_sum, s_nmin, s_max;
+  __shared__ unsigned long long s_stat[4];
   const u32 g = blockIdx.y;
-  const u32 first = grp_inst ? grp_off[g] : 0u, cnt = grp_inst ? grp_off[g + 1] - first : p.m;
+  const uint2 grp = gs_group(grp_inst, grp_off, g, p.m);
+  const u32 first = grp.x, cnt = grp.y;
   const u32 lanes = cnt * p.n;  // (< 2^31: lbft_batch_create bounds instances x nodes)
   if (blockIdx.x * LBFT_HIST_BLOCK >= lanes) return;  // (the whole workgroup: its group has fewer lanes)
   const u32 t = blockIdx.x * LBFT_HIST_BLOCK + threadIdx.x;
-  u32 node = 0, i = grp_inst ? grp_inst[first] : 0u, nc = 0;
+  u32 node = 0, i = gs_instance(grp_inst, first, 0), nc = 0;
   if (t < lanes) {
     node = t / cnt;  // consecutive lanes -> consecutive instances of one node
-    i = grp_inst ? grp_inst[first + t % cnt] : t % cnt;
+    i = gs_instance(grp_inst, first, t % cnt);
   }
   Sim s(p, const_cast<u32*>(state), i);
   if (t < lanes && s.ld(I_FAULT) == 0) nc = s.nfm(node, NF_NCOMMITS);
   if (nc > p.lcap) nc = p.lcap;
   const i32* ct = ctimes + ((size_t)i * p.n + node) * p.lcap;
-  if (threadIdx.x == 0) { s_cnt = 0; s_sum = 0; s_nmin = 0; s_max = 0; }
+  gs_stats_clear<4>(s_stat);
+  GsStat st = {};
   for (u32 base = 0; base < bins; base += LBFT_HIST_LDS_BINS) {
     const u32 span = bins - base < LBFT_HIST_LDS_BINS ? bins - base : LBFT_HIST_LDS_BINS;
-    for (u32 k = threadIdx.x; k < span; k += LBFT_HIST_BLOCK) h[k] = 0;
+    gs_lds_clear<LBFT_HIST_BLOCK>(h, span);
     __syncthreads();
-    unsigned long long cnt_l = 0, sum_l = 0, nmin_l = 0, max_l = 0;
     for (u32 k = 0; k < nc; k++) {
       const i32 c = ct[k];
       if (c < 0) continue;  // (not recorded)
       const u32 b = s.ld(p.off_log + node * p.lcap + k);
       const u32 a = s.blk_author(b);
       const i64 lat = (i64)c - ((i64)(i32)s.nfm(a, NF_STARTUP) + (i64)(i32)s.bf(b, B_TIME));  // in [0, max_clock]
-      const u64 l = (u64)lat;
-      const u64 q = l / bin_width;
-      const u32 bin = q < bins - 1u ? (u32)q : bins - 1u;
-      if (bin >= base && bin - base < span) atomicAdd(&h[bin - base], 1u);
-      cnt_l++; sum_l += l;
-      nmin_l = ~l > nmin_l ? ~l : nmin_l;
-      max_l = l > max_l ? l : max_l;
+      const u32 l = (u32)lat;  // (max_clock < 2^31: nothing is cut off)
+      gs_lds_count(h, l, bin_width, bins, base, span);
+      if (base == 0) gs_stat_add(st, l);
     }
-    if (base == 0 && cnt_l) { atomicAdd(&s_cnt, cnt_l); atomicAdd(&s_sum, sum_l); atomicMax(&s_nmin, nmin_l); atomicMax(&s_max, max_l); }
+    if (base == 0) gs_reduce_to_lds<1>(&st, s_stat, threadIdx.x % 64 == 0);
     __syncthreads();
-    for (u32 k = threadIdx.x; k < span; k += LBFT_HIST_BLOCK)
-      if (h[k]) atomicAdd(&hist[(size_t)g * bins + base + k], (unsigned long long)h[k]);
-    if (base == 0 && threadIdx.x == 0 && s_cnt) {
-      atomicAdd(&stats[g * 4 + 0], s_cnt); atomicAdd(&stats[g * 4 + 1], s_sum);
-      atomicMax(&stats[g * 4 + 2], s_nmin); atomicMax(&stats[g * 4 + 3], s_max);
-    }
+    gs_lds_flush<LBFT_HIST_BLOCK>(h, hist, g, bins, base, span);
+    if (base == 0) gs_stats_out<4>(s_stat, stats, g);
     __syncthreads();  // (before the next pass clears h)
   }
 }
@@ -107,9 +99,8 @@ __global__ __launch_bounds__(LBFT_HIST_BLOCK) void lbft_k_ct_latency_hist(Params
 // only the nc recorded entries of a row are read.  A lane takes its predecessor's entry by __shfl_up -- lane 0 of the segment the last
 // entry of the row's previous chunk -- and lbft_commit_timeline.h turns (entry, predecessor) into samples; the per-row quantities
 // (longest interval, last instant, first instant at or after `since`) are segment reductions by __shfl_xor.
-// grid = (workgroups per group, groups); a workgroup strides over the rows of its group, LBFT_TL_ROWS at a time, and bins into its
-// LDS histogram with integer atomics, in passes of LBFT_HIST_LDS_BINS bins; then one global atomic per non-zero bin per workgroup.
-// The statistics stay in registers over the whole stride, are reduced in the wavefront, then in LDS, then go out once per workgroup.
+// grid = (workgroups per group, groups); a workgroup strides over the rows of its group, LBFT_TL_ROWS at a time, and accumulates by
+// the scheme of lbft_group_stats.h, in passes of LBFT_HIST_LDS_BINS bins.
 // stalls == 0: the series (one sample per entry: its commit time; no statistics).  stalls != 0: the gap histogram and
 // stats[group * 16 + family * 4 + {samples, sum, ~min, max}].  Instances with a non-zero fault word are skipped.
 #define LBFT_TL_BLOCK 256
@@ -125,16 +116,17 @@ __global__ __launch_bounds__(LBFT_TL_BLOCK) void lbft_k_ct_timeline(Params p, co
   __shared__ u32 h[LBFT_HIST_LDS_BINS];
   __shared__ unsigned long long s_stat[LBFT_STALL_STATS];
   const u32 g = blockIdx.y;
-  const u32 first = grp_inst ? grp_off[g] : 0u, cnt = grp_inst ? grp_off[g + 1] - first : p.m;
+  const uint2 grp = gs_group(grp_inst, grp_off, g, p.m);
+  const u32 first = grp.x, cnt = grp.y;
   const u32 rows = cnt * p.n;  // (< 2^31: lbft_batch_create bounds instances x nodes)
   if (blockIdx.x * LBFT_TL_ROWS >= rows) return;  // (the whole workgroup: its group has fewer rows)
   const u32 seg = threadIdx.x / LBFT_TL_SEG, k0 = threadIdx.x % LBFT_TL_SEG;
   const i32 since = since_of ? since_of[g] : 0;
-  if (threadIdx.x < LBFT_STALL_STATS) s_stat[threadIdx.x] = 0;
-  CtlStat st[CTL_FAMILIES] = {};
+  gs_stats_clear<LBFT_STALL_STATS>(s_stat);
+  GsStat st[CTL_FAMILIES] = {};
   for (u32 base = 0; base < bins; base += LBFT_HIST_LDS_BINS) {
     const u32 span = bins - base < LBFT_HIST_LDS_BINS ? bins - base : LBFT_HIST_LDS_BINS;
-    for (u32 k = threadIdx.x; k < span; k += LBFT_TL_BLOCK) h[k] = 0;
+    gs_lds_clear<LBFT_TL_BLOCK>(h, span);
     __syncthreads();
     // What a row starts from -- its first chunk, the instance's fault word, the node's commit count -- is loaded one row ahead, all
     // three together (none waits for another), and most rows are one chunk: the loads of the next row are in flight while this one is
@@ -144,7 +136,7 @@ __global__ __launch_bounds__(LBFT_TL_BLOCK) void lbft_k_ct_timeline(Params p, co
     i32 head_next = -1;
     u32 fault_next = 1, nc_next = 0;
     auto fetch = [&](u32 r) {
-      const u32 node = r % p.n, i = grp_inst ? grp_inst[first + r / p.n] : r / p.n;
+      const u32 node = r % p.n, i = gs_instance(grp_inst, first, r / p.n);
       ct_next = ctimes + ((size_t)i * p.n + node) * p.lcap;
       head_next = k0 < p.lcap ? ct_next[k0] : -1;
       Sim s(p, const_cast<u32*>(state), i);
@@ -172,9 +164,8 @@ __global__ __launch_bounds__(LBFT_TL_BLOCK) void lbft_k_ct_timeline(Params p, co
         if (stalls) { sample = ctl_entry(row, c, prev, since); have = sample != 0; }
         else { sample = (u32)c; have = c >= 0; }
         if (have) {
-          const u32 bin = ctl_bin(sample, bin_width, bins);
-          if (bin >= base && bin - base < span) atomicAdd(&h[bin - base], 1u);
-          if (stalls && base == 0) ctl_stat_add(st[CTL_GAPS], sample);
+          gs_lds_count(h, sample, bin_width, bins, base, span);
+          if (stalls && base == 0) gs_stat_add(st[CTL_GAPS], sample);
         }
       }
       if (stalls && base == 0) {
@@ -186,35 +177,16 @@ __global__ __launch_bounds__(LBFT_TL_BLOCK) void lbft_k_ct_timeline(Params p, co
           row = ctl_merge(row, o);
         }
         if (k0 == 0) {  // one sample per node
-          if (row.first != LBFT_CTL_NONE) ctl_stat_add(st[CTL_FIRST], row.first);
-          ctl_stat_add(st[CTL_TAIL], ctl_tail(row, p.max_clock));
-          ctl_stat_add(st[CTL_LONGEST], ctl_longest(row, p.max_clock));
+          if (row.first != LBFT_CTL_NONE) gs_stat_add(st[CTL_FIRST], row.first);
+          gs_stat_add(st[CTL_TAIL], ctl_tail(row, p.max_clock));
+          gs_stat_add(st[CTL_LONGEST], ctl_longest(row, p.max_clock));
         }
       }
     }
-    if (stalls && base == 0) {  // wavefront, then workgroup (LDS), then one global atomic per statistic
-      for (u32 f = 0; f < CTL_FAMILIES; f++) {
-        CtlStat v = st[f];
-        for (int d = 32; d; d >>= 1) {
-          const unsigned long long oc = __shfl_xor((unsigned long long)v.cnt, d, 64), os = __shfl_xor((unsigned long long)v.sum, d, 64);
-          const unsigned long long on = __shfl_xor((unsigned long long)v.nmin, d, 64), om = __shfl_xor((unsigned long long)v.max, d, 64);
-          v.cnt += oc; v.sum += os;
-          v.nmin = on > v.nmin ? on : v.nmin;
-          v.max = om > v.max ? om : v.max;
-        }
-        if (threadIdx.x % 64 == 0 && v.cnt) {
-          atomicAdd(&s_stat[f * 4 + 0], (unsigned long long)v.cnt); atomicAdd(&s_stat[f * 4 + 1], (unsigned long long)v.sum);
-          atomicMax(&s_stat[f * 4 + 2], (unsigned long long)v.nmin); atomicMax(&s_stat[f * 4 + 3], (unsigned long long)v.max);
-        }
-      }
-    }
+    if (stalls && base == 0) gs_reduce_to_lds<CTL_FAMILIES>(st, s_stat, threadIdx.x % 64 == 0);
     __syncthreads();
-    for (u32 k = threadIdx.x; k < span; k += LBFT_TL_BLOCK)
-      if (h[k]) atomicAdd(&hist[(size_t)g * bins + base + k], (unsigned long long)h[k]);
-    if (stalls && base == 0 && threadIdx.x < LBFT_STALL_STATS && s_stat[threadIdx.x & ~3u]) {
-      if ((threadIdx.x & 3u) < 2u) atomicAdd(&stats[g * LBFT_STALL_STATS + threadIdx.x], s_stat[threadIdx.x]);
-      else atomicMax(&stats[g * LBFT_STALL_STATS + threadIdx.x], s_stat[threadIdx.x]);
-    }
+    gs_lds_flush<LBFT_TL_BLOCK>(h, hist, g, bins, base, span);
+    if (stalls && base == 0) gs_stats_out<LBFT_STALL_STATS>(s_stat, stats, g);
     __syncthreads();  // (before the next pass clears h)
   }
 }
@@ -250,13 +222,8 @@ __attribute__((visibility("default"))) hipError_t lbft_ct_launch_timeline(const 
                                                                          const i32* since_of, u32 bin_width, u32 bins, unsigned long long* hist,
                                                                          unsigned long long* stats, hipStream_t stream) {
   if (bin_width == 0 || bins == 0 || n_groups == 0 || max_group == 0 || (stalls && !stats)) return hipErrorInvalidValue;
-  // about LBFT_TL_WORKGROUPS workgroups in all: each adds its LDS histogram to the global one, so fewer, longer-running workgroups mean
-  // fewer global atomics per bin.  Never so few that one could count 2^32 samples into a bin of its u32 LDS histogram.
-  const u64 rows = (u64)max_group * p->n, steps = (rows + LBFT_TL_ROWS - 1) / LBFT_TL_ROWS;
-  u64 gx = LBFT_TL_WORKGROUPS / n_groups ? LBFT_TL_WORKGROUPS / n_groups : 1;
-  const u64 least = (rows * p->lcap >> 31) + 1;
-  if (gx < least) gx = least;
-  if (gx > steps) gx = steps;
+  const u64 rows = (u64)max_group * p->n;  // of the largest group; a row gives at most lcap samples
+  const u64 gx = gs_workgroups(LBFT_TL_WORKGROUPS, n_groups, (rows + LBFT_TL_ROWS - 1) / LBFT_TL_ROWS, rows * p->lcap);
   lbft_k_ct_timeline<<<dim3((u32)gx, n_groups), LBFT_TL_BLOCK, 0, stream>>>(*p, state, ctimes, grp_inst, grp_off, stalls, since_of, bin_width, bins, hist,
                                                                           stats);
   return hipGetLastError();

@@ -629,7 +629,6 @@ int lbft_batch_create(const lbft_config* cfg, const uint64_t* seeds, size_t n_in
 // ---- parameter-set batches (lbft_batch_create_param_sets) ----
 // Their kernels live in liblbft_paramsets.so (lbft_paramsets.hip), opened beside this library on first use: a code object of its own,
 // so that adding them leaves this library's machine code as it is.
-static std::mutex g_ps_mutex;
 static lbft_ps_init_fn g_ps_init = nullptr;
 static lbft_ps_run_fn g_ps_run = nullptr;
 static std::string side_lib_path(const char* name) {  // a library beside this one
@@ -642,16 +641,28 @@ static std::string side_lib_path(const char* name) {  // a library beside this o
   }
   return path;
 }
-static int load_paramsets_lib() {
-  std::lock_guard<std::mutex> lock(g_ps_mutex);
-  if (g_ps_init && g_ps_run) return LBFT_OK;
-  const std::string path = side_lib_path(LBFT_PARAMSETS_LIB);
+// Opens side library `lib` and fills every function-pointer slot, or none: `what` ("parameter sets") names the feature in the error text.
+struct SideSym { const char* name; void** slot; };
+static std::mutex g_side_mutex;
+static int load_side_lib(const char* lib, const char* what, std::initializer_list<SideSym> syms) {
+  std::lock_guard<std::mutex> lock(g_side_mutex);
+  auto loaded = [&] { return std::all_of(syms.begin(), syms.end(), [](const SideSym& y) { return *y.slot != nullptr; }); };
+  if (loaded()) return LBFT_OK;
+  const std::string path = side_lib_path(lib);
   void* h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
-  if (!h) { const char* e = dlerror(); g_err = "parameter sets need " + path + " (build it with librabft_simulator_amd.build): " + (e ? e : "not found"); return LBFT_ERR_UNSUPPORTED; }
-  g_ps_init = reinterpret_cast<lbft_ps_init_fn>(dlsym(h, "lbft_ps_launch_init"));
-  g_ps_run = reinterpret_cast<lbft_ps_run_fn>(dlsym(h, "lbft_ps_launch_run"));
-  if (!g_ps_init || !g_ps_run) { g_ps_init = nullptr; g_ps_run = nullptr; g_err = path + " lacks lbft_ps_launch_init / lbft_ps_launch_run"; return LBFT_ERR_UNSUPPORTED; }
-  return LBFT_OK;
+  if (!h) { const char* e = dlerror(); g_err = std::string(what) + " need " + path + " (build it with librabft_simulator_amd.build): " + (e ? e : "not found"); return LBFT_ERR_UNSUPPORTED; }
+  std::string names;
+  for (const SideSym& y : syms) {
+    *y.slot = dlsym(h, y.name);
+    names += (names.empty() ? "" : " / ") + std::string(y.name);
+  }
+  if (loaded()) return LBFT_OK;
+  for (const SideSym& y : syms) *y.slot = nullptr;
+  g_err = path + " lacks " + names;
+  return LBFT_ERR_UNSUPPORTED;
+}
+static int load_paramsets_lib() {
+  return load_side_lib(LBFT_PARAMSETS_LIB, "parameter sets", {{"lbft_ps_launch_init", (void**)&g_ps_init}, {"lbft_ps_launch_run", (void**)&g_ps_run}});
 }
 static int launch_init(lbft_batch* b, u32 grid_init) {
   if (b->psets.empty()) {
@@ -665,25 +676,12 @@ static int launch_init(lbft_batch* b, u32 grid_init) {
 // ---- batches that record commit times (lbft_batch_record_commit_times) ----
 // Their run kernels -- commit-time twins of lbft_k_run0 / lbft_k_run<1> and of the parameter-set kernels -- and the latency histogram
 // live in liblbft_commit_times.so (lbft_commit_times.hip), opened beside this library on first use, like liblbft_paramsets.so.
-static std::mutex g_ct_mutex;
 static lbft_ct_run_fn g_ct_run = nullptr;
 static lbft_ct_hist_fn g_ct_hist = nullptr;
 static lbft_ct_timeline_fn g_ct_timeline = nullptr;
 static int load_commit_times_lib() {
-  std::lock_guard<std::mutex> lock(g_ct_mutex);
-  if (g_ct_run && g_ct_hist && g_ct_timeline) return LBFT_OK;
-  const std::string path = side_lib_path(LBFT_COMMIT_TIMES_LIB);
-  void* h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
-  if (!h) { const char* e = dlerror(); g_err = "commit times need " + path + " (build it with librabft_simulator_amd.build): " + (e ? e : "not found"); return LBFT_ERR_UNSUPPORTED; }
-  g_ct_run = reinterpret_cast<lbft_ct_run_fn>(dlsym(h, "lbft_ct_launch_run"));
-  g_ct_hist = reinterpret_cast<lbft_ct_hist_fn>(dlsym(h, "lbft_ct_launch_histogram"));
-  g_ct_timeline = reinterpret_cast<lbft_ct_timeline_fn>(dlsym(h, "lbft_ct_launch_timeline"));
-  if (!g_ct_run || !g_ct_hist || !g_ct_timeline) {
-    g_ct_run = nullptr; g_ct_hist = nullptr; g_ct_timeline = nullptr;
-    g_err = path + " lacks lbft_ct_launch_run / lbft_ct_launch_histogram / lbft_ct_launch_timeline";
-    return LBFT_ERR_UNSUPPORTED;
-  }
-  return LBFT_OK;
+  return load_side_lib(LBFT_COMMIT_TIMES_LIB, "commit times", {{"lbft_ct_launch_run", (void**)&g_ct_run}, {"lbft_ct_launch_histogram", (void**)&g_ct_hist},
+                                                               {"lbft_ct_launch_timeline", (void**)&g_ct_timeline}});
 }
 // A run starts with every entry unrecorded (-1)
 static int fill_commit_times(lbft_batch* b) {
@@ -1434,7 +1432,6 @@ struct GroupIndex {
   size_t groups;
   std::vector<u32> off, inst;
   u32 max_group;  // instances of the largest group
-  u32 *d_inst = nullptr, *d_off = nullptr;
   explicit GroupIndex(const lbft_batch* b) : groups(b->psets.empty() ? 1 : b->psets.size()), off(groups + 1, 0), max_group((u32)b->m) {
     if (b->psets.empty()) return;
     for (u8 v : b->set_of) off[v + 1]++;
@@ -1445,44 +1442,74 @@ struct GroupIndex {
     max_group = 0;
     for (size_t g = 0; g < groups; g++) max_group = std::max(max_group, off[g + 1] - off[g]);
   }
-  GroupIndex(const GroupIndex&) = delete;
-  GroupIndex& operator=(const GroupIndex&) = delete;
-  ~GroupIndex() { hipFree(d_inst); hipFree(d_off); }
-  hipError_t upload(hipStream_t stream) {
-    if (inst.empty()) return hipSuccess;
-    hipError_t e = hipMalloc(&d_inst, inst.size() * sizeof(u32));
-    if (e == hipSuccess) e = hipMalloc(&d_off, off.size() * sizeof(u32));
-    if (e == hipSuccess) e = hipMemcpyAsync(d_inst, inst.data(), inst.size() * sizeof(u32), hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_off, off.data(), off.size() * sizeof(u32), hipMemcpyHostToDevice, stream);
-    return e;
-  }
 };
 static size_t group_count(const lbft_batch* b) { return b->psets.empty() ? 1 : b->psets.size(); }
 
+// What every statistic per group refuses before its first HIP call, in this order: a NULL argument (args_ok == false) or a zero
+// bin_width / bins, more than 2^31 bins in all, a batch without commit times where the statistic needs them, a batch that has not run.
+static int refuse_grouped(const lbft_batch* b, bool args_ok, uint32_t bin_width, uint32_t bins, bool needs_ctimes) {
+  if (!b || !args_ok || bin_width == 0 || bins == 0) { g_err = "NULL argument, or bin_width / bins of 0"; return LBFT_ERR_INVALID; }
+  if ((u64)group_count(b) * bins > (1ULL << 31)) { g_err = "groups x bins exceeds 2^31"; return LBFT_ERR_INVALID; }
+  if (needs_ctimes && !b->ctimes) { g_err = "the batch does not record commit times (lbft_batch_record_commit_times)"; return LBFT_ERR_STATE; }
+  if (!b->ran) { g_err = "run the batch first"; return LBFT_ERR_STATE; }
+  return LBFT_OK;
+}
+
+// The device side of one statistic call: the group index, uint64 output arrays (histograms, statistics) that are zeroed on the stream and
+// copied back into the caller's memory by finish(), small inputs; all freed at the end of the call.  `e` carries the first HIP error:
+// once it is set nothing more is started, and finish() reports it.
+struct GroupedCall {
+  // host, words: an output's destination and length (NULL: an input); stats: words of {samples, sum, max(~sample), max}, whose third
+  // finish() turns into the minimum
+  struct Buf { void* d; uint64_t* host; size_t words; bool stats; };
+  hipStream_t stream;
+  hipError_t e = hipSuccess;
+  std::vector<Buf> bufs;
+  const GroupIndex gi;
+  const u32 *d_inst, *d_off;  // (NULL for a plain batch)
+  explicit GroupedCall(const lbft_batch* b)
+      : stream(b->stream), gi(b), d_inst(static_cast<const u32*>(in(gi.inst.data(), gi.inst.size() * sizeof(u32)))),
+        d_off(static_cast<const u32*>(in(gi.off.data(), gi.inst.empty() ? 0 : gi.off.size() * sizeof(u32)))) {}
+  GroupedCall(const GroupedCall&) = delete;
+  GroupedCall& operator=(const GroupedCall&) = delete;
+  ~GroupedCall() { for (const Buf& f : bufs) hipFree(f.d); }
+  void* alloc(size_t bytes, uint64_t* host, size_t words, bool stats) {
+    void* d = nullptr;
+    if (e == hipSuccess) e = hipMalloc(&d, bytes);
+    if (d) bufs.push_back(Buf{d, host, words, stats});
+    return d;
+  }
+  unsigned long long* out(uint64_t* host, size_t words, bool stats = false) {  // host == NULL: no such output, NULL for the kernel
+    void* d = host ? alloc(words * sizeof(u64), host, words, stats) : nullptr;
+    if (d && e == hipSuccess) e = hipMemsetAsync(d, 0, words * sizeof(u64), stream);
+    return static_cast<unsigned long long*>(d);
+  }
+  const void* in(const void* src, size_t bytes) {  // nothing: NULL for the kernel
+    void* d = bytes ? alloc(bytes, nullptr, 0, false) : nullptr;
+    if (d && e == hipSuccess) e = hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, stream);
+    return d;
+  }
+  int finish(const char* what) {
+    for (const Buf& f : bufs)
+      if (e == hipSuccess && f.host) e = hipMemcpyAsync(f.host, f.d, f.words * sizeof(u64), hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) return hip_fail(e, what);
+    for (const Buf& f : bufs)
+      for (size_t q = 0; f.stats && q < f.words / 4; q++) f.host[q * 4 + 2] = f.host[q * 4] ? ~f.host[q * 4 + 2] : 0;  // (max(~sample) -> min)
+    return LBFT_OK;
+  }
+};
+
 // Commit-latency histogram per group (the batch's parameter sets, or one group), computed on the device (lbft_k_ct_latency_hist).
 int lbft_batch_commit_latency_histogram(const lbft_batch* b, uint32_t bin_width, uint32_t bins, uint64_t* hist, uint64_t* stats) {
-  if (!b || !hist || !stats || bin_width == 0 || bins == 0) { g_err = "NULL argument, or bin_width / bins of 0"; return LBFT_ERR_INVALID; }
+  int rc = refuse_grouped(b, hist && stats, bin_width, bins, true);
+  if (rc != LBFT_OK) return rc;
   const size_t groups = group_count(b);
-  if ((u64)groups * bins > (1ULL << 31)) { g_err = "groups x bins exceeds 2^31"; return LBFT_ERR_INVALID; }
-  if (!b->ctimes) { g_err = "the batch does not record commit times (lbft_batch_record_commit_times)"; return LBFT_ERR_STATE; }
-  if (!b->ran) { g_err = "run the batch first"; return LBFT_ERR_STATE; }
   HIP_TRY(hipSetDevice(b->device));
-  GroupIndex gi(b);
-  const size_t hist_bytes = groups * bins * sizeof(u64), stats_bytes = groups * 4 * sizeof(u64);
-  unsigned long long *d_hist = nullptr, *d_stats = nullptr;
-  hipError_t e = hipMalloc(&d_hist, hist_bytes);
-  if (e == hipSuccess) e = hipMalloc(&d_stats, stats_bytes);
-  if (e == hipSuccess) e = gi.upload(b->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(d_hist, 0, hist_bytes, b->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(d_stats, 0, stats_bytes, b->stream);
-  if (e == hipSuccess) e = g_ct_hist(&b->p, b->d_state, b->d_ctimes, gi.d_inst, gi.d_off, (u32)groups, gi.max_group, bin_width, bins, d_hist, d_stats, b->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(hist, d_hist, hist_bytes, hipMemcpyDeviceToHost, b->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(stats, d_stats, stats_bytes, hipMemcpyDeviceToHost, b->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
-  hipFree(d_hist); hipFree(d_stats);
-  if (e != hipSuccess) return hip_fail(e, "commit latency histogram");
-  for (size_t g = 0; g < groups; g++) stats[g * 4 + 2] = stats[g * 4] ? ~stats[g * 4 + 2] : 0;  // (the kernel accumulates max(~latency))
-  return LBFT_OK;
+  GroupedCall gc(b);
+  unsigned long long *d_hist = gc.out(hist, groups * bins), *d_stats = gc.out(stats, groups * 4, true);
+  if (gc.e == hipSuccess) gc.e = g_ct_hist(&b->p, b->d_state, b->d_ctimes, gc.d_inst, gc.d_off, (u32)groups, gc.gi.max_group, bin_width, bins, d_hist, d_stats, b->stream);
+  return gc.finish("commit latency histogram");
 }
 
 // Commit timelines per group, computed on the device from the commit-time rows alone (lbft_k_ct_timeline): the series (stats == NULL)
@@ -1490,9 +1517,6 @@ int lbft_batch_commit_latency_histogram(const lbft_batch* b, uint32_t bin_width,
 static int commit_timeline(const lbft_batch* b, const int64_t* since, uint32_t bin_width, uint32_t bins, uint64_t* hist, uint64_t* stats,
                            const char* what) {
   const size_t groups = group_count(b);
-  if ((u64)groups * bins > (1ULL << 31)) { g_err = "groups x bins exceeds 2^31"; return LBFT_ERR_INVALID; }
-  if (!b->ctimes) { g_err = "the batch does not record commit times (lbft_batch_record_commit_times)"; return LBFT_ERR_STATE; }
-  if (!b->ran) { g_err = "run the batch first"; return LBFT_ERR_STATE; }
   std::vector<i32> since_of;
   if (since) {
     since_of.resize(groups);
@@ -1502,82 +1526,43 @@ static int commit_timeline(const lbft_batch* b, const int64_t* since, uint32_t b
     }
   }
   HIP_TRY(hipSetDevice(b->device));
-  GroupIndex gi(b);
-  const size_t hist_bytes = groups * bins * sizeof(u64), stats_bytes = stats ? groups * LBFT_STALL_STATS * sizeof(u64) : 0;
-  unsigned long long *d_hist = nullptr, *d_stats = nullptr;
-  i32* d_since = nullptr;
-  hipError_t e = hipMalloc(&d_hist, hist_bytes);
-  if (e == hipSuccess && stats) e = hipMalloc(&d_stats, stats_bytes);
-  if (e == hipSuccess && since) e = hipMalloc(&d_since, groups * sizeof(i32));
-  if (e == hipSuccess) e = gi.upload(b->stream);
-  if (e == hipSuccess && since) e = hipMemcpyAsync(d_since, since_of.data(), groups * sizeof(i32), hipMemcpyHostToDevice, b->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(d_hist, 0, hist_bytes, b->stream);
-  if (e == hipSuccess && stats) e = hipMemsetAsync(d_stats, 0, stats_bytes, b->stream);
-  if (e == hipSuccess) e = g_ct_timeline(&b->p, b->d_state, b->d_ctimes, gi.d_inst, gi.d_off, (u32)groups, gi.max_group, stats ? 1 : 0, d_since, bin_width, bins,
-                                         d_hist, d_stats, b->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(hist, d_hist, hist_bytes, hipMemcpyDeviceToHost, b->stream);
-  if (e == hipSuccess && stats) e = hipMemcpyAsync(stats, d_stats, stats_bytes, hipMemcpyDeviceToHost, b->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
-  hipFree(d_hist); hipFree(d_stats); hipFree(d_since);
-  if (e != hipSuccess) return hip_fail(e, what);
-  for (size_t q = 0; stats && q < groups * CTL_FAMILIES; q++) stats[q * 4 + 2] = stats[q * 4] ? ~stats[q * 4 + 2] : 0;  // (max(~sample) -> min)
-  return LBFT_OK;
+  GroupedCall gc(b);
+  unsigned long long *d_hist = gc.out(hist, groups * bins), *d_stats = gc.out(stats, groups * LBFT_STALL_STATS, true);
+  const i32* d_since = static_cast<const i32*>(gc.in(since_of.data(), since_of.size() * sizeof(i32)));
+  if (gc.e == hipSuccess) gc.e = g_ct_timeline(&b->p, b->d_state, b->d_ctimes, gc.d_inst, gc.d_off, (u32)groups, gc.gi.max_group, stats ? 1 : 0, d_since, bin_width, bins,
+                                               d_hist, d_stats, b->stream);
+  return gc.finish(what);
 }
 int lbft_batch_commit_series(const lbft_batch* b, uint32_t bin_width, uint32_t bins, uint64_t* series) {
-  if (!b || !series || bin_width == 0 || bins == 0) { g_err = "NULL argument, or bin_width / bins of 0"; return LBFT_ERR_INVALID; }
-  return commit_timeline(b, nullptr, bin_width, bins, series, nullptr, "commit series");
+  int rc = refuse_grouped(b, series, bin_width, bins, true);
+  return rc != LBFT_OK ? rc : commit_timeline(b, nullptr, bin_width, bins, series, nullptr, "commit series");
 }
 int lbft_batch_commit_stalls(const lbft_batch* b, const int64_t* since, uint32_t bin_width, uint32_t bins, uint64_t* hist, uint64_t* stats) {
-  if (!b || !hist || !stats || bin_width == 0 || bins == 0) { g_err = "NULL argument, or bin_width / bins of 0"; return LBFT_ERR_INVALID; }
-  return commit_timeline(b, since, bin_width, bins, hist, stats, "commit stalls");
+  int rc = refuse_grouped(b, hist && stats, bin_width, bins, true);
+  return rc != LBFT_OK ? rc : commit_timeline(b, since, bin_width, bins, hist, stats, "commit stalls");
 }
 
 // ---- round statistics (lbft_batch_round_stats) ----
 // The kernel lives in liblbft_round_stats.so (lbft_round_stats.hip), opened beside this library on first use, like the other two side
 // libraries: a traced batch that never asks for the statistics loads nothing.
-static std::mutex g_rs_mutex;
 static lbft_rs_rounds_fn g_rs_rounds = nullptr;
-static int load_round_stats_lib() {
-  std::lock_guard<std::mutex> lock(g_rs_mutex);
-  if (g_rs_rounds) return LBFT_OK;
-  const std::string path = side_lib_path(LBFT_ROUND_STATS_LIB);
-  void* h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
-  if (!h) { const char* e = dlerror(); g_err = "round statistics need " + path + " (build it with librabft_simulator_amd.build): " + (e ? e : "not found"); return LBFT_ERR_UNSUPPORTED; }
-  g_rs_rounds = reinterpret_cast<lbft_rs_rounds_fn>(dlsym(h, "lbft_rs_launch_rounds"));
-  if (!g_rs_rounds) { g_err = path + " lacks lbft_rs_launch_rounds"; return LBFT_ERR_UNSUPPORTED; }
-  return LBFT_OK;
-}
+static int load_round_stats_lib() { return load_side_lib(LBFT_ROUND_STATS_LIB, "round statistics", {{"lbft_rs_launch_rounds", (void**)&g_rs_rounds}}); }
 
 // Round statistics per group, computed on the device from the trace rows (lbft_k_rs_rounds).  Arguments are checked before the first
 // HIP call.
 int lbft_batch_round_stats(const lbft_batch* b, uint32_t bin_width, uint32_t bins, uint64_t* stay_hist, uint64_t* skew_hist, uint64_t* stats) {
-  if (!b || !stay_hist || !skew_hist || !stats || bin_width == 0 || bins == 0) { g_err = "NULL argument, or bin_width / bins of 0"; return LBFT_ERR_INVALID; }
-  const size_t groups = group_count(b);
-  if ((u64)groups * bins > (1ULL << 31)) { g_err = "groups x bins exceeds 2^31"; return LBFT_ERR_INVALID; }
-  if (!b->ran) { g_err = "run the batch first"; return LBFT_ERR_STATE; }
-  if (b->p.rcap == 0) { g_err = "lbft_batch_enable_round_trace was not called"; return LBFT_ERR_STATE; }
-  int rc = load_round_stats_lib();
+  int rc = refuse_grouped(b, stay_hist && skew_hist && stats, bin_width, bins, false);
   if (rc != LBFT_OK) return rc;
+  if (b->p.rcap == 0) { g_err = "lbft_batch_enable_round_trace was not called"; return LBFT_ERR_STATE; }
+  rc = load_round_stats_lib();
+  if (rc != LBFT_OK) return rc;
+  const size_t groups = group_count(b);
   HIP_TRY(hipSetDevice(b->device));
-  GroupIndex gi(b);
-  const size_t hist_bytes = groups * bins * sizeof(u64), stats_bytes = groups * LBFT_ROUND_STATS * sizeof(u64);
-  unsigned long long *d_stay = nullptr, *d_skew = nullptr, *d_stats = nullptr;
-  hipError_t e = hipMalloc(&d_stay, hist_bytes);
-  if (e == hipSuccess) e = hipMalloc(&d_skew, hist_bytes);
-  if (e == hipSuccess) e = hipMalloc(&d_stats, stats_bytes);
-  if (e == hipSuccess) e = gi.upload(b->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(d_stay, 0, hist_bytes, b->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(d_skew, 0, hist_bytes, b->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(d_stats, 0, stats_bytes, b->stream);
-  if (e == hipSuccess) e = g_rs_rounds(&b->p, b->d_state, gi.d_inst, gi.d_off, (u32)groups, gi.max_group, bin_width, bins, d_stay, d_skew, d_stats, b->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(stay_hist, d_stay, hist_bytes, hipMemcpyDeviceToHost, b->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(skew_hist, d_skew, hist_bytes, hipMemcpyDeviceToHost, b->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(stats, d_stats, stats_bytes, hipMemcpyDeviceToHost, b->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
-  hipFree(d_stay); hipFree(d_skew); hipFree(d_stats);
-  if (e != hipSuccess) return hip_fail(e, "round statistics");
-  for (size_t q = 0; q < groups * RTL_FAMILIES; q++) stats[q * 4 + 2] = stats[q * 4] ? ~stats[q * 4 + 2] : 0;  // (max(~sample) -> min)
-  return LBFT_OK;
+  GroupedCall gc(b);
+  unsigned long long *d_stay = gc.out(stay_hist, groups * bins), *d_skew = gc.out(skew_hist, groups * bins);
+  unsigned long long* d_stats = gc.out(stats, groups * LBFT_ROUND_STATS, true);
+  if (gc.e == hipSuccess) gc.e = g_rs_rounds(&b->p, b->d_state, gc.d_inst, gc.d_off, (u32)groups, gc.gi.max_group, bin_width, bins, d_stay, d_skew, d_stats, b->stream);
+  return gc.finish("round statistics");
 }
 
 // Every instance's round-switch table in one call: out[(inst * cap_rounds + round) * num_nodes + node], what lbft_batch_round_switches

@@ -21,19 +21,13 @@ using namespace lbft;
 //     registers; nothing is carried.  It reads the cells a second time, from L2.
 // With tile width 1 a load instruction reads 256 contiguous bytes; with wider tiles consecutive rounds lie 4 * tw bytes apart and the
 // neighbouring instances' wavefronts read the lines' other words.
-// grid = (workgroups per group, groups); a workgroup's LBFT_RS_WAVES wavefronts stride over the instances of its group.  Samples are
-// binned into two LDS histograms with integer atomics, in passes of LBFT_RS_LDS_BINS bins; then one global atomic per non-zero bin per
-// workgroup.  The statistics stay in registers over the whole stride, are reduced in the wavefront, then in LDS, then go out once per
-// workgroup.  Instances with a non-zero fault word are skipped.  Every accumulation is an integer add / max.
+// grid = (workgroups per group, groups); a workgroup's LBFT_RS_WAVES wavefronts stride over the instances of its group and accumulate
+// by the scheme of lbft_group_stats.h: two LDS histograms, in passes of LBFT_RS_LDS_BINS bins.  Instances with a non-zero fault word are
+// skipped.
 #define LBFT_RS_BLOCK 256
 #define LBFT_RS_WAVES (LBFT_RS_BLOCK / 64)
 #define LBFT_RS_LDS_BINS 4096  // per histogram: 2 x 16 KiB of u32 counts
 #define LBFT_RS_WORKGROUPS 1024u
-
-__device__ __forceinline__ void rs_bin(u32* h, u32 v, u32 bin_width, u32 bins, u32 base, u32 span) {
-  const u32 bin = rtl_bin(v, bin_width, bins);
-  if (bin >= base && bin - base < span) atomicAdd(&h[bin - base], 1u);
-}
 
 __global__ __launch_bounds__(LBFT_RS_BLOCK) void lbft_k_rs_rounds(Params p, const u32* __restrict__ state, const u32* __restrict__ grp_inst,
                                                                   const u32* __restrict__ grp_off, u32 bin_width, u32 bins,
@@ -43,19 +37,21 @@ __global__ __launch_bounds__(LBFT_RS_BLOCK) void lbft_k_rs_rounds(Params p, cons
   __shared__ u32 h_stay[LBFT_RS_LDS_BINS], h_skew[LBFT_RS_LDS_BINS];
   __shared__ unsigned long long s_stat[LBFT_ROUND_STATS];
   const u32 g = blockIdx.y;
-  const u32 first = grp_inst ? grp_off[g] : 0u, cnt = grp_inst ? grp_off[g + 1] - first : p.m;
+  const uint2 grp = gs_group(grp_inst, grp_off, g, p.m);
+  const u32 first = grp.x, cnt = grp.y;
   if (blockIdx.x * LBFT_RS_WAVES >= cnt) return;  // (the whole workgroup: its group has fewer instances)
   const u32 wave = threadIdx.x / 64, lane = threadIdx.x % 64;
   const u32 n = p.n, rcap = p.rcap, tr = p.off_trace;
-  if (threadIdx.x < LBFT_ROUND_STATS) s_stat[threadIdx.x] = 0;
-  RtlStat st[RTL_FAMILIES] = {};
+  gs_stats_clear<LBFT_ROUND_STATS>(s_stat);
+  GsStat st[RTL_FAMILIES] = {};
   for (u32 base = 0; base < bins; base += LBFT_RS_LDS_BINS) {
     const u32 span = bins - base < LBFT_RS_LDS_BINS ? bins - base : LBFT_RS_LDS_BINS;
     const bool stat_pass = base == 0;
-    for (u32 k = threadIdx.x; k < span; k += LBFT_RS_BLOCK) { h_stay[k] = 0; h_skew[k] = 0; }
+    gs_lds_clear<LBFT_RS_BLOCK>(h_stay, span);
+    gs_lds_clear<LBFT_RS_BLOCK>(h_skew, span);
     __syncthreads();
     for (u32 k = blockIdx.x * LBFT_RS_WAVES + wave; k < cnt; k += gridDim.x * LBFT_RS_WAVES) {  // (one instance per wavefront: uniform in it)
-      const u32 i = grp_inst ? grp_inst[first + k] : k;
+      const u32 i = gs_instance(grp_inst, first, k);
       Sim s(p, const_cast<u32*>(state), i);
       if (s.ld(I_FAULT) != 0) continue;
       u32 highest = 0;
@@ -80,8 +76,8 @@ __global__ __launch_bounds__(LBFT_RS_BLOCK) void lbft_k_rs_rounds(Params p, cons
           const u32 pr = below ? c0 + pl : carry_r, pt = below ? pt_chunk : carry_t;
           u32 stay, skipped;
           if (rtl_pair(t, r, pt, pr, stay, skipped)) {
-            rs_bin(h_stay, stay, bin_width, bins, base, span);
-            if (stat_pass) { rtl_stat_add(st[RTL_STAY], stay); rtl_stat_add(st[RTL_SKIPPED], skipped); }
+            gs_lds_count(h_stay, stay, bin_width, bins, base, span);
+            if (stat_pass) { gs_stat_add(st[RTL_STAY], stay); gs_stat_add(st[RTL_SKIPPED], skipped); }
           }
           if (mask) {
             const u32 hl = 63u - (u32)__clzll((long long)mask);
@@ -97,37 +93,17 @@ __global__ __launch_bounds__(LBFT_RS_BLOCK) void lbft_k_rs_rounds(Params p, cons
           for (u32 j = 0; j < n; j++) rtl_round_add(q, s.ld(tr + j * rcap + r));
         u32 v;
         if (rtl_skew(q, r, rows, v)) {
-          rs_bin(h_skew, v, bin_width, bins, base, span);
-          if (stat_pass) rtl_stat_add(st[RTL_SKEW], v);
+          gs_lds_count(h_skew, v, bin_width, bins, base, span);
+          if (stat_pass) gs_stat_add(st[RTL_SKEW], v);
         }
-        if (stat_pass && rtl_reach(q, r, rows, v)) rtl_stat_add(st[RTL_REACH], v);
+        if (stat_pass && rtl_reach(q, r, rows, v)) gs_stat_add(st[RTL_REACH], v);
       }
     }
-    if (stat_pass) {  // wavefront, then workgroup (LDS), then one global atomic per statistic
-      for (u32 f = 0; f < RTL_FAMILIES; f++) {
-        RtlStat v = st[f];
-        for (int d = 32; d; d >>= 1) {
-          const unsigned long long oc = __shfl_xor((unsigned long long)v.cnt, d, 64), os = __shfl_xor((unsigned long long)v.sum, d, 64);
-          const unsigned long long on = __shfl_xor((unsigned long long)v.nmin, d, 64), om = __shfl_xor((unsigned long long)v.max, d, 64);
-          v.cnt += oc; v.sum += os;
-          v.nmin = on > v.nmin ? on : v.nmin;
-          v.max = om > v.max ? om : v.max;
-        }
-        if (lane == 0 && v.cnt) {
-          atomicAdd(&s_stat[f * 4 + 0], (unsigned long long)v.cnt); atomicAdd(&s_stat[f * 4 + 1], (unsigned long long)v.sum);
-          atomicMax(&s_stat[f * 4 + 2], (unsigned long long)v.nmin); atomicMax(&s_stat[f * 4 + 3], (unsigned long long)v.max);
-        }
-      }
-    }
+    if (stat_pass) gs_reduce_to_lds<RTL_FAMILIES>(st, s_stat, lane == 0);
     __syncthreads();
-    for (u32 k = threadIdx.x; k < span; k += LBFT_RS_BLOCK) {
-      if (h_stay[k]) atomicAdd(&stay_hist[(size_t)g * bins + base + k], (unsigned long long)h_stay[k]);
-      if (h_skew[k]) atomicAdd(&skew_hist[(size_t)g * bins + base + k], (unsigned long long)h_skew[k]);
-    }
-    if (stat_pass && threadIdx.x < LBFT_ROUND_STATS && s_stat[threadIdx.x & ~3u]) {
-      if ((threadIdx.x & 3u) < 2u) atomicAdd(&stats[g * LBFT_ROUND_STATS + threadIdx.x], s_stat[threadIdx.x]);
-      else atomicMax(&stats[g * LBFT_ROUND_STATS + threadIdx.x], s_stat[threadIdx.x]);
-    }
+    gs_lds_flush<LBFT_RS_BLOCK>(h_stay, stay_hist, g, bins, base, span);
+    gs_lds_flush<LBFT_RS_BLOCK>(h_skew, skew_hist, g, bins, base, span);
+    if (stat_pass) gs_stats_out<LBFT_ROUND_STATS>(s_stat, stats, g);
     __syncthreads();  // (before the next pass clears the histograms)
   }
 }
@@ -139,13 +115,8 @@ __attribute__((visibility("default"))) hipError_t lbft_rs_launch_rounds(const Pa
                                                                        unsigned long long* stay_hist, unsigned long long* skew_hist,
                                                                        unsigned long long* stats, hipStream_t stream) {
   if (bin_width == 0 || bins == 0 || n_groups == 0 || max_group == 0 || p->rcap == 0 || !stay_hist || !skew_hist || !stats) return hipErrorInvalidValue;
-  // about LBFT_RS_WORKGROUPS workgroups in all: each adds its LDS histograms to the global ones, so fewer, longer-running workgroups mean
-  // fewer global atomics per bin.  Never so few that one could count 2^32 cells into a bin of its u32 LDS histograms.
-  const u64 steps = ((u64)max_group + LBFT_RS_WAVES - 1) / LBFT_RS_WAVES;
-  u64 gx = LBFT_RS_WORKGROUPS / n_groups ? LBFT_RS_WORKGROUPS / n_groups : 1;
-  const u64 least = ((u64)max_group * p->n * p->rcap >> 31) + 1;
-  if (gx < least) gx = least;
-  if (gx > steps) gx = steps;
+  // (an instance of the largest group gives at most n x rcap cells)
+  const u64 gx = gs_workgroups(LBFT_RS_WORKGROUPS, n_groups, ((u64)max_group + LBFT_RS_WAVES - 1) / LBFT_RS_WAVES, (u64)max_group * p->n * p->rcap);
   lbft_k_rs_rounds<<<dim3((u32)gx, n_groups), LBFT_RS_BLOCK, 0, stream>>>(*p, state, grp_inst, grp_off, bin_width, bins, stay_hist, skew_hist, stats);
   return hipGetLastError();
 }

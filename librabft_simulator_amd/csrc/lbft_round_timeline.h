@@ -1,6 +1,7 @@
 // lbft_round_timeline.h -- the arithmetic of the round statistics (lbft_batch_round_stats, include/lbft.h): how the cells of one
 // instance's round-switch table turn into samples.  Compiled by the device kernel (lbft_k_rs_rounds, lbft_round_stats.hip) and by a
-// plain C++ host shim (tests/round_stats_host.cpp), so the CPU tests check the same code the GPU runs.  Needs nothing but <stdint.h>.
+// plain C++ host shim (tests/round_stats_host.cpp), so the CPU tests check the same code the GPU runs.  Needs nothing but <stdint.h> and
+// lbft_group_stats.h, which says what becomes of a sample.
 //
 // The table of an instance is T[r][j], r in [0, rows), rows = min(max_j max_round[j], trace capacity): the row of the highest round
 // reached is not part of it (data_writer.rs:74-75), although the device stores that cell too.  A cell is the GlobalTime at which node j
@@ -12,13 +13,7 @@
 
 #include <stdint.h>
 
-#ifndef LBFT_HD  // (lbft_math.h's, when that came first)
-#if defined(__HIPCC__)
-#define LBFT_HD __host__ __device__ __forceinline__
-#else
-#define LBFT_HD inline
-#endif
-#endif
+#include "lbft_group_stats.h"  // LBFT_HD; GsStat / gs_bin: what becomes of a sample
 
 #define LBFT_RTL_EMPTY 0xffffffffu  // an empty cell as the device stores it (a GlobalTime is a non-negative i32)
 #define LBFT_RTL_NO_ROUND 0xffffffffu  // "no predecessor" (a round index is below the trace capacity)
@@ -66,22 +61,7 @@ LBFT_HD bool rtl_reach(const RtlRound& q, uint32_t r, uint32_t rows, uint32_t& r
   return true;
 }
 
-// min(v / bin_width, bins - 1): the last bin also counts everything above it.  bin_width >= 1, bins >= 1.
-LBFT_HD uint32_t rtl_bin(uint32_t v, uint32_t bin_width, uint32_t bins) {
-  const uint32_t q = v / bin_width;
-  return q < bins - 1u ? q : bins - 1u;
-}
-
-// One sample family's statistics as they are accumulated: samples, sum, max(~value) (the minimum's complement: zero-initialised and
-// combined by max like the others) and max.  LBFT_ROUND_STATS = 4 families x these 4.
-struct RtlStat {
-  uint64_t cnt, sum, nmin, max;
-};
-LBFT_HD void rtl_stat_add(RtlStat& s, uint32_t v) {
-  s.cnt++; s.sum += v;
-  s.nmin = ~(uint64_t)v > s.nmin ? ~(uint64_t)v : s.nmin;
-  s.max = v > s.max ? v : s.max;
-}
+// The sample families.  LBFT_ROUND_STATS = these 4 x GsStat's 4 words.
 enum { RTL_STAY = 0, RTL_SKIPPED = 1, RTL_SKEW = 2, RTL_REACH = 3, RTL_FAMILIES = 4 };
 
 #endif  // LBFT_ROUND_TIMELINE_H

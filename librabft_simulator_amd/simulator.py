@@ -164,6 +164,16 @@ def histogram_quantile(hist, width, q):
     return int(np.searchsorted(cdf, target, side="left")) * int(width)
 
 
+def _families(stats, families):
+    """One group's device statistics -- (samples, sum, min, max) per family, in the order of ``families`` = ((name, count_key), ...) -- as
+    ``{name: {count_key, mean, min, max}}``, ``None`` where a family has no samples."""
+    out = {}
+    for f, (name, count_key) in enumerate(families):
+        n, total, lo, hi = (int(v) for v in stats[4 * f:4 * f + 4])
+        out[name] = {count_key: n, "mean": total / n if n else None, "min": lo if n else None, "max": hi if n else None}
+    return out
+
+
 class BatchResult:
     """Results of ``BatchSimulator.loop_until`` (lazy device read-back through the C ABI)."""
 
@@ -325,10 +335,7 @@ class BatchResult:
         stay, skew, stats = self.round_histogram()
         out = []
         for g in range(stay.shape[0]):
-            row = {"set": g}
-            for f, name in enumerate(("stay", "skipped", "skew", "reach")):
-                n, total, lo, hi = (int(v) for v in stats[g, 4 * f:4 * f + 4])
-                row[name] = {"samples": n, "mean": total / n if n else None, "min": lo if n else None, "max": hi if n else None}
+            row = {"set": g, **_families(stats[g], (("stay", "samples"), ("skipped", "samples"), ("skew", "samples"), ("reach", "samples")))}
             row["stay"]["quantiles"] = {str(q): histogram_quantile(stay[g], width, q) for q in quantiles}
             row["skew"]["quantiles"] = {str(q): histogram_quantile(skew[g], width, q) for q in quantiles}
             out.append(row)
@@ -385,14 +392,11 @@ class BatchResult:
         ``min``, ``max`` and ``quantiles`` ({str(q): latency}), from the device histogram with its default (exact) binning.  Quantiles use
         the inverted-CDF rule -- the smallest L with count(<= L) >= ceil(q * samples), numpy's ``method="inverted_cdf"`` -- and are exact
         with bins of width 1; ``None`` without samples."""
-        span = int(self._sim._max_clock) + 1
-        width = max(1, -(-span // (1 << 16)))
+        width, _ = self._binning(None, None)
         hist, stats = self.latency_histogram()
         out = []
         for g in range(hist.shape[0]):
-            n = int(stats[g, 0])
-            row = {"set": g, "samples": n, "mean": float(stats[g, 1]) / n if n else None, "min": int(stats[g, 2]) if n else None,
-                   "max": int(stats[g, 3]) if n else None}
+            row = {"set": g, **_families(stats[g], (("latency", "samples"),))["latency"]}
             row["quantiles"] = {str(q): histogram_quantile(hist[g], width, q) for q in quantiles}
             out.append(row)
         return out
@@ -467,10 +471,8 @@ class BatchResult:
         hist, stats = self.stall_histogram(since)
         out = []
         for g in range(hist.shape[0]):
-            row = {"set": g, "since": int(since[g]) if since is not None else 0}
-            for f, (name, count) in enumerate((("gaps", "samples"), ("first", "nodes"), ("tail", "nodes"), ("longest", "nodes"))):
-                n, total, lo, hi = (int(v) for v in stats[g, 4 * f:4 * f + 4])
-                row[name] = {count: n, "mean": total / n if n else None, "min": lo if n else None, "max": hi if n else None}
+            row = {"set": g, "since": int(since[g]) if since is not None else 0,
+                   **_families(stats[g], (("gaps", "samples"), ("first", "nodes"), ("tail", "nodes"), ("longest", "nodes")))}
             row["gaps"]["quantiles"] = {str(q): histogram_quantile(hist[g], width, q) for q in quantiles}
             out.append(row)
         return out

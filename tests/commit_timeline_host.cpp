@@ -13,7 +13,7 @@ extern "C" int ctl_host(const int64_t* ct, const uint32_t* counts, const uint32_
                         uint32_t cap, uint32_t groups, const int64_t* since, int64_t max_clock, uint32_t width, uint32_t bins, uint32_t seg,
                         uint64_t* series, uint64_t* hist, uint64_t* stats) {
   if (!width || !bins || !seg || !groups) return -1;
-  std::vector<CtlStat> st((size_t)groups * CTL_FAMILIES, CtlStat{0, 0, 0, 0});
+  std::vector<GsStat> st((size_t)groups * CTL_FAMILIES, GsStat{0, 0, 0, 0});
   std::vector<CtlRow> lane(seg);
   std::vector<int32_t> c(seg);
   for (uint32_t i = 0; i < m; i++) {
@@ -29,20 +29,20 @@ extern "C" int ctl_host(const int64_t* ct, const uint32_t* counts, const uint32_
       for (uint32_t c0 = 0; c0 < nc; c0 += seg) {
         for (uint32_t l = 0; l < seg; l++) c[l] = c0 + l < nc ? (int32_t)row[c0 + l] : -1;
         for (uint32_t l = 0; l < seg; l++) {
-          if (c[l] >= 0) series[(size_t)g * bins + ctl_bin((uint32_t)c[l], width, bins)]++;
+          if (c[l] >= 0) series[(size_t)g * bins + gs_bin((uint32_t)c[l], width, bins)]++;
           const uint32_t gap = ctl_entry(lane[l], c[l], l ? c[l - 1] : carry, s);
           if (gap) {
-            hist[(size_t)g * bins + ctl_bin(gap, width, bins)]++;
-            ctl_stat_add(st[g * CTL_FAMILIES + CTL_GAPS], gap);
+            hist[(size_t)g * bins + gs_bin(gap, width, bins)]++;
+            gs_stat_add(st[g * CTL_FAMILIES + CTL_GAPS], gap);
           }
         }
         carry = c[seg - 1];
       }
       CtlRow r = lane[seg - 1];  // (merged in another order than the walk: the order must not matter)
       for (uint32_t l = 0; l + 1 < seg; l++) r = ctl_merge(lane[l], r);
-      if (r.first != LBFT_CTL_NONE) ctl_stat_add(st[g * CTL_FAMILIES + CTL_FIRST], r.first);
-      ctl_stat_add(st[g * CTL_FAMILIES + CTL_TAIL], ctl_tail(r, (int32_t)max_clock));
-      ctl_stat_add(st[g * CTL_FAMILIES + CTL_LONGEST], ctl_longest(r, (int32_t)max_clock));
+      if (r.first != LBFT_CTL_NONE) gs_stat_add(st[g * CTL_FAMILIES + CTL_FIRST], r.first);
+      gs_stat_add(st[g * CTL_FAMILIES + CTL_TAIL], ctl_tail(r, (int32_t)max_clock));
+      gs_stat_add(st[g * CTL_FAMILIES + CTL_LONGEST], ctl_longest(r, (int32_t)max_clock));
     }
   }
   for (size_t q = 0; q < st.size(); q++) {

@@ -14,7 +14,7 @@ extern "C" int rtl_host(const uint32_t* first_time, const uint32_t* max_round, c
                         uint32_t n, uint32_t rcap, uint32_t groups, uint32_t width, uint32_t bins, uint32_t chunk, uint64_t* stay_hist,
                         uint64_t* skew_hist, uint64_t* stats) {
   if (!width || !bins || !chunk || !groups || !rcap) return -1;
-  std::vector<RtlStat> st((size_t)groups * RTL_FAMILIES, RtlStat{0, 0, 0, 0});
+  std::vector<GsStat> st((size_t)groups * RTL_FAMILIES, GsStat{0, 0, 0, 0});
   std::vector<uint32_t> t(chunk);
   for (uint32_t i = 0; i < m; i++) {
     if (faults[i]) continue;
@@ -34,9 +34,9 @@ extern "C" int rtl_host(const uint32_t* first_time, const uint32_t* max_round, c
             if (!rtl_empty(t[b])) { pr = c0 + b; pt = t[b]; break; }
           uint32_t stay, skipped;
           if (rtl_pair(t[l], c0 + l, pt, pr, stay, skipped)) {
-            stay_hist[(size_t)g * bins + rtl_bin(stay, width, bins)]++;
-            rtl_stat_add(st[g * RTL_FAMILIES + RTL_STAY], stay);
-            rtl_stat_add(st[g * RTL_FAMILIES + RTL_SKIPPED], skipped);
+            stay_hist[(size_t)g * bins + gs_bin(stay, width, bins)]++;
+            gs_stat_add(st[g * RTL_FAMILIES + RTL_STAY], stay);
+            gs_stat_add(st[g * RTL_FAMILIES + RTL_SKIPPED], skipped);
           }
         }
         for (uint32_t l = chunk; l-- > 0;)
@@ -49,10 +49,10 @@ extern "C" int rtl_host(const uint32_t* first_time, const uint32_t* max_round, c
       for (uint32_t j = 0; j < n; j++) rtl_round_add(q, table[(size_t)j * rcap + r]);
       uint32_t v;
       if (rtl_skew(q, r, rows, v)) {
-        skew_hist[(size_t)g * bins + rtl_bin(v, width, bins)]++;
-        rtl_stat_add(st[g * RTL_FAMILIES + RTL_SKEW], v);
+        skew_hist[(size_t)g * bins + gs_bin(v, width, bins)]++;
+        gs_stat_add(st[g * RTL_FAMILIES + RTL_SKEW], v);
       }
-      if (rtl_reach(q, r, rows, v)) rtl_stat_add(st[g * RTL_FAMILIES + RTL_REACH], v);
+      if (rtl_reach(q, r, rows, v)) gs_stat_add(st[g * RTL_FAMILIES + RTL_REACH], v);
     }
   }
   for (size_t q = 0; q < st.size(); q++) {
@@ -61,3 +61,6 @@ extern "C" int rtl_host(const uint32_t* first_time, const uint32_t* max_round, c
   }
   return 0;
 }
+
+// The grid rule of the statistic kernels' launchers (lbft_group_stats.h), as it is.
+extern "C" uint64_t gs_workgroups_host(uint64_t target, uint64_t groups, uint64_t steps, uint64_t samples) { return gs_workgroups(target, groups, steps, samples); }

@@ -73,7 +73,7 @@ def test_fails_loudly_without_gpu(hiplib):
 
 
 def _kernel_metadata(so_path):
-    """name -> {private_segment_fixed_size, vgpr_count, vgpr_spill_count} of every gfx950 kernel in the library
+    """name -> {private_segment_fixed_size, group_segment_fixed_size, vgpr_count, vgpr_spill_count, sgpr_count} of every gfx950 kernel in the library
     (the code object is unbundled from .hip_fatbin and its AMDGPU metadata note read with llvm-readelf)."""
     import struct
     import subprocess
@@ -101,7 +101,7 @@ def _kernel_metadata(so_path):
     for chunk in notes.split("  - .agpr_count:")[1:]:
         name = re.search(r"\.name:\s+(\S+)", chunk).group(1)
         kernels[name] = {k: int(re.search(r"\.%s:\s+(\d+)" % k, chunk).group(1))
-                         for k in ("private_segment_fixed_size", "vgpr_count", "vgpr_spill_count", "sgpr_count")}
+                         for k in ("private_segment_fixed_size", "group_segment_fixed_size", "vgpr_count", "vgpr_spill_count", "sgpr_count")}
     return kernels
 
 

@@ -28,6 +28,8 @@ def shim(tmp_path_factory):
     vp = C.c_void_p
     L.rtl_host.argtypes = [vp, vp, vp, vp] + [C.c_uint32] * 7 + [vp, vp, vp]
     L.rtl_host.restype = C.c_int
+    L.gs_workgroups_host.argtypes = [C.c_uint64] * 4
+    L.gs_workgroups_host.restype = C.c_uint64
     return L
 
 
@@ -172,6 +174,54 @@ def test_shim_equals_the_numpy_reference_on_drawn_traces(shim):
         cleared[i, :, int(max_rounds[i])] = NONE
     assert all((a == b).all() for a, b in zip(run_shim(shim, ft, mr, faults, group_of, groups, 3, 50, 64),
                                               run_shim(shim, cleared, mr, faults, group_of, groups, 3, 50, 64)))
+
+
+def test_grid_rule_equals_the_two_launchers_formulas(shim):
+    """gs_workgroups (lbft_group_stats.h), called the way lbft_ct_launch_timeline and lbft_rs_launch_rounds call it, gives the workgroups
+    per group that each launcher used to compute for itself (written out below): about 1024 workgroups in all, at least one more than
+    the largest group's samples >> 31 (no u32 LDS bin can wrap), at most one per step of a workgroup's stride."""
+    target, tl_rows, rs_waves = 1024, 8, 4  # LBFT_TL_WORKGROUPS = LBFT_RS_WORKGROUPS, LBFT_TL_ROWS, LBFT_RS_WAVES
+    csrc = os.path.join(ROOT, "librabft_simulator_amd", "csrc")
+    ct_src, rs_src = (open(os.path.join(csrc, f)).read() for f in ("lbft_commit_times.hip", "lbft_round_stats.hip"))
+    assert "#define LBFT_TL_WORKGROUPS 1024u" in ct_src and "#define LBFT_TL_BLOCK 256" in ct_src and "#define LBFT_TL_SEG 32" in ct_src
+    assert "#define LBFT_RS_WORKGROUPS 1024u" in rs_src and "#define LBFT_RS_BLOCK 256" in rs_src
+
+    def timeline_was(n_groups, max_group, n, lcap):
+        rows = max_group * n
+        steps = (rows + tl_rows - 1) // tl_rows
+        gx = target // n_groups if target // n_groups else 1
+        least = (rows * lcap >> 31) + 1
+        gx = max(gx, least)
+        return min(gx, steps)
+
+    def rounds_was(n_groups, max_group, n, rcap):
+        steps = (max_group + rs_waves - 1) // rs_waves
+        gx = target // n_groups if target // n_groups else 1
+        least = (max_group * n * rcap >> 31) + 1
+        gx = max(gx, least)
+        return min(gx, steps)
+
+    table = [  # (n_groups, max_group, n, lcap or rcap)
+        (1, 65536, 4, 64),           # one group: the target binds (1024)
+        (256, 1024, 4, 64),          # 256 groups: 4 workgroups each
+        (256, 1, 4, 64), (1, 1, 1, 1), (7, 1, 32, 4096),  # a largest group of one instance: one step
+        (1, 3, 4, 16), (1, 37, 3, 100), (64, 9, 2, 8),    # fewer steps than the target: the cap binds
+        (256, 1 << 20, 32, 4096),    # 2^37 samples: the floor of 65 binds over 1024 / 256 = 4
+        (1, 1 << 26, 32, 65534),     # ... and over the target itself (65 535 > 1024)
+        (1000, 1 << 22, 16, 2048),   # 1024 / 1000 = 1, floor 65
+        (2048, 5000, 4, 64),         # more groups than the target: 1
+    ]
+    seen = set()
+    for n_groups, max_group, n, cap in table:
+        rows = max_group * n
+        got_tl = shim.gs_workgroups_host(target, n_groups, (rows + tl_rows - 1) // tl_rows, rows * cap)
+        got_rs = shim.gs_workgroups_host(target, n_groups, (max_group + rs_waves - 1) // rs_waves, max_group * n * cap)
+        assert got_tl == timeline_was(n_groups, max_group, n, cap), (n_groups, max_group, n, cap, got_tl)
+        assert got_rs == rounds_was(n_groups, max_group, n, cap), (n_groups, max_group, n, cap, got_rs)
+        for gx, steps in ((got_tl, (rows + tl_rows - 1) // tl_rows), (got_rs, (max_group + rs_waves - 1) // rs_waves)):
+            floor = (rows * cap >> 31) + 1
+            seen.add("steps" if gx == steps else "floor" if gx == floor and floor > max(target // n_groups, 1) else "target")
+    assert seen == {"steps", "floor", "target"}, seen
 
 
 def test_oracle_tables_of_a_partitioned_network(shim, oracle):
