@@ -14,17 +14,17 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc", "lbft_hip.hip")
 DEPS = [SRC] + [os.path.join(HERE, "csrc", f) for f in ("lbft_core.h", "lbft_math.h", "lbft_tables.h", "lbft_save_node.h", "lbft_launch.h", "lbft_plan.h",
                                                          "lbft_paramsets.h", "lbft_commit_times.h", "lbft_commit_timeline.h", "lbft_round_stats.h",
-                                                         "lbft_round_timeline.h", "lbft_group_stats.h", "lbft_node_ops.h")] + [
+                                                         "lbft_round_timeline.h", "lbft_group_stats.h", "lbft_node_ops.h", "lbft_run_body.h")] + [
     os.path.join(HERE, "..", "include", "lbft.h")]
 OUT = os.path.join(HERE, "liblbft_hip.so")
 PS_SRC = os.path.join(HERE, "csrc", "lbft_paramsets.hip")
 PS_DEPS = [PS_SRC] + [os.path.join(HERE, "csrc", f) for f in ("lbft_core.h", "lbft_math.h", "lbft_launch.h", "lbft_paramsets.h",
-                                                               "lbft_lane_run.h")] + [
+                                                               "lbft_run_body.h")] + [
     os.path.join(HERE, "..", "include", "lbft.h")]
 PS_OUT = os.path.join(HERE, "liblbft_paramsets.so")
 CT_SRC = os.path.join(HERE, "csrc", "lbft_commit_times.hip")
 CT_DEPS = [CT_SRC] + [os.path.join(HERE, "csrc", f) for f in ("lbft_core.h", "lbft_math.h", "lbft_launch.h", "lbft_commit_times.h",
-                                                               "lbft_commit_timeline.h", "lbft_group_stats.h", "lbft_lane_run.h")] + [
+                                                               "lbft_commit_timeline.h", "lbft_group_stats.h", "lbft_run_body.h")] + [
     os.path.join(HERE, "..", "include", "lbft.h")]
 CT_OUT = os.path.join(HERE, "liblbft_commit_times.so")
 RS_SRC = os.path.join(HERE, "csrc", "lbft_round_stats.hip")

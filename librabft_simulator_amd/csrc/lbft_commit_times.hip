@@ -2,7 +2,7 @@
 //
 // The run kernels are the commit-time twins of the lane-private run kernels: lbft_core.h's step instantiated for K_SMALL / K_MID (and
 // their K_PARAM_SETS forms) with K_COMMIT_TIMES added, where commit_block also stores the clock of every commit into the batch's
-// commit-time buffer ([instance][node][lcap] i32, the log's index).  Their run body (lbft_lane_run.h) and LDS layout (lbft_launch.h) are
+// commit-time buffer ([instance][node][lcap] i32, the log's index).  Their run body (lbft_run_body.h) and LDS layout (lbft_launch.h) are
 // those of lbft_k_run0 / lbft_k_run<1> and the parameter-set kernels, so the host side of liblbft_hip.so sizes them as those.
 // The histogram kernel turns a finished run's logs and commit times into commit-latency histograms per group (parameter set); the
 // timeline kernel turns the commit times alone into commits over time and the statistics of the commit-free intervals.
@@ -18,27 +18,29 @@
 using namespace lbft;
 
 #include "lbft_launch.h"
-#include "lbft_lane_run.h"  // ps_run_body
+#include "lbft_run_body.h"  // run_body
+static_assert(run_lane_private<K_SMALL_TIMED> && run_lane_private<K_MID_TIMED> && run_lane_private<K_SMALL_SETS_TIMED> && run_lane_private<K_MID_SETS_TIMED>,
+              "lane-private classes only");
 
 // Small class (lbft_k_run0's geometry: two wavefronts per SIMD) and mid class (lbft_k_run<1>'s: one wavefront per SIMD, the whole register
 // file), each plain and with parameter sets.
 __global__ __launch_bounds__(LBFT_RUN_BLOCK) __attribute__((amdgpu_waves_per_eu(LBFT_RUN_WAVES_PER_SIMD, LBFT_RUN_WAVES_PER_SIMD)))
 void lbft_k_ct_run0(Params p, u32* __restrict__ state, u32* __restrict__ unfinished, i32* __restrict__ ctimes) {
-  ps_run_body<K_SMALL_TIMED>(p, state, unfinished, nullptr, nullptr, ctimes);
+  run_body<K_SMALL_TIMED>(p, state, unfinished, nullptr, nullptr, ctimes);
 }
 __global__ __launch_bounds__(64 * LBFT_RUN_WAVES_FULL)
 void lbft_k_ct_run1(Params p, u32* __restrict__ state, u32* __restrict__ unfinished, i32* __restrict__ ctimes) {
-  ps_run_body<K_MID_TIMED>(p, state, unfinished, nullptr, nullptr, ctimes);
+  run_body<K_MID_TIMED>(p, state, unfinished, nullptr, nullptr, ctimes);
 }
 __global__ __launch_bounds__(LBFT_RUN_BLOCK) __attribute__((amdgpu_waves_per_eu(LBFT_RUN_WAVES_PER_SIMD, LBFT_RUN_WAVES_PER_SIMD)))
 void lbft_k_ct_ps_run0(Params p, u32* __restrict__ state, u32* __restrict__ unfinished, const ParamSetDev* __restrict__ sets, const u8* __restrict__ set_of,
                        i32* __restrict__ ctimes) {
-  ps_run_body<K_SMALL_SETS_TIMED>(p, state, unfinished, sets, set_of, ctimes);
+  run_body<K_SMALL_SETS_TIMED>(p, state, unfinished, sets, set_of, ctimes);
 }
 __global__ __launch_bounds__(64 * LBFT_RUN_WAVES_FULL)
 void lbft_k_ct_ps_run1(Params p, u32* __restrict__ state, u32* __restrict__ unfinished, const ParamSetDev* __restrict__ sets, const u8* __restrict__ set_of,
                        i32* __restrict__ ctimes) {
-  ps_run_body<K_MID_SETS_TIMED>(p, state, unfinished, sets, set_of, ctimes);
+  run_body<K_MID_SETS_TIMED>(p, state, unfinished, sets, set_of, ctimes);
 }
 
 // Commit-latency histogram: grid = (lanes of the largest group / LBFT_HIST_BLOCK, groups); one lane per (instance, node) of the
@@ -197,15 +199,10 @@ __attribute__((visibility("default"))) hipError_t lbft_ct_launch_run(int cls, co
                                                                     const u8* set_of, i32* ctimes, u32 grid, u32 block, size_t lds_bytes,
                                                                     hipStream_t stream) {
   if (cls != K_SMALL && cls != K_MID) return hipErrorInvalidValue;
-  const void* fn = sets ? (cls == K_SMALL ? reinterpret_cast<const void*>(lbft_k_ct_ps_run0) : reinterpret_cast<const void*>(lbft_k_ct_ps_run1))
-                        : (cls == K_SMALL ? reinterpret_cast<const void*>(lbft_k_ct_run0) : reinterpret_cast<const void*>(lbft_k_ct_run1));
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-  if (e != hipSuccess) return e;
-  if (sets && cls == K_SMALL) lbft_k_ct_ps_run0<<<grid, block, lds_bytes, stream>>>(*p, state, unfinished, sets, set_of, ctimes);
-  else if (sets) lbft_k_ct_ps_run1<<<grid, block, lds_bytes, stream>>>(*p, state, unfinished, sets, set_of, ctimes);
-  else if (cls == K_SMALL) lbft_k_ct_run0<<<grid, block, lds_bytes, stream>>>(*p, state, unfinished, ctimes);
-  else lbft_k_ct_run1<<<grid, block, lds_bytes, stream>>>(*p, state, unfinished, ctimes);
-  return hipGetLastError();
+  if (sets)
+    return launch_run_kernel(cls == K_SMALL ? lbft_k_ct_ps_run0 : lbft_k_ct_ps_run1, grid, block, lds_bytes, stream, *p, state, unfinished, sets, set_of,
+                             ctimes);
+  return launch_run_kernel(cls == K_SMALL ? lbft_k_ct_run0 : lbft_k_ct_run1, grid, block, lds_bytes, stream, *p, state, unfinished, ctimes);
 }
 
 __attribute__((visibility("default"))) hipError_t lbft_ct_launch_histogram(const Params* p, const u32* state, const i32* ctimes, const u32* grp_inst,

@@ -46,217 +46,8 @@ __global__ __launch_bounds__(LBFT_BLOCK) void lbft_k_init(Params p, u32* __restr
   s.init(seeds[i]);
 }
 
-template <int CLS>
-__device__ __forceinline__ void run_body(const Params& p, u32* __restrict__ state, u32* __restrict__ unfinished) {
-  extern __shared__ u64 lds[];
-  const u32 nwaves = blockDim.x >> 6;  // wavefronts per workgroup: 8 for the two-wavefronts-per-SIMD kernels, 4 for the full-register ones
-  u64* t_zx = lds;
-  u64* t_zf = lds + 257;
-  u64* t_et = lds + 514;
-  for (u32 t = threadIdx.x; t < 257; t += blockDim.x) { t_zx[t] = p.zig_x[t]; t_zf[t] = p.zig_f[t]; }
-  for (u32 t = threadIdx.x; t < 256; t += blockDim.x) t_et[t] = p.exp_tab[t];
-  i64* t_dur = reinterpret_cast<i64*>(lds + 770);
-  u8* t_leader = reinterpret_cast<u8*>(lds + 770 + LBFT_LDS_DURS);
-  u32 n_dur = p.dur_len < LBFT_LDS_DURS ? p.dur_len : LBFT_LDS_DURS;
-  u32 n_leader = p.leader_len < LBFT_LDS_LEADERS ? p.leader_len : LBFT_LDS_LEADERS;
-  for (u32 t = threadIdx.x; t < n_dur; t += blockDim.x) t_dur[t] = p.dur_tab[t];
-  for (u32 t = threadIdx.x; t < n_leader; t += blockDim.x) t_leader[t] = p.leader_tab[t];
-  u32* t_weights = reinterpret_cast<u32*>(lds + 770 + LBFT_LDS_DURS + LBFT_LDS_LEADERS / 8);
-  for (u32 t = threadIdx.x; t < p.n; t += blockDim.x) t_weights[t] = p.weights[t];
-  __syncthreads();
-  u32 wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const u32 qslots = p.ql;  // u64 words per instance in the key area
-  const u32 qcols = SimT<CLS>::QS32 ? 32u : p.lpw;  // queue columns per wavefront (lbft_k_run0q: always 32, see LBFT_QUAD_STRIDE32)
-  u64* keys = lds + LBFT_TABLE_U64 + (size_t)wave * p.ql * qcols + lane;
-  u32* metas = reinterpret_cast<u32*>(lds + LBFT_TABLE_U64 + (size_t)nwaves * qslots * qcols) + (size_t)wave * p.ql * qcols + lane;  // (CLS 0: unused, not allocated)
-  const u32 meta_words = SimT<CLS>::C0 ? 0u : nwaves * p.ql * p.lpw;
-  // Only the first p.lpw lanes of a wavefront carry an instance (occupancy vs lane-utilisation knob).
-  u32 i = (blockIdx.x * nwaves + wave) * p.lpw + lane;
-  bool active = lane < p.lpw && i < p.m;
-  bool done = true;
-  // lpw divides 64, so a wavefront's instances share one tile: its base is wavefront-uniform (SGPRs) and
-  // every row access is saddr + 32-bit voffset
-  // (tile width tw: 64 for the small-network classes -- two 32-lane wavefronts share a tile --, otherwise tw == lpw: one tile per wavefront)
-  const u32 tw = SimT<CLS>::TILE64 ? 64u : SimT<CLS>::IMAJOR ? 1u : p.tw;
-  u32 tile_idx = __builtin_amdgcn_readfirstlane(((blockIdx.x * nwaves + wave) * p.lpw) / tw);
-  char* tile = reinterpret_cast<char*>(state) + (size_t)tile_idx * p.total_words * ((size_t)4 * tw);
-  if constexpr (SimT<CLS>::COOP) {
-    // Large networks: EVERY lane of the wavefront runs the event loop; the first lpw lanes carry a network each, all 64
-    // cooperate on the bulk sends of those networks (SimT::run_coop / coop_bulk).
-    // (tw may be narrower than the lanes that carry a network: lane j's instance then sits j / tw tiles behind the wavefront's
-    // first tile -- folded into the lane's 32-bit column offset, the tile base stays wavefront-uniform)
-    const u32 li = active ? (i - ((blockIdx.x * nwaves + wave) * p.lpw)) : (lane & (p.lpw - 1u));
-    SimT<CLS> s(p, tile, (li / tw) * (p.total_words * 4u * tw) + (li & (tw - 1u)) * 4u, 0);
-    bool lead = false;
-    if (active) lead = s.ld(I_DONE) == 0;
-    s.attach_queue(keys, metas, p.lpw, p.ql);
-    s.attach_tables(t_zx, t_zf, t_et);
-    s.attach_round_tables(t_leader, n_leader, t_dur, n_dur);
-    s.attach_weights(t_weights);
-    {  // [receiver lists: nwaves * lpw * LBFT_MAX_NODES bytes][block-record windows: lane-private columns per wavefront]
-      u8* lists = reinterpret_cast<u8*>(lds) + run_lds_bytes_dev(p.ql, p.lpw, 12u, nwaves);
-      u32* win = reinterpret_cast<u32*>(lists + (size_t)nwaves * p.lpw * LBFT_MAX_NODES) + (size_t)wave * p.lpw * p.blw * (1u + BC_WORDS);
-      u32 wsh = 0;
-      while ((1u << wsh) < p.lpw) wsh++;
-      s.attach_blk_window(win + (lane & (p.lpw - 1u)), p.blw, wsh);
-      if (lane < p.lpw) s.blw_reset();
-    }
-    if (lead) {
-      u8* lists = reinterpret_cast<u8*>(lds) + run_lds_bytes_dev(p.ql, p.lpw, 12u, nwaves);
-      s.attach_peer_list(lists + ((size_t)wave * p.lpw + lane) * LBFT_MAX_NODES);
-      s.load_scalars();
-      s.queue_to_lds();
-    }
-#if defined(LBFT_PHASE_TIMERS)
-    u64* wprof = reinterpret_cast<u64*>(reinterpret_cast<u32*>(lds + LBFT_TABLE_U64 + (size_t)nwaves * qslots * qcols) +
-                                        (size_t)meta_words + (meta_words & 1u)) + wave * LBFT_NPHASES;
-    if (lane == 0) { for (int k = 0; k < LBFT_NPHASES; k++) wprof[k] = 0; wprof[31] = __builtin_readcyclecounter(); }
-    s.wprof = wprof;
-    u64 t_begin = __builtin_readcyclecounter();
-#endif
-    bool drained = s.run_coop(lead);
-    if (lead) {
-      done = drained;
-      s.queue_from_lds();
-      s.store_scalars(done);
-    }
-#if defined(LBFT_PHASE_TIMERS)
-    if (p.prof && lane == 0) {
-      for (int k = 0; k < 31; k++) atomicAdd(&p.prof[k], (unsigned long long)s.wprof[k]);
-      atomicAdd(&p.prof[31], (unsigned long long)(__builtin_readcyclecounter() - t_begin));
-    }
-#endif
-  } else if constexpr (SimT<CLS>::WUNI) {
-    // ONE network per wavefront as wavefront-uniform code (SimT<K_SMALL_UNIFORM>, lbft_k_run0u; p.lpw == 1): nothing below depends on the lane -- the
-    // network's index, rows and LDS columns come from the wavefront's index through readfirstlane -- so all 64 lanes run the event loop
-    // with the same values and the compiler keeps the protocol logic on the scalar unit (lbft_core.h, SimT::WUNI); only the pop's scan
-    // (coop_find) reads per-lane slots.  Stores / LDS writes: the same address and value in every lane.
-    const u32 uwave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const u32 ui = __builtin_amdgcn_readfirstlane(blockIdx.x * nwaves + uwave);  // (p.lpw == 1: the wavefront's network)
-    u64* ukeys = lds + LBFT_TABLE_U64 + (size_t)uwave * p.ql;
-    SimT<CLS> s(p, tile, 0u, 0);
-    bool lead = false;
-    if (ui < p.m) lead = s.ld(I_DONE) == 0;
-    s.attach_queue(ukeys, nullptr, 1u, p.ql);
-    s.attach_tables(t_zx, t_zf, t_et);
-    s.attach_round_tables(t_leader, n_leader, t_dur, n_dur);
-    s.attach_weights(t_weights);
-    if (p.n <= 4) {  // the nodes' hcbr buffers
-      u32* hcb = reinterpret_cast<u32*>(reinterpret_cast<u8*>(lds) + run_lds_bytes_dev(p.ql, 1u, 8u, nwaves));
-      s.attach_hcbr(hcb + (size_t)uwave * LBFT_LDS_HCBR_WORDS);
-    }
-    s.qlen = 0;
-    if (lead) {
-      s.load_scalars();
-      s.queue_to_lds();
-      s.hcbr_to_lds();
-    }
-#if defined(LBFT_PHASE_TIMERS)
-    u64* wprof = reinterpret_cast<u64*>(reinterpret_cast<u32*>(lds + LBFT_TABLE_U64 + (size_t)nwaves * qslots * qcols) +
-                                        (size_t)meta_words + (meta_words & 1u)) + uwave * LBFT_NPHASES;
-    if (lane == 0) { for (int k = 0; k < LBFT_NPHASES; k++) wprof[k] = 0; wprof[31] = __builtin_readcyclecounter(); }
-    s.wprof = wprof;
-    u64 t_begin = __builtin_readcyclecounter();
-#endif
-    bool drained = s.run_popc(lead, ukeys);
-    if (lead) {
-      done = drained;
-      s.queue_from_lds();
-      s.hcbr_from_lds();
-      s.store_scalars(done);
-    }
-#if defined(LBFT_PHASE_TIMERS)
-    if (p.prof && lane == 0) {
-      for (int k = 0; k < 31; k++) atomicAdd(&p.prof[k], (unsigned long long)s.wprof[k]);
-      atomicAdd(&p.prof[31], (unsigned long long)(__builtin_readcyclecounter() - t_begin));
-    }
-#endif
-    active = lane == 0 && ui < p.m;  // (one report per wavefront below)
-  } else if constexpr (SimT<CLS>::POPC) {
-    // Class 0 with the wavefront-wide pop (SimT::run_popc): every lane runs the event loop and scans the wavefront's queue columns;
-    // the lanes that carry a network execute its events.
-    SimT<CLS> s(p, tile, SimT<CLS>::IMAJOR ? lane * (p.total_words * 4u) : (i & (tw - 1u)) * 4u, 0);
-    bool lead = false;
-    if (active) lead = s.ld(I_DONE) == 0;
-    s.attach_queue(keys, metas, p.lpw, p.ql);
-    s.attach_tables(t_zx, t_zf, t_et);
-    s.attach_round_tables(t_leader, n_leader, t_dur, n_dur);
-    s.attach_weights(t_weights);
-    if (p.n <= 4 && !SimT<CLS>::HCREG) {  // the nodes' hcbr buffers
-      u32* hcb = reinterpret_cast<u32*>(reinterpret_cast<u8*>(lds) + run_lds_bytes_dev(p.ql, p.lpw, 8u, nwaves));
-      s.attach_hcbr(hcb + (size_t)wave * LBFT_LDS_HCBR_WORDS * p.lpw + lane);
-    }
-    s.qlen = 0;
-    if (lead) {
-      s.load_scalars();
-      s.queue_to_lds();
-      s.hcbr_to_lds();
-    }
-#if defined(LBFT_PHASE_TIMERS)
-    u64* wprof = reinterpret_cast<u64*>(reinterpret_cast<u32*>(lds + LBFT_TABLE_U64 + (size_t)nwaves * qslots * qcols) +
-                                        (size_t)meta_words + (meta_words & 1u)) + wave * LBFT_NPHASES;
-    if (lane == 0) { for (int k = 0; k < LBFT_NPHASES; k++) wprof[k] = 0; wprof[31] = __builtin_readcyclecounter(); }
-    s.wprof = wprof;
-    u64 t_begin = __builtin_readcyclecounter();
-#endif
-    bool drained = s.run_popc(lead, keys - lane);
-    if (lead) {
-      done = drained;
-      s.queue_from_lds();
-      s.hcbr_from_lds();
-      s.store_scalars(done);
-    }
-#if defined(LBFT_PHASE_TIMERS)
-    if (p.prof && lane == 0) {
-      for (int k = 0; k < 31; k++) atomicAdd(&p.prof[k], (unsigned long long)s.wprof[k]);
-      atomicAdd(&p.prof[31], (unsigned long long)(__builtin_readcyclecounter() - t_begin));
-    }
-#endif
-  } else
-  if (active) {
-    // (instance-major classes: lane j's instance sits j instances behind the wavefront's first one -- folded into the lane's 32-bit column offset)
-    SimT<CLS> s(p, tile, SimT<CLS>::IMAJOR ? lane * (p.total_words * 4u) : (i & (tw - 1u)) * 4u, 0);
-    if (s.ld(I_DONE) == 0) {
-      s.attach_queue(keys, metas, p.lpw, p.ql);
-      s.attach_tables(t_zx, t_zf, t_et);
-      s.attach_round_tables(t_leader, n_leader, t_dur, n_dur);
-      s.attach_weights(t_weights);
-      if (p.n > 16) {  // receiver / sender lists of process_node_actions: LDS instead of HBM rows
-        u8* lists = reinterpret_cast<u8*>(lds) + run_lds_bytes_dev(p.ql, p.lpw, SimT<CLS>::C0 ? 8u : 12u, nwaves);
-        s.attach_peer_list(lists + ((size_t)wave * p.lpw + lane) * LBFT_MAX_NODES);
-      }
-      if (SimT<CLS>::C0 && p.n <= 4 && !SimT<CLS>::HCREG) {  // the nodes' hcbr buffers (same place as the receiver lists of large networks)
-        u32* hcb = reinterpret_cast<u32*>(reinterpret_cast<u8*>(lds) + run_lds_bytes_dev(p.ql, p.lpw, 8u, nwaves));
-        s.attach_hcbr(hcb + (size_t)wave * LBFT_LDS_HCBR_WORDS * p.lpw + lane);
-      }
-      s.load_scalars();
-      s.queue_to_lds();
-      s.hcbr_to_lds();
-#if defined(LBFT_PHASE_TIMERS)
-      // per-wavefront accumulators behind the queue columns (8-byte aligned: the meta area is a multiple of 8 words)
-      u64* wprof = reinterpret_cast<u64*>(reinterpret_cast<u32*>(lds + LBFT_TABLE_U64 + (size_t)nwaves * qslots * qcols) +
-                                          (size_t)meta_words + (meta_words & 1u)) + wave * LBFT_NPHASES;
-      if (lane == 0) { for (int k = 0; k < LBFT_NPHASES; k++) wprof[k] = 0; wprof[31] = __builtin_readcyclecounter(); }
-      s.wprof = wprof;
-      u64 t_begin = __builtin_readcyclecounter();
-#endif
-      done = s.run();
-      s.queue_from_lds();
-      s.hcbr_from_lds();
-      s.store_scalars(done);
-#if defined(LBFT_PHASE_TIMERS)
-      // every lane of a wavefront sees the wavefront's clock: the first active lane reports
-      if (p.prof && lane == 0) {
-        for (int k = 0; k < 31; k++) atomicAdd(&p.prof[k], (unsigned long long)s.wprof[k]);  // 30 = wavefront loop iterations
-        atomicAdd(&p.prof[31], (unsigned long long)(__builtin_readcyclecounter() - t_begin));  // total cycles
-      }
-#endif
-    }
-  }
-  // one atomic per wavefront: ballot of the lanes that still have pending events
-  unsigned long long pending = __ballot(active && !done);
-  if (pending && lane == (u32)(__ffsll((long long)pending) - 1)) atomicAdd(unfinished, (u32)__popcll(pending));
-}
+// The run kernels: run_body<CLS> (lbft_run_body.h) under the launch bounds of its class.
+#include "lbft_run_body.h"
 // (register-budget experiments: -DLBFT_DEV_ONLY_CLASS=k compiles the event loop of class k alone -- seconds instead of minutes; never a product build)
 #if defined(LBFT_DEV_ONLY_CLASS)
 #define LBFT_DEV_ONLY(k) if ((k) != LBFT_DEV_ONLY_CLASS) return;
@@ -1104,24 +895,29 @@ static int prepare_run(lbft_batch* b, int64_t max_clock) {
   return LBFT_OK;
 }
 
+// The start of a prepared run, between the events ev0 and ev1: the calendar's rows zeroed, no commit time recorded, Simulator::new
+// for every instance.
+static int start_run(lbft_batch* b) {
+  HIP_TRY(hipEventRecord(b->ev0, b->stream));
+  { int zrc = zero_calendar(b); if (zrc != LBFT_OK) return zrc; }
+  { int frc = fill_commit_times(b); if (frc != LBFT_OK) return frc; }
+  b->generation++;
+  { int irc = launch_init(b, (u32)((b->m + b->p.lpw - 1) / b->p.lpw)); if (irc != LBFT_OK) return irc; }
+  HIP_TRY(hipEventRecord(b->ev1, b->stream));
+  return LBFT_OK;
+}
+
 int lbft_batch_run_until(lbft_batch* b, int64_t max_clock) {
   if (!b) return LBFT_ERR_INVALID;
   if (b->ran || b->started) { g_err = "batch already ran (or is being stepped); call lbft_batch_reset first"; return LBFT_ERR_STATE; }
   int prc = prepare_run(b, max_clock);
   if (prc != LBFT_OK) return prc;
   Params& p = b->p;
-  u32 lpw = p.lpw;
 #if defined(LBFT_PHASE_TIMERS)
   HIP_TRY(hipMemsetAsync(b->d_prof, 0, LBFT_NPHASES * sizeof(unsigned long long), b->stream));  // (product builds never write the phase accumulators)
 #endif
   u32 grid_full = (u32)((b->m + LBFT_BLOCK - 1) / LBFT_BLOCK);
-  u32 grid_init = (u32)((b->m + lpw - 1) / lpw);
-  HIP_TRY(hipEventRecord(b->ev0, b->stream));
-  { int zrc = zero_calendar(b); if (zrc != LBFT_OK) return zrc; }
-  { int frc = fill_commit_times(b); if (frc != LBFT_OK) return frc; }
-  b->generation++;
-  { int irc = launch_init(b, grid_init); if (irc != LBFT_OK) return irc; }
-  HIP_TRY(hipEventRecord(b->ev1, b->stream));
+  { int src = start_run(b); if (src != LBFT_OK) return src; }
   u64 launches = 0;
   for (;;) {
     int rc = launch_run(b);
@@ -1147,21 +943,18 @@ static int launch_run(lbft_batch* b) {
   u32 grid_run = (u32)((b->m + (size_t)nwaves * p.lpw - 1) / ((size_t)nwaves * p.lpw));
   HIP_TRY(hipMemsetAsync(b->d_unfinished, 0, sizeof(u32), b->stream));
   b->generation++;
-#define LBFT_LAUNCH(kernel)                                                                                                    \
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-  kernel<<<grid_run, block, lds, b->stream>>>(p, b->d_state, b->d_unfinished);                                               \
-  break
+  auto launch = [&](auto kernel) { return launch_run_kernel(kernel, grid_run, block, lds, b->stream, p, b->d_state, b->d_unfinished); };
   const int cls = sim_class(p);  // (the twins: K_SMALL or K_MID)
   switch (b->launch.kernel) {
-    case RK_RUN0: LBFT_LAUNCH(lbft_k_run0);
-    case RK_RUN0Q: LBFT_LAUNCH(lbft_k_run0q);
-    case RK_RUN0S: LBFT_LAUNCH(lbft_k_run0s);
-    case RK_RUN0U: LBFT_LAUNCH(lbft_k_run0u);
-    case RK_RUN1L: LBFT_LAUNCH(lbft_k_run1l);
-    case RK_RUN1: LBFT_LAUNCH(lbft_k_run<K_MID>);
-    case RK_RUN2L: LBFT_LAUNCH(lbft_k_run2l);
-    case RK_RUN2Q: LBFT_LAUNCH(lbft_k_run2q);
-    case RK_RUN2: LBFT_LAUNCH(lbft_k_run<K_LARGE>);
+    case RK_RUN0: HIP_TRY(launch(lbft_k_run0)); break;
+    case RK_RUN0Q: HIP_TRY(launch(lbft_k_run0q)); break;
+    case RK_RUN0S: HIP_TRY(launch(lbft_k_run0s)); break;
+    case RK_RUN0U: HIP_TRY(launch(lbft_k_run0u)); break;
+    case RK_RUN1L: HIP_TRY(launch(lbft_k_run1l)); break;
+    case RK_RUN1: HIP_TRY(launch(lbft_k_run<K_MID>)); break;
+    case RK_RUN2L: HIP_TRY(launch(lbft_k_run2l)); break;
+    case RK_RUN2Q: HIP_TRY(launch(lbft_k_run2q)); break;
+    case RK_RUN2: HIP_TRY(launch(lbft_k_run<K_LARGE>)); break;
     case RK_PS_RUN0: case RK_PS_RUN1:
       HIP_TRY(g_ps_run(cls, &p, b->d_state, b->d_unfinished, b->d_psets, b->d_set_of, grid_run, block, lds, b->stream));
       break;
@@ -1173,8 +966,6 @@ static int launch_run(lbft_batch* b) {
       break;
     default: g_err = "no launch for this run kernel"; return LBFT_ERR_UNSUPPORTED;
   }
-#undef LBFT_LAUNCH
-  HIP_TRY(hipGetLastError());
   return LBFT_OK;
 }
 
@@ -1186,13 +977,8 @@ int lbft_batch_run_steps(lbft_batch* b, int64_t max_clock, uint32_t steps, uint6
   if (!b->started) {
     int rc = prepare_run(b, max_clock);
     if (rc != LBFT_OK) return rc;
-    u32 grid_init = (u32)((b->m + b->p.lpw - 1) / b->p.lpw);
-    HIP_TRY(hipEventRecord(b->ev0, b->stream));
-    { int zrc = zero_calendar(b); if (zrc != LBFT_OK) return zrc; }
-    { int frc = fill_commit_times(b); if (frc != LBFT_OK) return frc; }
-    b->generation++;
-    { int irc = launch_init(b, grid_init); if (irc != LBFT_OK) return irc; }
-    HIP_TRY(hipEventRecord(b->ev1, b->stream));
+    rc = start_run(b);
+    if (rc != LBFT_OK) return rc;
     b->started = true;
     b->started_max_clock = max_clock;
   } else if (max_clock != b->started_max_clock) {

@@ -1,5 +1,6 @@
-// lbft_launch.h -- launch geometry and LDS layout of the run kernels, shared by liblbft_hip.so (lbft_hip.hip) and the
-// parameter-set kernels of liblbft_paramsets.so (lbft_paramsets.hip), so that the host code of the first sizes the LDS of both alike.
+// lbft_launch.h -- launch geometry and LDS layout of the run kernels (their body: lbft_run_body.h) and the host's launch of one, shared by
+// liblbft_hip.so (lbft_hip.hip), the parameter-set kernels of liblbft_paramsets.so (lbft_paramsets.hip) and the commit-time kernels of
+// liblbft_commit_times.so (lbft_commit_times.hip), so that the host code of the first sizes the LDS of all three alike.
 #ifndef LBFT_LAUNCH_H
 #define LBFT_LAUNCH_H
 #define LBFT_BLOCK 64  // one wavefront per workgroup: wavefronts retire independently
@@ -40,6 +41,14 @@
 #if defined(__HIPCC__)
 __device__ __forceinline__ size_t run_lds_bytes_dev(u32 ql, u32 lpw, u32 slot_bytes, u32 nwaves) {  // = run_lds_bytes(ql, lpw, 0, ..): where the receiver lists start
   return (size_t)LBFT_TABLE_U64 * 8 + (size_t)nwaves * ql * lpw * slot_bytes + (size_t)nwaves * LBFT_NPHASES * 8 + 8;
+}
+// One launch of run kernel `kernel` with `lds_bytes` of dynamic LDS (more than the default limit: the attribute is set first)
+template <typename... KArgs, typename... Args>
+inline hipError_t launch_run_kernel(void (*kernel)(KArgs...), u32 grid, u32 block, size_t lds_bytes, hipStream_t stream, const Args&... args) {
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+  if (e != hipSuccess) return e;
+  kernel<<<grid, block, lds_bytes, stream>>>(args...);
+  return hipGetLastError();
 }
 #endif
 #ifndef LBFT_RUN_WAVES_PER_SIMD

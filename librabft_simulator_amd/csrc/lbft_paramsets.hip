@@ -16,7 +16,8 @@
 using namespace lbft;
 
 #include "lbft_launch.h"
-#include "lbft_lane_run.h"  // ps_run_body
+#include "lbft_run_body.h"  // run_body
+static_assert(run_lane_private<K_SMALL_SETS> && run_lane_private<K_MID_SETS>, "lane-private classes only");
 
 // Simulator::new for every instance: init() draws the startup times with the set's delay parameters.
 __global__ __launch_bounds__(LBFT_BLOCK) void lbft_k_ps_init(Params p, u32* __restrict__ state, const u64* __restrict__ seeds,
@@ -31,12 +32,12 @@ __global__ __launch_bounds__(LBFT_BLOCK) void lbft_k_ps_init(Params p, u32* __re
 // Small class (lbft_k_run0's geometry: two wavefronts per SIMD): n <= 16, honest, lossless, no trace, reference routing.
 __global__ __launch_bounds__(LBFT_RUN_BLOCK) __attribute__((amdgpu_waves_per_eu(LBFT_RUN_WAVES_PER_SIMD, LBFT_RUN_WAVES_PER_SIMD)))
 void lbft_k_ps_run0(Params p, u32* __restrict__ state, u32* __restrict__ unfinished, const ParamSetDev* __restrict__ sets, const u8* __restrict__ set_of) {
-  ps_run_body<K_SMALL_SETS>(p, state, unfinished, sets, set_of, nullptr);
+  run_body<K_SMALL_SETS>(p, state, unfinished, sets, set_of);
 }
 // Mid class (lbft_k_run<1>'s geometry: one wavefront per SIMD, the whole register file): n <= 32, every feature.
 __global__ __launch_bounds__(64 * LBFT_RUN_WAVES_FULL)
 void lbft_k_ps_run1(Params p, u32* __restrict__ state, u32* __restrict__ unfinished, const ParamSetDev* __restrict__ sets, const u8* __restrict__ set_of) {
-  ps_run_body<K_MID_SETS>(p, state, unfinished, sets, set_of, nullptr);
+  run_body<K_MID_SETS>(p, state, unfinished, sets, set_of);
 }
 
 extern "C" {
@@ -50,12 +51,7 @@ __attribute__((visibility("default"))) hipError_t lbft_ps_launch_init(const Para
 __attribute__((visibility("default"))) hipError_t lbft_ps_launch_run(int cls, const Params* p, u32* state, u32* unfinished, const ParamSetDev* sets,
                                                                     const u8* set_of, u32 grid, u32 block, size_t lds_bytes, hipStream_t stream) {
   if (cls != K_SMALL && cls != K_MID) return hipErrorInvalidValue;
-  const void* fn = cls == K_SMALL ? reinterpret_cast<const void*>(lbft_k_ps_run0) : reinterpret_cast<const void*>(lbft_k_ps_run1);
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-  if (e != hipSuccess) return e;
-  if (cls == K_SMALL) lbft_k_ps_run0<<<grid, block, lds_bytes, stream>>>(*p, state, unfinished, sets, set_of);
-  else lbft_k_ps_run1<<<grid, block, lds_bytes, stream>>>(*p, state, unfinished, sets, set_of);
-  return hipGetLastError();
+  return launch_run_kernel(cls == K_SMALL ? lbft_k_ps_run0 : lbft_k_ps_run1, grid, block, lds_bytes, stream, *p, state, unfinished, sets, set_of);
 }
 
 }  // extern "C"
