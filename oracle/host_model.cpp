@@ -359,19 +359,28 @@ int lbft_hostmodel_session_save_node(void* h, uint32_t inst, uint32_t node, uint
   return 0;
 }
 
-// ---- The planner of the device library (csrc/lbft_plan.h: plan_layout + plan_launch with the default knobs) for one batch, so that
-// the CPU tier takes a batch's geometry from the code the device runs.  capacities: queue, snapshot, block, log (0 = auto); lanes: per
-// wavefront, 0 = auto; n_sets: parameter sets of the batch (0 = a plain batch; `cfg` is then the batch-wide configuration);
-// avail_bytes: the device memory the state may take.  The struct is mirrored by oracle_ctypes.HostModelPlan.  -> 0, or the planner's
-// error code.  (The horizon's range is the run's check, not the planner's.)
+// ---- The planner of the device library (csrc/lbft_plan.h: plan_layout + plan_launch) for one batch, so that the CPU tier takes a
+// batch's geometry from the code the device runs.  capacities: queue, snapshot, block, log (0 = auto); lanes: per wavefront, 0 = auto;
+// n_sets: parameter sets of the batch (0 = a plain batch; `cfg` is then the batch-wide configuration); avail_bytes: the device memory
+// the state may take.  lbft_hostmodel_plan plans with the default knobs, lbft_hostmodel_plan_knobs with the caller's (what the device
+// library reads from the environment, lbft_hip.hip knobs_from_env; nothing here reads it).  The structs are mirrored by
+// oracle_ctypes.HostModelPlan / HostModelKnobs.  -> 0, or the planner's error code.  (The horizon's range is the run's check, not the
+// planner's.)
 typedef struct lbft_hostmodel_plan_out {
   uint32_t qcap, scap, bcap, lcap, ecap, qheap, qcal, ring, ring_topup, tw, lpw, ql, blw, run_waves, kernel /* RunKernel */, lds_bytes;
   uint32_t layout[8];  // lbft_batch_layout
   uint64_t state_bytes, device_bytes;  // lbft_batch_device_bytes
 } lbft_hostmodel_plan_out;
 
-int lbft_hostmodel_plan(const lbft_oracle_config* cfg, const uint32_t* capacities, size_t n_instances, int64_t max_clock, uint32_t lanes,
-                        uint32_t n_sets, int commit_times, int keep_stores, int calendar_queue, uint64_t avail_bytes, lbft_hostmodel_plan_out* out) {
+// The fields of PlanKnobs the caller sets, in this order from bit 0 of `set`; a field whose bit is clear keeps PlanKnobs' own default, so
+// the defaults are stated in lbft_plan.h alone (ring / ring_topup: the bit is ring_set / ring_topup_set, an unset variable without it)
+typedef struct lbft_hostmodel_knobs {
+  uint32_t set, no_quad, no_popc, no_uni, no_lean, lean2, ring, ring_topup, blk_window;
+} lbft_hostmodel_knobs;
+
+int lbft_hostmodel_plan_knobs(const lbft_oracle_config* cfg, const uint32_t* capacities, size_t n_instances, int64_t max_clock, uint32_t lanes,
+                              uint32_t n_sets, int commit_times, int keep_stores, int calendar_queue, uint64_t avail_bytes,
+                              const lbft_hostmodel_knobs* hk /* NULL = the defaults */, lbft_hostmodel_plan_out* out) {
   lbft_config c = product_config(cfg);
   c.queue_capacity = capacities[0]; c.snapshot_capacity = capacities[1]; c.block_capacity = capacities[2]; c.log_capacity = capacities[3];
   if (int rc = validate(&c)) return rc;
@@ -379,7 +388,18 @@ int lbft_hostmodel_plan(const lbft_oracle_config* cfg, const uint32_t* capacitie
   Params p;
   std::vector<u32> weights;
   if (int rc = fill_params(&c, n_instances, p, weights)) return rc;
-  const PlanKnobs knobs;
+  PlanKnobs knobs;
+  if (hk) {
+    const uint32_t set = hk->set;
+    if (set & 1u) knobs.no_quad = hk->no_quad != 0;
+    if (set & 2u) knobs.no_popc = hk->no_popc != 0;
+    if (set & 4u) knobs.no_uni = hk->no_uni != 0;
+    if (set & 8u) knobs.no_lean = hk->no_lean != 0;
+    if (set & 16u) knobs.lean2 = hk->lean2 != 0;
+    if (set & 32u) { knobs.ring_set = true; knobs.ring = hk->ring; }
+    if (set & 64u) { knobs.ring_topup_set = true; knobs.ring_topup = hk->ring_topup; }
+    if (set & 128u) knobs.blk_window = hk->blk_window;
+  }
   bool relayout;
   std::string err;
   LaunchPlan launch;
@@ -393,6 +413,12 @@ int lbft_hostmodel_plan(const lbft_oracle_config* cfg, const uint32_t* capacitie
   out->state_bytes = state_words(p) * sizeof(u32);
   out->device_bytes = device_bytes(p, out->state_bytes, n_sets, commit_times ? commit_times_bytes(p) : 0);
   return 0;
+}
+
+int lbft_hostmodel_plan(const lbft_oracle_config* cfg, const uint32_t* capacities, size_t n_instances, int64_t max_clock, uint32_t lanes,
+                        uint32_t n_sets, int commit_times, int keep_stores, int calendar_queue, uint64_t avail_bytes, lbft_hostmodel_plan_out* out) {
+  return lbft_hostmodel_plan_knobs(cfg, capacities, n_instances, max_clock, lanes, n_sets, commit_times, keep_stores, calendar_queue, avail_bytes,
+                                   nullptr, out);
 }
 
 }  // extern "C"

@@ -454,20 +454,56 @@ class HostModelPlan(C.Structure):
                [("layout", C.c_uint32 * 8), ("state_bytes", C.c_uint64), ("device_bytes", C.c_uint64)]
 
 
+class HostModelKnobs(C.Structure):
+    """``set``: bit k = the k-th field after it is given; the others keep the defaults of PlanKnobs (csrc/lbft_plan.h), stated there alone."""
+    _fields_ = [(n, C.c_uint32) for n in ("set", "no_quad", "no_popc", "no_uni", "no_lean", "lean2", "ring", "ring_topup", "blk_window")]
+
+
+# The tuning variables the device library reads when a run is prepared (lbft_hip.hip knobs_from_env; DESIGN.md section 4 "Knobs")
+SWITCHES = ("LBFT_NO_QUAD", "LBFT_NO_POPC", "LBFT_NO_UNI", "LBFT_NO_LEAN", "LBFT_LEAN2", "LBFT_RING", "LBFT_RING_TOPUP", "LBFT_BLK_WINDOW")
+
+
+def knobs_of_switches(switches):
+    """``plan(knobs=...)`` for a dict of the environment variables ``SWITCHES`` (name -> decimal text or int; an absent name = an unset
+    variable), read as knobs_from_env reads them."""
+    unknown = set(switches) - set(SWITCHES)
+    if unknown:
+        raise KeyError(sorted(unknown))
+    k = {n[5:].lower(): int(bool(int(switches[n]))) for n in SWITCHES[:4] if n in switches}
+    if "LBFT_LEAN2" in switches:
+        k["lean2"] = int(bool(int(switches["LBFT_LEAN2"])))
+    for n in SWITCHES[5:]:
+        if n in switches:
+            k[{"LBFT_RING": "ring", "LBFT_RING_TOPUP": "ring_topup", "LBFT_BLK_WINDOW": "blk_window"}[n]] = int(switches[n])
+    return k
+
+
 def plan(cfg, n_instances, max_clock, queue_capacity=0, snapshot_capacity=0, block_capacity=0, log_capacity=0, lanes_per_wavefront=0,
-         param_sets=0, commit_times=False, keep_stores=False, calendar_queue=True, avail_bytes=1 << 40):
+         param_sets=0, commit_times=False, keep_stores=False, calendar_queue=True, avail_bytes=1 << 40, knobs=None):
     """The geometry the device library chooses for a batch of ``cfg`` (an OracleConfig; for a parameter-set batch the batch-wide one and
     ``param_sets`` = their number): csrc/lbft_plan.h's plan_layout + plan_launch, compiled into the host model -- capacities, queue
     discipline, ring, tile width, lanes per wavefront, LDS slots, run kernel, the words of lbft_batch_layout, device bytes.
-    ``avail_bytes``: the device memory the state may take.  Raises ValueError with the planner's code on a refused batch."""
+    ``avail_bytes``: the device memory the state may take.  ``knobs``: the tuning switches as PlanKnobs fields -- no_quad, no_popc,
+    no_uni, no_lean, lean2 (0 / 1), ring, ring_topup, blk_window (entries); a field left out is the unset variable (knobs_of_switches
+    turns a dict of variables into one); None = every default.  Raises ValueError with the planner's code on a refused batch."""
     L = hostmodel_lib()
-    L.lbft_hostmodel_plan.argtypes = [C.POINTER(OracleConfig), C.POINTER(C.c_uint32), C.c_size_t, C.c_int64, C.c_uint32, C.c_uint32, C.c_int,
-                                      C.c_int, C.c_int, C.c_uint64, C.POINTER(HostModelPlan)]
-    L.lbft_hostmodel_plan.restype = C.c_int
+    L.lbft_hostmodel_plan_knobs.argtypes = [C.POINTER(OracleConfig), C.POINTER(C.c_uint32), C.c_size_t, C.c_int64, C.c_uint32, C.c_uint32, C.c_int,
+                                            C.c_int, C.c_int, C.c_uint64, C.POINTER(HostModelKnobs), C.POINTER(HostModelPlan)]
+    L.lbft_hostmodel_plan_knobs.restype = C.c_int
+    hk = None
+    if knobs is not None:
+        fields = [n for n, _ in HostModelKnobs._fields_[1:]]
+        unknown = set(knobs) - set(fields)
+        if unknown:
+            raise KeyError(sorted(unknown))
+        hk = HostModelKnobs()
+        for n, v in knobs.items():
+            setattr(hk, n, int(v))
+            hk.set |= 1 << fields.index(n)
     caps = (C.c_uint32 * 4)(queue_capacity, snapshot_capacity, block_capacity, log_capacity)
     out = HostModelPlan()
-    rc = L.lbft_hostmodel_plan(C.byref(cfg), caps, n_instances, max_clock, lanes_per_wavefront, param_sets, bool(commit_times), bool(keep_stores),
-                               bool(calendar_queue), avail_bytes, C.byref(out))
+    rc = L.lbft_hostmodel_plan_knobs(C.byref(cfg), caps, n_instances, max_clock, lanes_per_wavefront, param_sets, bool(commit_times),
+                                     bool(keep_stores), bool(calendar_queue), avail_bytes, C.byref(hk) if hk is not None else None, C.byref(out))
     if rc != 0:
         raise ValueError("the planner refuses the batch: %d" % rc)
     d = {n: getattr(out, n) for n, _ in HostModelPlan._fields_}
