@@ -362,6 +362,35 @@ int lbft_batch_round_switches(const lbft_batch* b, size_t inst, int64_t* out, si
 int lbft_batch_round_stats(const lbft_batch* b, uint32_t bin_width, uint32_t bins, uint64_t* stay_hist, uint64_t* skew_hist, uint64_t* stats);
 int lbft_batch_round_switches_all(const lbft_batch* b, int64_t* out, size_t cap_rounds, uint64_t* max_round /*[m]*/, uint64_t* messages /*[m], may be NULL*/);
 
+/* Chain statistics: agreement, chain quality and block cadence per group, computed on the device from what every run leaves behind -- the
+ * nodes' commit logs, the block pool the nodes of an instance share (equal id = equal block), the startup times and the fault words.  The
+ * call needs no commit times and no round trace.  For instance i without a fault (a non-zero fault word skips the instance,
+ * LBFT_FAULT_LOG_OVERFLOW included):
+ *   nc_j = min(commit count of node j, log capacity);
+ *   the chain is the log of the reference node `ref`, the lowest-numbered node with the largest nc_j; L = nc_ref;
+ *   entry k of the chain is block b_k, its author a_k, its global proposal time g_k = startup[a_k] + time of b_k (the quantity the
+ *   latency histogram subtracts).
+ * Groups are those of the latency histogram (the parameter sets, or one group for a plain batch).  Six sample families, each reported as
+ * stats[g * LBFT_CHAIN_STATS + 4 * family + {0, 1, 2, 3}] = samples, sum, min, max (min = max = 0 without samples):
+ *   family 0, interval:   max(g_{k+1} - g_k, 0) for k = 0 .. L - 2, one sample per consecutive pair of the chain; also binned,
+ *                         interval_hist[g * bins + min(interval / bin_width, bins - 1)]
+ *   family 1, length:     L, one sample per instance
+ *   family 2, lag:        L - nc_j, one sample per (instance, node), `ref` included (it gives 0)
+ *   family 3, tenure:     the lengths of the maximal runs of consecutive chain entries with the same author, one sample per run; a chain
+ *                         of L >= 1 entries has handovers + 1 runs, and they sum to L
+ *   family 4, differing:  one sample per instance, the number of pairs (j, k), k < nc_j, with log[j][k] != b_k; a sum of 0 means that every
+ *                         node's history is a prefix of its instance's chain
+ *   family 5, inversions: one sample per instance, the number of k with g_{k+1} < g_k
+ * author_blocks[g * num_nodes + a] = the chain entries of the group's instances authored by a; a group's row sums to family 1's sum.
+ * bin_width >= 1, bins >= 1, groups * bins <= 2^31 (LBFT_ERR_INVALID otherwise, and for NULL arguments, before any HIP call).  Legal
+ * whenever lbft_batch_commit_counts is -- after a finished run (lbft_batch_run_until, lbft_batch_run_steps once it reports 0, also on a
+ * batch that loaded a checkpoint) or after lbft_batch_manual_finalize of a node-level session; LBFT_ERR_STATE otherwise.  The batch may be
+ * plain or parameter-set, timed or not, traced or not, of any kernel class (2 to 128 nodes).  The call changes no state.  Computed on the
+ * device (lbft_k_cs_chain, liblbft_chain_stats.so beside this library; LBFT_ERR_UNSUPPORTED naming it when it is missing); every
+ * accumulation is an integer add, min or max: bit-reproducible. */
+#define LBFT_CHAIN_STATS 24
+int lbft_batch_chain_stats(const lbft_batch* b, uint32_t bin_width, uint32_t bins, uint64_t* interval_hist, uint64_t* author_blocks, uint64_t* stats);
+
 /* ---- Node-level interface: the reference's trait surface for ONE node of ONE instance, without the event loop
  * (bft-lib/src/interfaces.rs:12-86), so that record-store / pacemaker scenarios can be replayed step by step
  * (librabft-v2/src/unit_tests/record_store_tests.rs) and a host-side driver other than the batch simulator (the

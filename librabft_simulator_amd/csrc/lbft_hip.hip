@@ -26,6 +26,7 @@
 #include "lbft_commit_times.h"
 #include "lbft_commit_timeline.h"
 #include "lbft_round_stats.h"
+#include "lbft_chain_stats.h"
 #include "lbft_round_timeline.h"
 
 using namespace lbft;
@@ -1349,6 +1350,30 @@ int lbft_batch_round_stats(const lbft_batch* b, uint32_t bin_width, uint32_t bin
   unsigned long long* d_stats = gc.out(stats, groups * LBFT_ROUND_STATS, true);
   if (gc.e == hipSuccess) gc.e = g_rs_rounds(&b->p, b->d_state, gc.d_inst, gc.d_off, (u32)groups, gc.gi.max_group, bin_width, bins, d_stay, d_skew, d_stats, b->stream);
   return gc.finish("round statistics");
+}
+
+// ---- chain statistics (lbft_batch_chain_stats) ----
+// The kernel lives in liblbft_chain_stats.so (lbft_chain_stats.hip), opened beside this library on first use, like the other side
+// libraries: a batch that never asks for the statistics loads nothing.
+static lbft_cs_chain_fn g_cs_chain = nullptr;
+static int load_chain_stats_lib() { return load_side_lib(LBFT_CHAIN_STATS_LIB, "chain statistics", {{"lbft_cs_launch_chain", (void**)&g_cs_chain}}); }
+
+// Chain statistics per group, computed on the device from the commit logs, the block pool and the startup times (lbft_k_cs_chain).
+// Legal when lbft_batch_commit_counts is: after a finished run (lbft_batch_run_until, a drained lbft_batch_run_steps, also after a
+// checkpoint load) or a node-level session's lbft_batch_manual_finalize.  Arguments are checked before the first HIP call; the call
+// changes no state of the batch.
+int lbft_batch_chain_stats(const lbft_batch* b, uint32_t bin_width, uint32_t bins, uint64_t* interval_hist, uint64_t* author_blocks, uint64_t* stats) {
+  int rc = refuse_grouped(b, interval_hist && author_blocks && stats, bin_width, bins, false);
+  if (rc != LBFT_OK) return rc;
+  rc = load_chain_stats_lib();
+  if (rc != LBFT_OK) return rc;
+  const size_t groups = group_count(b);
+  HIP_TRY(hipSetDevice(b->device));
+  GroupedCall gc(b);
+  unsigned long long *d_hist = gc.out(interval_hist, groups * bins), *d_auth = gc.out(author_blocks, groups * b->p.n);
+  unsigned long long* d_stats = gc.out(stats, groups * LBFT_CHAIN_STATS, true);
+  if (gc.e == hipSuccess) gc.e = g_cs_chain(&b->p, b->d_state, gc.d_inst, gc.d_off, (u32)groups, gc.gi.max_group, bin_width, bins, d_hist, d_auth, d_stats, b->stream);
+  return gc.finish("chain statistics");
 }
 
 // Every instance's round-switch table in one call: out[(inst * cap_rounds + round) * num_nodes + node], what lbft_batch_round_switches

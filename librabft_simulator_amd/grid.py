@@ -16,6 +16,9 @@ ticks (BatchResult.commit_series).
 instance that passes it counts as faulted and gives no sample) and adds a ``"round_stats"`` object (BatchResult.rounds_by_param_set: how
 long nodes stay in a round, how many rounds they jump, how far apart the nodes of a network enter a round and how many of them enter it);
 ``"rounds"``, the final active round's mean / min / max, stays as it is.
+``--chain`` adds a ``"chain"`` object (BatchResult.chain_by_param_set: the intervals between the proposals of consecutive blocks of the
+committed chain, its length, the nodes' lag behind it, the leaders' tenure, the blocks per proposer and whether every node's history is
+a prefix of the chain); it needs neither commit times nor the trace and leaves the batch on the kernel it would run anyway.
 """
 import argparse
 import itertools
@@ -101,6 +104,7 @@ def main(argv=None):
     ap.add_argument("--stalls", action="store_true", help="record commit times and add each point's stall / recovery summary")
     ap.add_argument("--series", type=int, default=None, metavar="WIDTH", help="record commit times and add each point's commits per WIDTH ticks")
     ap.add_argument("--rounds", action="store_true", help="record the round-switch trace and add each point's round statistics")
+    ap.add_argument("--chain", action="store_true", help="add each point's chain statistics (agreement, chain quality, block cadence)")
     ap.add_argument("--round-trace", type=int, default=None, metavar="N", help="with --rounds: rounds per node the trace keeps")
     args = ap.parse_args(argv)
     if args.round_trace is not None and (args.round_trace < 1 or not args.rounds):
@@ -125,6 +129,7 @@ def main(argv=None):
         stalls = res.stalls_by_param_set(since="partition_end") if args.stalls else None
         series = res.commit_series(bin_width=args.series) if args.series is not None else None
         round_stats = res.rounds_by_param_set() if args.rounds else None
+        chain = res.chain_by_param_set() if args.chain else None
         for k, (pt, row) in enumerate(zip(points, res.by_param_set())):
             line = dict(pt, nodes=args.nodes, max_clock=args.max_clock, seeds=args.seeds_per_point, assign=args.assign)
             line.update(instances=row["instances"], faulted=row["faulted"], commits=row["commits"], rounds=row["rounds"])
@@ -136,6 +141,8 @@ def main(argv=None):
                 line["series"] = [int(v) for v in series[k]]
             if round_stats is not None:
                 line["round_stats"] = round_stats[k]
+            if chain is not None:
+                line["chain"] = chain[k]
             print(json.dumps(line), flush=True)
     finally:
         sim.close()

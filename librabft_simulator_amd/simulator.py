@@ -341,6 +341,47 @@ class BatchResult:
             out.append(row)
         return out
 
+    def chain_stats(self, bin_width=None, bins=None):
+        """Statistics of the committed chain computed on the device (lbft_batch_chain_stats), per group (the parameter sets of a
+        ``with_param_sets`` batch, else one group): ``(interval_hist, author_blocks, stats)``.  An instance's chain is the log of its
+        reference node, the lowest-numbered node with the most commits; a chain entry's proposal time is
+        ``startup_times[proposer] + time``.  ``interval_hist[group, min(interval // bin_width, bins - 1)]`` counts the times between the
+        proposals of consecutive chain entries; ``author_blocks[group, a]`` the chain entries proposed by node ``a``; ``stats[group]``
+        (24 uint64) holds ``(samples, sum, min, max)`` of six families: ``interval``, ``length`` (chain entries, per instance), ``lag``
+        (chain length - a node's commits, per (instance, node)), ``tenure`` (consecutive chain entries of one proposer, per run),
+        ``differing`` (per instance, the entries of all its nodes' histories that are not the chain's entry at that place: a sum of 0
+        means that every history is a prefix of the chain) and ``inversions`` (per instance, the chain entries proposed before their
+        predecessor; their interval counts as 0).  Instances with a fault are skipped.  Needs nothing of the run: no commit times, no
+        round trace.  Groups and default binning as ``latency_histogram``."""
+        bin_width, bins = self._binning(bin_width, bins)
+        groups = self._groups()
+        hist = np.zeros((groups, bins), dtype=np.uint64)
+        authors = np.zeros((groups, self._sim.num_nodes), dtype=np.uint64)
+        stats = np.zeros((groups, _lib.CHAIN_STATS), dtype=np.uint64)
+        check(_lib.lib().lbft_batch_chain_stats(self._sim._h, bin_width, bins, hist.ctypes.data, authors.ctypes.data, stats.ctypes.data))
+        return hist, authors, stats
+
+    def chain_by_param_set(self, quantiles=(0.5, 0.9, 0.99)):
+        """Per group of ``chain_stats`` (default, exact binning), in set order: ``interval`` = samples, mean, min, max and ``quantiles``
+        ({str(q): ticks}, the inverted-CDF rule of ``histogram_quantile``); ``length``, ``differing`` and ``inversions`` = instances, mean,
+        min, max; ``lag`` = nodes, mean, min, max; ``tenure`` = runs, mean, min, max; ``authors``, the chain blocks per proposer, and
+        ``author_share``, their fractions of the group's chain blocks (``None`` when it has none); ``agreement``: every history is a prefix
+        of its instance's chain and no chain goes back in time.  ``None`` where there are no samples."""
+        width, _ = self._binning(None, None)
+        hist, authors, stats = self.chain_stats()
+        out = []
+        for g in range(hist.shape[0]):
+            row = {"set": g, **_families(stats[g], (("interval", "samples"), ("length", "instances"), ("lag", "nodes"), ("tenure", "runs"),
+                                                    ("differing", "instances"), ("inversions", "instances")))}
+            row["interval"]["quantiles"] = {str(q): histogram_quantile(hist[g], width, q) for q in quantiles}
+            counts = [int(v) for v in authors[g]]
+            blocks = sum(counts)
+            row["authors"] = counts
+            row["author_share"] = [c / blocks for c in counts] if blocks else None
+            row["agreement"] = int(stats[g, 4 * 4 + 1]) == 0 and int(stats[g, 4 * 5 + 1]) == 0
+            out.append(row)
+        return out
+
     def by_param_set(self):
         """Per parameter set of a ``BatchSimulator.with_param_sets`` batch, in set order: the number of instances, of faulted instances,
         and mean / min / max over its instances of the commits and of the active round (each instance's minimum over its nodes)."""
