@@ -108,6 +108,28 @@ pub struct LbftCounters {
     pub timers_folded: u64,
     pub node_updates: u64,
 }
+/// `lbft_record_hash` (include/lbft.h): one entry of a committed chain's record hashes
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct LbftRecordHash {
+    pub block_hash: u64,
+    pub state: u64,
+    pub qc_hash: u64,
+    pub num_votes: u32,
+    pub flags: u32,
+}
+/// `lbft_chain_head` (include/lbft.h): the last entry of an instance's committed chain, its length and reference node
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct LbftChainHead {
+    pub block_hash: u64,
+    pub state: u64,
+    pub qc_hash: u64,
+    pub length: u32,
+    pub ref_node: u32,
+    pub num_votes: u32,
+    pub flags: u32,
+}
 
 pub const LBFT_OK: c_int = 0;
 pub const LBFT_ERR_FAULT: c_int = -5;
@@ -128,6 +150,9 @@ extern "C" {
     fn lbft_batch_commit_counts(b: *const c_void, out: *mut u32) -> c_int;
     fn lbft_batch_committed_history(b: *const c_void, inst: usize, node: u32, out: *mut LbftCommit, cap: usize, len: *mut usize) -> c_int;
     fn lbft_batch_last_committed_state(b: *const c_void, inst: usize, node: u32, out: *mut u64) -> c_int;
+    /// the record hashes of every instance's committed chain in one device call; `out` ([inst][cap_per_instance]) and `node_prefix`
+    /// ([inst][node]) may be null, `heads` ([inst]) is required: see include/lbft.h `lbft_batch_chain_record_hashes`
+    pub fn lbft_batch_chain_record_hashes(b: *const c_void, out: *mut LbftRecordHash, cap_per_instance: usize, heads: *mut LbftChainHead, node_prefix: *mut u32) -> c_int;
     fn lbft_batch_destroy(b: *mut c_void);
     // node-level interface
     fn lbft_batch_manual_begin(b: *mut c_void, max_clock: i64) -> c_int;

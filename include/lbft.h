@@ -391,6 +391,36 @@ int lbft_batch_round_switches_all(const lbft_batch* b, int64_t* out, size_t cap_
 #define LBFT_CHAIN_STATS 24
 int lbft_batch_chain_stats(const lbft_batch* b, uint32_t bin_width, uint32_t bins, uint64_t* interval_hist, uint64_t* author_blocks, uint64_t* stats);
 
+/* Record hashes of every committed chain of a batch in one device call: what lbft_batch_committed_record_hashes gives for one
+ * (instance, node), for the chain of every instance.  The nodes of an instance share one block pool (equal id = equal block = equal
+ * QC) and every history is a prefix of its instance's chain (chain statistics, family 4), so an instance's records are hashed once.
+ *   The chain of instance i is the log of its reference node by the rule of the chain statistics: nc_j = min(commit count of node j,
+ *   log capacity), `ref` = the lowest-numbered node with the largest nc_j, L = nc_ref.
+ *   out[i * cap_per_instance + k], k < min(length, cap_per_instance): entry k of lbft_batch_committed_record_hashes(i, ref) -- the same
+ *   four values, the same flag bits 0 and 1.  Entries at and past min(length, cap_per_instance) are zero.  out may be NULL: heads only.
+ *   heads[i]: the last entry (block_hash, state, qc_hash, num_votes, flags) with the number of entries `length` and `ref_node`.  The
+ *   last QC hash commits to every block, state and vote below it.  An empty chain gives all zeros (length == 0).
+ *   node_prefix[i * num_nodes + j] (may be NULL): the number of leading entries of node j's log, among its first min(nc_j, length), that
+ *   equal the chain's; it equals nc_j exactly when the node's history is a prefix of the chain, and then
+ *   lbft_batch_committed_record_hashes(i, j) is out[i][0 .. nc_j).
+ * An instance with a non-zero fault word is not walked: length 0, zeros, node_prefix 0 (as the other device statistics).  A log entry
+ * that is 0 or above the instance's block count is no index into the pool: it ends the walk of that instance with flag bit 2 on that
+ * entry (its hashes 0), which is then the last one (length = its index + 1); the kernel reads no block record it has not checked so.
+ * Bits of a block's voter words at and above num_nodes are no authors and are not counted.
+ * Legal whenever lbft_batch_commit_counts is (see lbft_batch_chain_stats), on plain, parameter-set and timed batches of any kernel class
+ * (2 to 128 nodes); LBFT_ERR_STATE otherwise.  LBFT_ERR_INVALID for a NULL b or heads, or out != NULL with cap_per_instance == 0; every
+ * refusal comes before the first HIP call.  The call changes no state.  Computed on the device (lbft_k_rh_chain,
+ * liblbft_record_hashes.so beside this library; LBFT_ERR_UNSUPPORTED naming it when it is missing): one segment of lanes per instance,
+ * SipHash a word at a time (csrc/lbft_record_hash_rules.h).  The device-side copy of `out` is taken in chunks of instances of at most
+ * 256 MiB, each copied back on the batch's stream. */
+typedef struct lbft_chain_head {
+  uint64_t block_hash, state, qc_hash;
+  uint32_t length, ref_node;
+  uint32_t num_votes, flags;
+} lbft_chain_head;
+int lbft_batch_chain_record_hashes(const lbft_batch* b, lbft_record_hash* out, size_t cap_per_instance, lbft_chain_head* heads,
+                                   uint32_t* node_prefix);
+
 /* ---- Node-level interface: the reference's trait surface for ONE node of ONE instance, without the event loop
  * (bft-lib/src/interfaces.rs:12-86), so that record-store / pacemaker scenarios can be replayed step by step
  * (librabft-v2/src/unit_tests/record_store_tests.rs) and a host-side driver other than the batch simulator (the

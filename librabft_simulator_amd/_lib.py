@@ -136,6 +136,9 @@ class LbftNodeView(C.Structure):
 
 COMMIT_DTYPE = np.dtype([("proposer", "<u8"), ("index", "<u8"), ("time", "<i8")])
 RECORD_HASH_DTYPE = np.dtype([("block_hash", "<u8"), ("state", "<u8"), ("qc_hash", "<u8"), ("num_votes", "<u4"), ("flags", "<u4")])
+# lbft_chain_head: the last entry of an instance's committed chain with the chain's length and reference node
+CHAIN_HEAD_DTYPE = np.dtype([("block_hash", "<u8"), ("state", "<u8"), ("qc_hash", "<u8"), ("length", "<u4"), ("ref_node", "<u4"),
+                             ("num_votes", "<u4"), ("flags", "<u4")])
 
 # every symbol include/lbft.h declares (tests check that the library exports all of them)
 ABI_SYMBOLS = [
@@ -147,7 +150,7 @@ ABI_SYMBOLS = [
     "lbft_batch_device_bytes", "lbft_batch_set_max_steps", "lbft_batch_set_lanes_per_wavefront",
     "lbft_batch_set_lds_queue_slots", "lbft_batch_set_calendar_queue", "lbft_batch_phase_cycles", "lbft_batch_layout",
     "lbft_batch_run_steps", "lbft_batch_checkpoint_bytes", "lbft_batch_checkpoint_save", "lbft_batch_checkpoint_load",
-    "lbft_batch_enable_round_trace", "lbft_batch_keep_retired_stores", "lbft_batch_counters_allreduce", "lbft_batch_counters_allgather_reduce", "lbft_node_calls", "lbft_batch_round_switches", "lbft_batch_round_switches_all", "lbft_batch_round_stats", "lbft_batch_chain_stats", "lbft_batch_manual_begin", "lbft_batch_manual_finalize", "lbft_node_update", "lbft_node_create_notification",
+    "lbft_batch_enable_round_trace", "lbft_batch_keep_retired_stores", "lbft_batch_counters_allreduce", "lbft_batch_counters_allgather_reduce", "lbft_node_calls", "lbft_batch_round_switches", "lbft_batch_round_switches_all", "lbft_batch_round_stats", "lbft_batch_chain_stats", "lbft_batch_chain_record_hashes", "lbft_batch_manual_begin", "lbft_batch_manual_finalize", "lbft_node_update", "lbft_node_create_notification",
     "lbft_node_handle_notification", "lbft_node_release_notification", "lbft_node_create_request", "lbft_node_handle_request",
     "lbft_node_handle_response", "lbft_node_view_get", "lbft_device_leaders", "lbft_device_sample_delays",
     "lbft_device_exp_log", "lbft_last_error", "lbft_build_info",
@@ -322,6 +325,8 @@ def lib():
     L.lbft_batch_round_stats.restype = C.c_int
     L.lbft_batch_chain_stats.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp]
     L.lbft_batch_chain_stats.restype = C.c_int
+    L.lbft_batch_chain_record_hashes.argtypes = [vp, vp, C.c_size_t, vp, vp]
+    L.lbft_batch_chain_record_hashes.restype = C.c_int
     L.lbft_batch_manual_begin.argtypes = [vp, C.c_int64]
     L.lbft_batch_manual_begin.restype = C.c_int
     L.lbft_batch_manual_finalize.argtypes = [vp]

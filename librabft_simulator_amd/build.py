@@ -1,10 +1,11 @@
-"""Build liblbft_hip.so, liblbft_paramsets.so, liblbft_commit_times.so, liblbft_round_stats.so and liblbft_chain_stats.so (hand-written HIP
-for gfx950) in-tree with hipcc.
+"""Build liblbft_hip.so, liblbft_paramsets.so, liblbft_commit_times.so, liblbft_round_stats.so, liblbft_chain_stats.so and
+liblbft_record_hashes.so (hand-written HIP for gfx950) in-tree with hipcc.
 
 `python -m librabft_simulator_amd.build` or `build()`; the libraries are git-ignored build products.
 liblbft_paramsets.so holds the kernels of parameter-set batches (lbft_batch_create_param_sets), liblbft_commit_times.so those of
 batches that record commit times (lbft_batch_record_commit_times), liblbft_round_stats.so the kernel of lbft_batch_round_stats,
-liblbft_chain_stats.so the kernel of lbft_batch_chain_stats; liblbft_hip.so opens them beside itself on first use, so that its own code object stays as it is.
+liblbft_chain_stats.so the kernel of lbft_batch_chain_stats, liblbft_record_hashes.so the kernel of lbft_batch_chain_record_hashes;
+liblbft_hip.so opens them beside itself on first use, so that its own code object stays as it is.
 """
 import os
 import shutil
@@ -14,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc", "lbft_hip.hip")
 DEPS = [SRC] + [os.path.join(HERE, "csrc", f) for f in ("lbft_core.h", "lbft_math.h", "lbft_tables.h", "lbft_save_node.h", "lbft_launch.h", "lbft_plan.h",
                                                          "lbft_paramsets.h", "lbft_commit_times.h", "lbft_commit_timeline.h", "lbft_round_stats.h",
-                                                         "lbft_round_timeline.h", "lbft_chain_stats.h", "lbft_group_stats.h", "lbft_node_ops.h", "lbft_run_body.h")] + [
+                                                         "lbft_round_timeline.h", "lbft_chain_stats.h", "lbft_record_hashes.h", "lbft_group_stats.h", "lbft_node_ops.h", "lbft_run_body.h")] + [
     os.path.join(HERE, "..", "include", "lbft.h")]
 OUT = os.path.join(HERE, "liblbft_hip.so")
 PS_SRC = os.path.join(HERE, "csrc", "lbft_paramsets.hip")
@@ -37,7 +38,13 @@ CS_DEPS = [CS_SRC] + [os.path.join(HERE, "csrc", f) for f in ("lbft_core.h", "lb
                                                                "lbft_group_stats.h")] + [
     os.path.join(HERE, "..", "include", "lbft.h")]
 CS_OUT = os.path.join(HERE, "liblbft_chain_stats.so")
-LIBS = ((SRC, OUT, DEPS), (PS_SRC, PS_OUT, PS_DEPS), (CT_SRC, CT_OUT, CT_DEPS), (RS_SRC, RS_OUT, RS_DEPS), (CS_SRC, CS_OUT, CS_DEPS))
+RH_SRC = os.path.join(HERE, "csrc", "lbft_record_hashes.hip")
+RH_DEPS = [RH_SRC] + [os.path.join(HERE, "csrc", f) for f in ("lbft_core.h", "lbft_math.h", "lbft_record_hashes.h", "lbft_record_hash_rules.h",
+                                                               "lbft_chain_rules.h", "lbft_group_stats.h")] + [
+    os.path.join(HERE, "..", "include", "lbft.h")]
+RH_OUT = os.path.join(HERE, "liblbft_record_hashes.so")
+LIBS = ((SRC, OUT, DEPS), (PS_SRC, PS_OUT, PS_DEPS), (CT_SRC, CT_OUT, CT_DEPS), (RS_SRC, RS_OUT, RS_DEPS), (CS_SRC, CS_OUT, CS_DEPS),
+        (RH_SRC, RH_OUT, RH_DEPS))
 
 # -ffp-contract=off: Rust never fuses; every fused multiply-add in lbft_math.h is explicit.
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wno-unused-value"]
@@ -116,7 +123,7 @@ def is_stale():
 
 
 def build(force=False, verbose=False):
-    """The five libraries, each with exactly HIPCC_FLAGS (they compile in parallel)."""
+    """The six libraries, each with exactly HIPCC_FLAGS (they compile in parallel)."""
     jobs = [(src, out) for src, out, deps in LIBS if force or _stale(out, deps)]
     procs = []
     for src, out in jobs:

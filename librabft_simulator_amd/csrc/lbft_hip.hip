@@ -27,6 +27,7 @@
 #include "lbft_commit_timeline.h"
 #include "lbft_round_stats.h"
 #include "lbft_chain_stats.h"
+#include "lbft_record_hashes.h"
 #include "lbft_round_timeline.h"
 
 using namespace lbft;
@@ -1467,6 +1468,56 @@ int lbft_batch_committed_record_hashes(const lbft_batch* b, size_t inst, uint32_
   if (e != hipSuccess) return hip_fail(e, "lbft_batch_committed_record_hashes");
   for (size_t i = 0; i < k; i++)
     out[i] = lbft_record_hash{h[4 * i], h[4 * i + 1], h[4 * i + 2], (uint32_t)h[4 * i + 3], (uint32_t)(h[4 * i + 3] >> 32)};
+  return LBFT_OK;
+}
+
+// ---- record hashes of every committed chain (lbft_batch_chain_record_hashes) ----
+// The kernel lives in liblbft_record_hashes.so (lbft_record_hashes.hip), opened beside this library on first use, like the other side
+// libraries.
+static lbft_rh_chain_fn g_rh_chain = nullptr;
+static int load_record_hashes_lib() { return load_side_lib(LBFT_RECORD_HASHES_LIB, "record hashes of whole batches", {{"lbft_rh_launch_chain", (void**)&g_rh_chain}}); }
+
+// Every instance's chain hashed once on the device (lbft_k_rh_chain).  Arguments are checked before the first HIP call; the call changes
+// no state of the batch.  The heads and prefix counts of the whole batch stay on the device until the end; the entries go through one
+// temporary buffer of at most LBFT_RH_TEMP_BYTES, a chunk of instances at a time, zeroed, filled and copied back on the batch's stream.
+int lbft_batch_chain_record_hashes(const lbft_batch* b, lbft_record_hash* out, size_t cap_per_instance, lbft_chain_head* heads, uint32_t* node_prefix) {
+  if (!b || !heads) { g_err = "NULL argument"; return LBFT_ERR_INVALID; }
+  if (out && cap_per_instance == 0) { g_err = "cap_per_instance of 0 with an output array"; return LBFT_ERR_INVALID; }
+  if (!b->ran) { g_err = "run the batch first"; return LBFT_ERR_STATE; }
+  int rc = load_record_hashes_lib();
+  if (rc != LBFT_OK) return rc;
+  HIP_TRY(hipSetDevice(b->device));
+  const size_t m = b->m, n = b->p.n;
+  // (no chain is longer than the log capacity: the device rows are that wide at most, what lies beyond them in `out` is zeroed here)
+  const size_t capd = out ? std::min<size_t>(cap_per_instance, b->p.lcap) : 0;
+  const size_t row_bytes = capd * sizeof(lbft_record_hash);
+  const size_t chunk = out ? std::min(m, std::max<size_t>(1, LBFT_RH_TEMP_BYTES / row_bytes)) : m;
+  struct Temp {
+    void* d[3] = {nullptr, nullptr, nullptr};
+    ~Temp() { for (void* q : d) if (q) hipFree(q); }
+  } t;
+  hipError_t e = hipMalloc(&t.d[0], m * sizeof(lbft_chain_head));
+  if (e == hipSuccess && node_prefix) e = hipMalloc(&t.d[1], m * n * sizeof(u32));
+  if (e == hipSuccess && out) e = hipMalloc(&t.d[2], chunk * row_bytes);
+  lbft_chain_head* d_heads = static_cast<lbft_chain_head*>(t.d[0]);
+  u32* d_prefix = static_cast<u32*>(t.d[1]);
+  lbft_record_hash* d_out = static_cast<lbft_record_hash*>(t.d[2]);
+  if (e == hipSuccess) e = hipMemsetAsync(d_heads, 0, m * sizeof(lbft_chain_head), b->stream);
+  if (e == hipSuccess && node_prefix) e = hipMemsetAsync(d_prefix, 0, m * n * sizeof(u32), b->stream);
+  if (out && cap_per_instance > capd) memset(out, 0, m * cap_per_instance * sizeof(lbft_record_hash));
+  for (size_t i0 = 0; i0 < m && e == hipSuccess; i0 += chunk) {
+    const size_t cnt = std::min(chunk, m - i0);
+    if (out) e = hipMemsetAsync(d_out, 0, cnt * row_bytes, b->stream);
+    if (e == hipSuccess) e = g_rh_chain(&b->p, b->d_state, (u32)i0, (u32)cnt, d_out, (u32)capd, d_heads, d_prefix, b->stream);
+    if (e == hipSuccess && out)
+      e = hipMemcpy2DAsync(out + i0 * cap_per_instance, cap_per_instance * sizeof(lbft_record_hash), d_out, row_bytes, row_bytes, cnt,
+                           hipMemcpyDeviceToHost, b->stream);
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(heads, d_heads, m * sizeof(lbft_chain_head), hipMemcpyDeviceToHost, b->stream);
+  if (e == hipSuccess && node_prefix) e = hipMemcpyAsync(node_prefix, d_prefix, m * n * sizeof(u32), hipMemcpyDeviceToHost, b->stream);
+  hipError_t es = hipStreamSynchronize(b->stream);  // (also after an error: nothing of this call is in flight when its buffers are freed)
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return hip_fail(e, "lbft_batch_chain_record_hashes");
   return LBFT_OK;
 }
 

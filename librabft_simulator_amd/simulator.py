@@ -18,7 +18,7 @@ from collections import namedtuple
 import numpy as np
 
 from . import _lib
-from ._lib import COMMIT_DTYPE, RECORD_HASH_DTYPE, LbftActions, LbftConfig, LbftCounters, LbftError, LbftNodeView, check
+from ._lib import CHAIN_HEAD_DTYPE, COMMIT_DTYPE, RECORD_HASH_DTYPE, LbftActions, LbftConfig, LbftCounters, LbftError, LbftNodeView, check
 
 Command = namedtuple("Command", ["proposer", "index"])  # simulated_context.rs:31-35
 Author = int
@@ -272,6 +272,34 @@ class BatchResult:
         ln = C.c_size_t()
         check(_lib.lib().lbft_batch_committed_record_hashes(self._sim._h, instance, node, out.ctypes.data, n, C.byref(ln)))
         return out[:n]
+
+    def chain_record_hashes(self, cap=None):
+        """The record hashes of every instance's committed chain in one device call (lbft_batch_chain_record_hashes):
+        ``(entries, heads, node_prefix)``.  An instance's chain is the log of its reference node, the lowest-numbered node with the most
+        commits.  ``entries[instance, k]`` (RECORD_HASH_DTYPE) is entry k of ``committed_record_hashes(instance, ref_node)``, zero at and
+        past the chain's length; ``heads[instance]`` (CHAIN_HEAD_DTYPE) the last entry with the chain's ``length`` and ``ref_node`` (all
+        zero for an empty chain); ``node_prefix[instance, node]`` the number of leading entries of that node's history that are the
+        chain's: where it equals ``commit_counts``, ``committed_record_hashes(instance, node)`` is ``entries[instance, :count]``.
+        Instances with a fault are skipped (zeros).  ``cap=None``: as many entries as the longest chain has (at least 1)."""
+        if cap is None:
+            cap = int(self.commit_counts.max()) if self._sim.num_instances else 0
+            cap = max(cap, 1)
+        cap = int(cap)
+        if cap < 1:
+            raise ValueError("cap must be at least 1 (chain_heads() gives the heads alone)")
+        m, n = self._sim.num_instances, self._sim.num_nodes
+        entries = np.zeros((m, cap), dtype=RECORD_HASH_DTYPE)
+        heads = np.zeros(m, dtype=CHAIN_HEAD_DTYPE)
+        prefix = np.zeros((m, n), dtype=np.uint32)
+        check(_lib.lib().lbft_batch_chain_record_hashes(self._sim._h, entries.ctypes.data, cap, heads.ctypes.data, prefix.ctypes.data))
+        return entries, heads, prefix
+
+    def chain_heads(self):
+        """``heads`` of ``chain_record_hashes`` alone: 40 bytes per instance, whose ``qc_hash`` -- the hash of the last
+        QuorumCertificate_ of the chain -- commits to every block, state and vote below it."""
+        heads = np.zeros(self._sim.num_instances, dtype=CHAIN_HEAD_DTYPE)
+        check(_lib.lib().lbft_batch_chain_record_hashes(self._sim._h, None, 0, heads.ctypes.data, None))
+        return heads
 
     def save_node(self, instance, node):
         """ConsensusNode::save_node (librabft-v2/src/node.rs:233-238): bincode image of the node's NodeState (bytes), HashMaps in
