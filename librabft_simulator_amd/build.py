@@ -1,50 +1,61 @@
-"""Build liblbft_hip.so, liblbft_paramsets.so, liblbft_commit_times.so, liblbft_round_stats.so, liblbft_chain_stats.so and
-liblbft_record_hashes.so (hand-written HIP for gfx950) in-tree with hipcc.
-
-`python -m librabft_simulator_amd.build` or `build()`; the libraries are git-ignored build products.
-liblbft_paramsets.so holds the kernels of parameter-set batches (lbft_batch_create_param_sets), liblbft_commit_times.so those of
-batches that record commit times (lbft_batch_record_commit_times), liblbft_round_stats.so the kernel of lbft_batch_round_stats,
-liblbft_chain_stats.so the kernel of lbft_batch_chain_stats, liblbft_record_hashes.so the kernel of lbft_batch_chain_record_hashes;
-liblbft_hip.so opens them beside itself on first use, so that its own code object stays as it is.
+"""Build the HIP libraries (hand-written HIP for gfx950) in-tree with hipcc: `python -m librabft_simulator_amd.build` or `build()`.
+The libraries are git-ignored build products; TABLE below names them, and what each depends on is read from its sources:
 """
+import collections
 import os
+import re
 import shutil
 import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "csrc", "lbft_hip.hip")
-DEPS = [SRC] + [os.path.join(HERE, "csrc", f) for f in ("lbft_core.h", "lbft_math.h", "lbft_tables.h", "lbft_save_node.h", "lbft_launch.h", "lbft_plan.h",
-                                                         "lbft_paramsets.h", "lbft_commit_times.h", "lbft_commit_timeline.h", "lbft_round_stats.h",
-                                                         "lbft_round_timeline.h", "lbft_chain_stats.h", "lbft_record_hashes.h", "lbft_group_stats.h", "lbft_node_ops.h", "lbft_run_body.h")] + [
-    os.path.join(HERE, "..", "include", "lbft.h")]
-OUT = os.path.join(HERE, "liblbft_hip.so")
-PS_SRC = os.path.join(HERE, "csrc", "lbft_paramsets.hip")
-PS_DEPS = [PS_SRC] + [os.path.join(HERE, "csrc", f) for f in ("lbft_core.h", "lbft_math.h", "lbft_launch.h", "lbft_paramsets.h",
-                                                               "lbft_run_body.h")] + [
-    os.path.join(HERE, "..", "include", "lbft.h")]
-PS_OUT = os.path.join(HERE, "liblbft_paramsets.so")
-CT_SRC = os.path.join(HERE, "csrc", "lbft_commit_times.hip")
-CT_DEPS = [CT_SRC] + [os.path.join(HERE, "csrc", f) for f in ("lbft_core.h", "lbft_math.h", "lbft_launch.h", "lbft_commit_times.h",
-                                                               "lbft_commit_timeline.h", "lbft_group_stats.h", "lbft_run_body.h")] + [
-    os.path.join(HERE, "..", "include", "lbft.h")]
-CT_OUT = os.path.join(HERE, "liblbft_commit_times.so")
-RS_SRC = os.path.join(HERE, "csrc", "lbft_round_stats.hip")
-RS_DEPS = [RS_SRC] + [os.path.join(HERE, "csrc", f) for f in ("lbft_core.h", "lbft_math.h", "lbft_round_stats.h", "lbft_round_timeline.h",
-                                                               "lbft_group_stats.h")] + [
-    os.path.join(HERE, "..", "include", "lbft.h")]
-RS_OUT = os.path.join(HERE, "liblbft_round_stats.so")
-CS_SRC = os.path.join(HERE, "csrc", "lbft_chain_stats.hip")
-CS_DEPS = [CS_SRC] + [os.path.join(HERE, "csrc", f) for f in ("lbft_core.h", "lbft_math.h", "lbft_chain_stats.h", "lbft_chain_rules.h",
-                                                               "lbft_group_stats.h")] + [
-    os.path.join(HERE, "..", "include", "lbft.h")]
-CS_OUT = os.path.join(HERE, "liblbft_chain_stats.so")
-RH_SRC = os.path.join(HERE, "csrc", "lbft_record_hashes.hip")
-RH_DEPS = [RH_SRC] + [os.path.join(HERE, "csrc", f) for f in ("lbft_core.h", "lbft_math.h", "lbft_record_hashes.h", "lbft_record_hash_rules.h",
-                                                               "lbft_chain_rules.h", "lbft_group_stats.h")] + [
-    os.path.join(HERE, "..", "include", "lbft.h")]
-RH_OUT = os.path.join(HERE, "liblbft_record_hashes.so")
-LIBS = ((SRC, OUT, DEPS), (PS_SRC, PS_OUT, PS_DEPS), (CT_SRC, CT_OUT, CT_DEPS), (RS_SRC, RS_OUT, RS_DEPS), (CS_SRC, CS_OUT, CS_DEPS),
-        (RH_SRC, RH_OUT, RH_DEPS))
+
+# One library: its tag, source and output file, the prefix of its kernels' names (None: the main library, which holds every other
+# kernel), the launchers it exports for liblbft_hip.so to look up (load_side_lib in lbft_hip.hip), and what it holds in one line.
+Lib = collections.namedtuple("Lib", "tag src out prefix launchers holds")
+
+
+def _lib(tag, prefix, launchers, holds):
+    return Lib(tag, os.path.join(HERE, "csrc", "lbft_%s.hip" % tag), os.path.join(HERE, "liblbft_%s.so" % tag), prefix, launchers, holds)
+
+
+TABLE = (
+    _lib("hip", None, (), "the C ABI of include/lbft.h and its kernels; opens the others beside itself on first use, so that its own "
+                          "code object stays as it is"),
+    _lib("paramsets", "lbft_k_ps_", ("lbft_ps_launch_init", "lbft_ps_launch_run"),
+         "the kernels of parameter-set batches (lbft_batch_create_param_sets)"),
+    _lib("commit_times", "lbft_k_ct_", ("lbft_ct_launch_run", "lbft_ct_launch_histogram", "lbft_ct_launch_timeline"),
+         "the kernels of batches that record commit times (lbft_batch_record_commit_times)"),
+    _lib("round_stats", "lbft_k_rs_", ("lbft_rs_launch_rounds",), "the kernel of lbft_batch_round_stats"),
+    _lib("chain_stats", "lbft_k_cs_", ("lbft_cs_launch_chain",), "the kernel of lbft_batch_chain_stats"),
+    _lib("record_hashes", "lbft_k_rh_", ("lbft_rh_launch_chain",), "the kernel of lbft_batch_chain_record_hashes"),
+)
+__doc__ = (__doc__ or "") + "".join("%s: %s.\n" % (os.path.basename(lib.out), lib.holds) for lib in TABLE)
+
+_INCLUDE = re.compile(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', re.M)
+
+
+def include_closure(src):
+    """`src` and every file its quoted #include lines reach, each resolved relative to the file that includes it.  An include
+    that does not resolve raises: a header nobody watches would let a stale library be served."""
+    seen, todo = [], [os.path.normpath(src)]
+    while todo:
+        path = todo.pop(0)
+        if path in seen:
+            continue
+        seen.append(path)
+        with open(path) as f:
+            text = f.read()
+        for inc in _INCLUDE.findall(text):
+            dep = os.path.normpath(os.path.join(os.path.dirname(path), inc))
+            if not os.path.isfile(dep):
+                raise FileNotFoundError('%s: #include "%s" does not resolve (%s)' % (path, inc, dep))
+            todo.append(dep)
+    return seen
+
+
+LIBS = tuple((lib.src, lib.out, include_closure(lib.src)) for lib in TABLE)
+(SRC, OUT, DEPS), (PS_SRC, PS_OUT, PS_DEPS), (CT_SRC, CT_OUT, CT_DEPS), (RS_SRC, RS_OUT, RS_DEPS), (CS_SRC, CS_OUT, CS_DEPS), \
+    (RH_SRC, RH_OUT, RH_DEPS) = LIBS
 
 # -ffp-contract=off: Rust never fuses; every fused multiply-add in lbft_math.h is explicit.
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wno-unused-value"]
@@ -123,7 +134,7 @@ def is_stale():
 
 
 def build(force=False, verbose=False):
-    """The six libraries, each with exactly HIPCC_FLAGS (they compile in parallel)."""
+    """The libraries of TABLE, each with exactly HIPCC_FLAGS (they compile in parallel)."""
     jobs = [(src, out) for src, out, deps in LIBS if force or _stale(out, deps)]
     procs = []
     for src, out in jobs:

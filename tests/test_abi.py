@@ -7,15 +7,9 @@ import re
 import numpy as np
 import pytest
 
+from support import hiplib  # noqa: F401
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def hiplib():
-    from librabft_simulator_amd import build
-    build.build()
-    from librabft_simulator_amd import _lib
-    return _lib
 
 
 def test_header_symbols_are_exported(hiplib):
@@ -177,6 +171,75 @@ def test_built_kernels_match_the_committed_codegen_manifest(hiplib):
     toolchain = committed["hipcc"] != built["hipcc"]
     assert not d, ("the built kernels deviate from tests/golden/kernel_manifest.json%s:\n  %s\nre-measure (tools/gpu_configs_profile.sh) and regenerate it in "
                    "the same commit: python tools/kernel_manifest.py --write" % (" (DIFFERENT hipcc: every kernel needs re-measuring)" if toolchain else "", "\n  ".join(d)))
+
+
+def test_launchers_are_exported_by_their_own_library_alone(hiplib):
+    """build.TABLE: every launcher liblbft_hip.so looks up lives in its side library and in none of the other five."""
+    from librabft_simulator_amd import build
+    assert [lib.tag for lib in build.TABLE] == ["hip", "paramsets", "commit_times", "round_stats", "chain_stats", "record_hashes"]
+    assert build.TABLE[0].out == build.OUT and not build.TABLE[0].launchers and all(lib.launchers for lib in build.TABLE[1:])
+    assert build.LIBS == tuple((lib.src, lib.out, build.include_closure(lib.src)) for lib in build.TABLE)
+    loaded = {lib.tag: ctypes.CDLL(lib.out) for lib in build.TABLE}
+    for lib in build.TABLE:
+        for name in lib.launchers:
+            for tag, raw in loaded.items():
+                assert hasattr(raw, name) == (tag == lib.tag), (name, tag)
+
+
+@pytest.mark.skipif(not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf"), reason="needs the ROCm LLVM binutils")
+def test_side_kernels_carry_their_prefix_and_stay_out_of_every_other_library(hiplib):
+    from librabft_simulator_amd import build
+    kernels = {lib.tag: sorted(_kernel_metadata(lib.out)) for lib in build.TABLE}
+    for lib in build.TABLE[1:]:
+        assert kernels[lib.tag] and all(lib.prefix in k for k in kernels[lib.tag]), (lib.tag, kernels[lib.tag])
+        for tag, names in kernels.items():
+            assert tag == lib.tag or not any(lib.prefix in k for k in names), (lib.prefix, tag, names)
+
+
+def test_table_names_the_files_and_launchers_the_host_code_opens():
+    """The Python table cannot drift from csrc: the side libraries' file names are the LBFT_*_LIB macros of their headers, the launchers
+    the strings lbft_hip.hip passes to load_side_lib."""
+    from librabft_simulator_amd import build
+    csrc = os.path.join(ROOT, "librabft_simulator_amd", "csrc")
+    macros = {}
+    for f in sorted(os.listdir(csrc)):
+        macros.update(re.findall(r'^#define (LBFT_\w+_LIB) "([^"]+)"', open(os.path.join(csrc, f)).read(), re.M))
+    table = {os.path.basename(lib.out): lib.launchers for lib in build.TABLE[1:]}
+    assert sorted(macros.values()) == sorted(table) and len(macros) == 5, macros
+    calls = re.findall(r'load_side_lib\((LBFT_\w+_LIB),\s*"[^"]*",\s*\{(.*?)\}\);', open(build.SRC).read(), re.S)
+    opened = {macros[macro]: tuple(re.findall(r'\{"(\w+)"', body)) for macro, body in calls}
+    assert len(calls) == 5 and opened == table, (opened, table)
+    for lib in build.TABLE:
+        assert os.path.dirname(lib.src) == csrc and os.path.isfile(lib.src), lib.src
+
+
+def test_a_newer_header_makes_exactly_the_libraries_that_include_it_stale(tmp_path):
+    """On a copy of the sources with built libraries older than all of them: one header at a time made newer."""
+    import shutil
+    from librabft_simulator_amd import build
+    shutil.copytree(os.path.join(ROOT, "librabft_simulator_amd", "csrc"), tmp_path / "librabft_simulator_amd" / "csrc")
+    shutil.copytree(os.path.join(ROOT, "include"), tmp_path / "include")
+    libs = {}
+    for lib in build.TABLE:
+        deps = build.include_closure(str(tmp_path / os.path.relpath(lib.src, ROOT)))
+        out = str(tmp_path / os.path.basename(lib.out))
+        assert build._stale(out, deps)  # not built yet
+        open(out, "wb").close()
+        os.utime(out, (1000, 1000))
+        libs[lib.tag] = (out, deps)
+        assert [os.path.relpath(d, tmp_path) for d in deps] == [os.path.relpath(d, ROOT) for d in build.LIBS[build.TABLE.index(lib)][2]]
+    files = sorted(set(d for _out, deps in libs.values() for d in deps))
+    for f in files:
+        os.utime(f, (900, 900))
+    assert not any(build._stale(out, deps) for out, deps in libs.values())
+    for f in files:
+        os.utime(f, (1100, 1100))
+        assert {tag: build._stale(out, deps) for tag, (out, deps) in libs.items()} == {tag: f in deps for tag, (_out, deps) in libs.items()}, f
+        os.utime(f, (900, 900))
+    # an include that does not resolve is an error, not a dependency nobody watches
+    (tmp_path / "lost.hip").write_text('#include "include/lbft.h"\n  #  include "no_such_header.h"\n')
+    with pytest.raises(FileNotFoundError):
+        build.include_closure(str(tmp_path / "lost.hip"))
 
 
 def test_kernel_hash_reads_the_code_object(hiplib):

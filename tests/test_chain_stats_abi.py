@@ -11,17 +11,10 @@ import sys
 import numpy as np
 import pytest
 
+from support import Stub, hiplib, other_libs  # noqa: F401
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "lbft_batch_chain_stats"
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-
-@pytest.fixture(scope="module")
-def hiplib():
-    from librabft_simulator_amd import build
-    build.build()
-    from librabft_simulator_amd import _lib
-    return _lib
 
 
 def test_chain_stats_symbol_is_declared_exported_and_bound(hiplib):
@@ -35,7 +28,7 @@ def test_chain_stats_symbol_is_declared_exported_and_bound(hiplib):
     assert re.search(r"#define LBFT_CHAIN_STATS 24\b", header) and hiplib.CHAIN_STATS == 24 == ref.CHAIN_STATS == 4 * ref.FAMILIES
     assert (build.CS_SRC, build.CS_OUT, build.CS_DEPS) in build.LIBS and os.path.basename(build.CS_OUT) == "liblbft_chain_stats.so"
     assert hasattr(ctypes.CDLL(build.CS_OUT), "lbft_cs_launch_chain")
-    for other in (hiplib.LIB_PATH, build.PS_OUT, build.CT_OUT, build.RS_OUT):
+    for other in (hiplib.LIB_PATH, *other_libs("chain_stats")):
         assert not hasattr(ctypes.CDLL(other), "lbft_cs_launch_chain"), other
     csrc = os.path.join(ROOT, "librabft_simulator_amd", "csrc")
     assert "lbft_cs_chain_fn" in open(os.path.join(csrc, "lbft_chain_stats.h")).read()
@@ -56,10 +49,6 @@ def test_arguments_are_refused_without_a_gpu(hiplib):
         assert L.lbft_batch_chain_stats(None, width, bins, *p) == hiplib.LBFT_ERR_INVALID
         assert L.lbft_batch_chain_stats(None, width, bins, None, None, None) == hiplib.LBFT_ERR_INVALID
     assert not hist.any() and not authors.any() and not stats.any()
-
-
-class Stub:  # (no batch behind it: the checks run before any library call)
-    _h, _max_clock, param_sets, num_instances, num_nodes = None, 1000, None, 1, 4
 
 
 def test_python_methods_refuse_bad_arguments_before_the_device():
@@ -89,7 +78,7 @@ def test_chain_stats_kernel_is_in_its_own_library_without_scratch(hiplib, capsys
     assert mine[0]["private_segment_fixed_size"] == 0 and mine[0]["vgpr_spill_count"] == 0, mine[0]
     assert mine[0]["vgpr_count"] <= 128 and mine[0]["group_segment_fixed_size"] <= 32 * 1024, mine[0]  # four wavefronts per SIMD, four workgroups per CU
     assert not any("lbft_k_run" in k or "lbft_k_ct_" in k or "lbft_k_ps_" in k or "lbft_k_rs_" in k for k in cs), sorted(cs)
-    for other in (build.OUT, build.PS_OUT, build.CT_OUT, build.RS_OUT):
+    for other in other_libs("chain_stats"):
         assert not any("lbft_k_cs_" in k for k in _kernel_metadata(other)), other
     # the register tool lists it
     sys.path.insert(0, os.path.join(ROOT, "tools"))

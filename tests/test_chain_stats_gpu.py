@@ -13,46 +13,13 @@ import sys
 import numpy as np
 import pytest
 
+import chain_stats_reference as ref
+from support import amd, binning, oracle_cfg, plain, same  # noqa: F401
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import chain_stats_reference as ref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 LOG_OVERFLOW = 1 << 3  # LBFT_FAULT_LOG_OVERFLOW
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import librabft_simulator_amd as L
-    L.lib()
-    return L
-
-
-def oracle_cfg(oc, n, ps, **kw):
-    """The oracle's configuration of parameter set `ps`; kw: quirks, voting_rights, equivocate_every, commands_per_epoch, rights_rotation."""
-    d, nc = ps.network_delay, ps.node_config
-    part = ps.partition or (0, 0, 0)
-    return oc.make_config(num_nodes=n, mean=d.mean, variance=d.variance, delay_model=d.model, uniform_lo=d.lo, uniform_hi=d.hi,
-                          target_commit_interval=nc.target_commit_interval, delta=nc.delta, gamma=nc.gamma, lambda_=nc.lambda_,
-                          drop_per_million=ps.drop_per_million, partition_size=part[0], partition_start=part[1], partition_end=part[2],
-                          math_mode=1, **kw)
-
-
-def plain(amd, seeds, n, ps, **kw):
-    return amd.BatchSimulator.new(np.asarray(seeds, dtype=np.uint64), n, ps.network_delay, ps.node_config, drop_per_million=ps.drop_per_million,
-                                  partition=ps.partition, **kw)
-
-
-def binning(max_clock, width, bins):
-    """latency_histogram's defaults: width 1 up to 65 536 bins, above that the smallest width that fits."""
-    span = max_clock + 1
-    if width is None:
-        width = -(-span // bins) if bins else max(1, -(-span // (1 << 16)))
-    if bins is None:
-        bins = -(-span // width)
-    return width, bins
 
 
 def check(res, want, max_clock, binnings=((None, None),), set_of=None, groups=1, faults=None, log_capacity=None):
@@ -74,10 +41,6 @@ def check(res, want, max_clock, binnings=((None, None),), set_of=None, groups=1,
         assert (hist.sum(axis=1) == stats[:, 0]).all() and (authors.sum(axis=1) == stats[:, 4 * ref.LENGTH + 1]).all()
     assert all(row["agreement"] is True for row in res.chain_by_param_set())
     return fam, authors_o, hist, authors, stats
-
-
-def same(a, b):
-    return len(a) == len(b) and all(x.shape == y.shape and (x == y).all() for x, y in zip(a, b))
 
 
 def arrays(res):

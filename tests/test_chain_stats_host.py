@@ -5,26 +5,21 @@ on logs written by hand that no run produces: this is where the audit families s
 figures of the oracle that were obtained before any of this code existed."""
 import ctypes as C
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import chain_stats_reference as ref
+from support import build_shim
 
-import chain_stats_reference as ref  # noqa: E402
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 CHUNKS = (1, 2, 7, 64)  # entries side by side in the shim's chain walk (the kernel: 64)
 
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("chn_host") / "libchn_host.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Werror", os.path.join(ROOT, "tests", "chain_stats_host.cpp"),
-                           "-o", out])
-    L = C.CDLL(out)
+    L = build_shim(tmp_path_factory.mktemp("chn_host"), "chain_stats_host.cpp", "libchn_host.so", "-Wall", "-Werror")
     vp = C.c_void_p
     L.chn_host.argtypes = [vp] * 7 + [C.c_uint32] * 8 + [vp, vp, vp]
     L.chn_host.restype = C.c_int

@@ -6,21 +6,14 @@ import argparse
 import ctypes
 import os
 import re
-import sys
 
 import numpy as np
 import pytest
 
+from support import Stub, hiplib, other_libs  # noqa: F401
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("lbft_batch_commit_series", "lbft_batch_commit_stalls")
-
-
-@pytest.fixture(scope="module")
-def hiplib():
-    from librabft_simulator_amd import build
-    build.build()
-    from librabft_simulator_amd import _lib
-    return _lib
 
 
 def test_timeline_symbols_are_declared_and_exported(hiplib):
@@ -34,8 +27,8 @@ def test_timeline_symbols_are_declared_and_exported(hiplib):
     assert re.search(r"#define LBFT_STALL_STATS 16\b", header) and hiplib.STALL_STATS == 16
     side = ctypes.CDLL(build.CT_OUT)
     assert hasattr(side, "lbft_ct_launch_timeline")
-    assert not hasattr(raw, "lbft_ct_launch_timeline")
-    assert not hasattr(ctypes.CDLL(build.PS_OUT), "lbft_ct_launch_timeline")
+    for other in (hiplib.LIB_PATH, *other_libs("commit_times")):
+        assert not hasattr(ctypes.CDLL(other), "lbft_ct_launch_timeline"), other
     assert "lbft_ct_timeline_fn" in open(os.path.join(ROOT, "librabft_simulator_amd", "csrc", "lbft_commit_times.h")).read()
 
 
@@ -51,10 +44,6 @@ def test_arguments_are_refused_without_a_gpu(hiplib):
             assert L.lbft_batch_commit_stalls(None, s, width, bins, hist.ctypes.data, stats.ctypes.data) == hiplib.LBFT_ERR_INVALID
             assert L.lbft_batch_commit_stalls(None, s, width, bins, None, None) == hiplib.LBFT_ERR_INVALID
     assert not hist.any() and not stats.any()
-
-
-class Stub:  # (no batch behind it: the checks run before any library call)
-    _h, _max_clock, param_sets, num_instances, num_nodes = None, 1000, None, 1, 4
 
 
 def test_python_methods_refuse_bad_arguments_before_the_device():
@@ -96,7 +85,6 @@ def test_since_forms():
 
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf"), reason="needs the ROCm LLVM binutils")
 def test_timeline_kernel_is_in_the_side_library_without_scratch(hiplib):
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
     from test_abi import _kernel_metadata
     from librabft_simulator_amd import build
     ct = _kernel_metadata(build.CT_OUT)
@@ -104,8 +92,8 @@ def test_timeline_kernel_is_in_the_side_library_without_scratch(hiplib):
     assert len(mine) == 1, sorted(ct)
     assert mine[0]["private_segment_fixed_size"] == 0, mine[0]
     assert not any("run0" in k or "run1" in k for k in ct if "timeline" in k)
-    assert not any("timeline" in k for k in _kernel_metadata(build.OUT))
-    assert not any("timeline" in k for k in _kernel_metadata(build.PS_OUT))
+    for other in other_libs("commit_times"):
+        assert not any("timeline" in k for k in _kernel_metadata(other)), other
 
 
 def test_grid_options():

@@ -13,33 +13,15 @@ import time
 import numpy as np
 import pytest
 
+import commit_timeline_reference as ref
+from support import amd, binning  # noqa: F401
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import commit_timeline_reference as ref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 HOST_THREADS = min(os.cpu_count() or 8, 16)
 BIG = 65536
 LOG_OVERFLOW = 1 << 3  # LBFT_FAULT_LOG_OVERFLOW
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import librabft_simulator_amd as L
-    L.lib()
-    return L
-
-
-def binning(max_clock, width, bins):
-    """latency_histogram's defaults: width 1 up to 65 536 bins, above that the smallest width that fits."""
-    span = max_clock + 1
-    if width is None:
-        width = -(-span // bins) if bins else max(1, -(-span // (1 << 16)))
-    if bins is None:
-        bins = -(-span // width)
-    return width, bins
 
 
 def check_against_numpy(res, max_clock, binnings, set_of=None, groups=1, since=None):

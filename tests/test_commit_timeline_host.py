@@ -4,26 +4,19 @@ definitions (tests/commit_timeline_reference.py) -- on drawn rows that hit every
 from the oracle for a control set and a set with a partition, where the reference alone already shows the stall and the recovery."""
 import ctypes as C
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-import commit_timeline_reference as ref  # noqa: E402
+import commit_timeline_reference as ref
+from support import build_shim
 
 THREADS = min(os.cpu_count() or 8, 16)
 
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("ctl_host") / "libctl_host.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Werror", os.path.join(ROOT, "tests", "commit_timeline_host.cpp"),
-                           "-o", out])
-    L = C.CDLL(out)
+    L = build_shim(tmp_path_factory.mktemp("ctl_host"), "commit_timeline_host.cpp", "libctl_host.so", "-Wall", "-Werror")
     vp = C.c_void_p
     L.ctl_host.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_int64, C.c_uint32, C.c_uint32, C.c_uint32,
                            vp, vp, vp]

@@ -6,21 +6,14 @@ import ctypes
 import json
 import os
 import re
-import sys
 
 import numpy as np
 import pytest
 
+from support import Stub, hiplib, other_libs  # noqa: F401
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("lbft_batch_record_commit_times", "lbft_batch_commit_times", "lbft_batch_commit_latency_histogram")
-
-
-@pytest.fixture(scope="module")
-def hiplib():
-    from librabft_simulator_amd import build
-    build.build()
-    from librabft_simulator_amd import _lib
-    return _lib
 
 
 def test_commit_time_symbols_are_declared_and_exported(hiplib):
@@ -34,7 +27,8 @@ def test_commit_time_symbols_are_declared_and_exported(hiplib):
     from librabft_simulator_amd import build
     side = ctypes.CDLL(build.CT_OUT)
     assert hasattr(side, "lbft_ct_launch_run") and hasattr(side, "lbft_ct_launch_histogram")
-    assert not hasattr(raw, "lbft_ct_launch_run")
+    for other in (hiplib.LIB_PATH, *other_libs("commit_times")):
+        assert not hasattr(ctypes.CDLL(other), "lbft_ct_launch_run"), other
 
 
 def test_arguments_are_refused_without_a_gpu(hiplib):
@@ -51,9 +45,6 @@ def test_arguments_are_refused_without_a_gpu(hiplib):
 
 def test_python_histogram_refuses_zero_bins_before_the_device():
     from librabft_simulator_amd.simulator import BatchResult
-
-    class Stub:  # (no batch behind it: the checks run before any library call)
-        _h, _max_clock, param_sets, num_instances, num_nodes = None, 1000, None, 1, 4
     res = BatchResult(Stub())
     for kw in ({"bins": 0}, {"bin_width": 0}, {"bin_width": 0, "bins": 0}, {"bins": -3}):
         with pytest.raises(ValueError):
@@ -62,7 +53,6 @@ def test_python_histogram_refuses_zero_bins_before_the_device():
 
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf"), reason="needs the ROCm LLVM binutils")
 def test_commit_time_kernels_are_a_separate_code_object_without_extra_scratch(hiplib):
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
     from test_abi import _kernel_metadata
     from librabft_simulator_amd import build
     assert os.path.exists(build.CT_OUT)
@@ -78,9 +68,9 @@ def test_commit_time_kernels_are_a_separate_code_object_without_extra_scratch(hi
     for k, v in ct.items():
         cap = run0[0] if "run0" in k else run1[0] if "run1" in k else {"private_segment_fixed_size": 0}
         assert v["private_segment_fixed_size"] <= cap["private_segment_fixed_size"], (k, v, cap)
-    # none of them went into liblbft_hip.so (or into liblbft_paramsets.so)
-    assert not any("lbft_k_ct_" in k for k in base)
-    assert not any("lbft_k_ct_" in k for k in _kernel_metadata(build.PS_OUT))
+    # none of them went into liblbft_hip.so or into another side library
+    for other in other_libs("commit_times"):
+        assert not any("lbft_k_ct_" in k for k in _kernel_metadata(other)), other
 
 
 def test_main_library_machine_code_is_unchanged(hiplib):

@@ -12,23 +12,14 @@ import sys
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import commit_times_oracle as cto
+from support import amd, oracle_cfg  # noqa: F401
 
-import commit_times_oracle as cto  # noqa: E402
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 pytestmark = pytest.mark.gpu
 HOST_THREADS = min(os.cpu_count() or 8, 16)
 BIG = 65536
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import librabft_simulator_amd as L
-    L.lib()
-    return L
 
 
 def layout_flags(sim):
@@ -36,18 +27,6 @@ def layout_flags(sim):
     out = np.zeros(8, dtype=np.uint32)
     assert _lib.lib().lbft_batch_layout(sim._h, out.ctypes.data) == 0
     return int(out[7])
-
-
-def oracle_cfg(oc, n, delay, node_config, **kw):
-    return oc.make_config(num_nodes=n, mean=delay.mean, variance=delay.variance, delay_model=delay.model, uniform_lo=delay.lo, uniform_hi=delay.hi,
-                          target_commit_interval=node_config.target_commit_interval, delta=node_config.delta, gamma=node_config.gamma,
-                          lambda_=node_config.lambda_, math_mode=1, **kw)
-
-
-def ps_oracle_cfg(oc, n, ps):
-    part = ps.partition or (0, 0, 0)
-    return oracle_cfg(oc, n, ps.network_delay, ps.node_config, drop_per_million=ps.drop_per_million, partition_size=part[0],
-                      partition_start=part[1], partition_end=part[2])
 
 
 def small_sets(amd):
@@ -79,7 +58,7 @@ def test_class0_commit_times_equal_the_oracle(amd, oracle):
     res = sim.loop_until(600)
     assert layout_flags(sim) & 0xff == 0 and layout_flags(sim) & (1 << 17) and not layout_flags(sim) & (0x3f << 10)
     ct = res.commit_times()
-    ref = cto.commit_times(oracle, oracle_cfg(oracle, 4, amd.RandomDelay.new(10.0, 4.0), amd.NodeConfig()), seeds, 600, ct.shape[2], HOST_THREADS)
+    ref = cto.commit_times(oracle, oracle_cfg(oracle, 4, amd.ParamSet(amd.RandomDelay.new(10.0, 4.0))), seeds, 600, ct.shape[2], HOST_THREADS)
     assert (res.faults == 0).all()
     assert (ct == ref).all()
     assert ((ct >= 0).sum(axis=2) == res.commit_counts).all()
@@ -92,7 +71,7 @@ def test_class1_commit_times_equal_the_oracle(amd, oracle):
     res = sim.loop_until(300)
     assert layout_flags(sim) & 0xff == 1 and layout_flags(sim) & (1 << 17) and not layout_flags(sim) & (0x3f << 10)
     ct = res.commit_times()
-    ref = cto.commit_times(oracle, oracle_cfg(oracle, 16, amd.RandomDelay.new(10.0, 4.0), amd.NodeConfig(), drop_per_million=20000),
+    ref = cto.commit_times(oracle, oracle_cfg(oracle, 16, amd.ParamSet(amd.RandomDelay.new(10.0, 4.0), drop_per_million=20000)),
                            seeds, 300, ct.shape[2], HOST_THREADS)
     assert (res.faults == 0).all()
     assert (ct == ref).all()
@@ -108,7 +87,7 @@ def test_param_set_commit_times_equal_the_oracle(amd, oracle):
     res = sim.loop_until(500)
     assert layout_flags(sim) & (1 << 16) and layout_flags(sim) & (1 << 17)
     ct = res.commit_times()
-    ref = cto.param_set_commit_times(oracle, [ps_oracle_cfg(oracle, 4, ps) for ps in sets], set_of, seeds, 500, ct.shape[2], HOST_THREADS)
+    ref = cto.param_set_commit_times(oracle, [oracle_cfg(oracle, 4, ps) for ps in sets], set_of, seeds, 500, ct.shape[2], HOST_THREADS)
     assert (res.faults == 0).all()
     assert (ct == ref).all()
     sim.close()
@@ -118,7 +97,7 @@ def test_big_batch_sample_equals_the_oracle(amd, oracle, big):
     seeds, _, rt, _, _ = big
     ct = rt.commit_times()
     idx = np.arange(0, BIG, BIG // 256)
-    ref = cto.commit_times(oracle, oracle_cfg(oracle, 4, amd.RandomDelay.new(10.0, 4.0), amd.NodeConfig()), seeds[idx], 1000, ct.shape[2],
+    ref = cto.commit_times(oracle, oracle_cfg(oracle, 4, amd.ParamSet(amd.RandomDelay.new(10.0, 4.0))), seeds[idx], 1000, ct.shape[2],
                            HOST_THREADS)
     assert (ct[idx] == ref).all()
 
@@ -404,7 +383,7 @@ def test_mid_class_param_set_steps_and_checkpoint(amd, oracle, tmp_path):
     rs = straight.loop_until(mc)
     assert layout_flags(straight) & 0xff == 1 and layout_flags(straight) & (3 << 16) == 3 << 16
     want = rs.commit_times()
-    ref = cto.param_set_commit_times(oracle, [ps_oracle_cfg(oracle, n, ps) for ps in sets], set_of, seeds, mc, want.shape[2], HOST_THREADS)
+    ref = cto.param_set_commit_times(oracle, [oracle_cfg(oracle, n, ps) for ps in sets], set_of, seeds, mc, want.shape[2], HOST_THREADS)
     assert (want == ref).all() and (want >= 0).any()
     a = mk()
     left, _ = a.run_steps(mc, 60)

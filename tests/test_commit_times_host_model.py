@@ -5,16 +5,12 @@ nodes, both delay models, equivocators, loss and partitions, quirks 0 and 3 with
 rights, and parameter-set batches with mixed sets."""
 import ctypes as C
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-import commit_times_oracle as cto  # noqa: E402
+import commit_times_oracle as cto
+from support import build_shim, set_oracle_cfg
 
 THREADS = min(os.cpu_count() or 8, 16)
 
@@ -26,10 +22,7 @@ def harness(tmp_path_factory):
 
 def load_harness(directory):
     """Compiles the host model into `directory` and binds it."""
-    out = str(directory / "libct_hostmodel.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-pthread", "-w",
-                           os.path.join(ROOT, "tests", "commit_times_host_model.cpp"), "-o", out])
-    L = C.CDLL(out)
+    L = build_shim(directory, "commit_times_host_model.cpp", "libct_hostmodel.so", "-ffp-contract=off", "-pthread", "-w")
     vp = C.c_void_p
     L.ct_hostmodel_run.argtypes = [vp, vp, C.c_uint32, vp, vp, C.c_size_t, C.c_int64, C.c_uint32, vp, vp, vp, vp, C.c_size_t, vp, C.c_uint32]
     L.ct_hostmodel_run.restype = C.c_int
@@ -51,14 +44,6 @@ def run_host(L, base, sets, set_of, seeds, max_clock, cap, state_fill=0):
                              ct.ctypes.data, hist.ctypes.data, st.ctypes.data, cap, faults.ctypes.data, state_fill)
     assert cls >= 0, cls
     return cls, {"commit_counts": cc, "commit_times": ct, "histories": hist, "startup_times": st, "faults": faults}
-
-
-def oracle_cfg(oc, base, s, rights):
-    return oc.make_config(num_nodes=base.num_nodes, mean=s.mean, variance=s.variance, delay_model=base.delay_model, uniform_lo=s.uniform_lo,
-                          uniform_hi=s.uniform_hi, commands_per_epoch=base.commands_per_epoch, target_commit_interval=s.target_commit_interval,
-                          delta=s.delta, gamma=s.gamma, lambda_=s.lambda_, quirks=base.quirks, equivocate_every=base.equivocate_every,
-                          drop_per_million=s.drop_per_million, partition_size=s.partition_size, partition_start=s.partition_start,
-                          partition_end=s.partition_end, voting_rights=rights)
 
 
 def draw(rng, n, n_sets, small=False):
@@ -121,7 +106,7 @@ def test_commit_times_equal_the_oracle(harness, oracle):
         cap = max_clock // 2 + 64
         cls, got = run_host(harness, base, sets, set_of, seeds, max_clock, cap)
         classes.add((cls, bool(n_sets)))
-        configs = [oracle_cfg(oracle, base, s, rights) for s in all_sets]
+        configs = [set_oracle_cfg(oracle, base, s, rights) for s in all_sets]
         ref_ct = cto.param_set_commit_times(oracle, configs, set_of, seeds, max_clock, cap, THREADS)
         ok = got["faults"] == 0  # (capacity faults are the host build's, not the protocol's: compared where none was raised)
         assert ok.sum() >= m // 2, (case, got["faults"])

@@ -14,6 +14,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import test_commit_times_host_model as ctm  # noqa: E402
 import test_node_level_fuzz as nlf  # noqa: E402
 import test_param_sets_host_model as psm  # noqa: E402
+from support import set_oracle_cfg  # noqa: E402
 from test_fuzz_model import draw_caps, draw_config, draw_large_caps, draw_large_config  # noqa: E402
 from test_host_model import round_switch_rows  # noqa: E402
 from test_save_node import EPOCH_CASES  # noqa: E402
@@ -291,7 +292,7 @@ def test_commit_time_model_on_dirty_state(oracle, tmp_path_factory):
         classes.add((cls, bool(n_sets)))
         assert not clean["faults"].any()
         for i in range(m):  # the oracle's histories and the commit times derived from fresh oracle runs
-            cfg = ctm.oracle_cfg(oracle, base, all_sets[set_of[i]], rights)
+            cfg = set_oracle_cfg(oracle, base, all_sets[set_of[i]], rights)
             ref = oracle.run_batch(cfg, seeds[i:i + 1], max_clock, history_cap=cap)
             assert (clean["commit_counts"][i] == ref["commit_counts"][0]).all() and (clean["histories"][i] == ref["histories"][0]).all(), (n, i)
             want = ctm.cto.commit_times(oracle, cfg, int(seeds[i]), max_clock, cap)

@@ -7,20 +7,13 @@ import os
 import numpy as np
 import pytest
 
+from support import amd  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 # Host threads of the oracle spot checks.  Measured on the GPU box (round 6, tests/tools/oracle_scaling.py, 512 instances of c4live): 32 threads 20.2 s,
 # 64: 24.0 s, 128: 35.3 s, 256 (= os.cpu_count() there): 51.2 s -- the box gives this container the throughput of ~32 cores, and every thread beyond
 # them costs: the suite's oracle time fell by 2.5 x with the cap.
 HOST_THREADS = min(__import__("os").cpu_count() or 8, 32)
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import librabft_simulator_amd as L
-    L.lib()  # fails loudly if liblbft_hip.so is missing
-    return L
 
 
 def run_gpu(amd, kw, seeds, max_clock, **sim_kw):

@@ -12,30 +12,19 @@ class-0 kernels, the window of block records), and the refusal of a checkpoint a
 
 The batches are tests/switch_batches.py's, the smallest at which the paths in question run: odd sizes, a partly filled last wavefront."""
 import os
-import sys
 
 import numpy as np
 import pytest
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-
-import switch_batches as sb  # noqa: E402
-from switch_batches import LEAN2_OFF, NO_LEAN, NO_POPC, NO_QUAD, NO_UNI, both  # noqa: E402
+import switch_batches as sb
+from support import amd, run_to_end  # noqa: F401
+from switch_batches import LEAN2_OFF, NO_LEAN, NO_POPC, NO_QUAD, NO_UNI, both
 
 pytestmark = pytest.mark.gpu
 
 RESULT_COUNTERS = ("events", "rng_draws", "rounds", "commits", "events_scheduled")
 HISTORY_CAP = 96
 INVALID = -1  # LBFT_ERR_INVALID
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import librabft_simulator_amd as L
-    L.lib()
-    return L
 
 
 def seeds_of(m):
@@ -107,16 +96,6 @@ def run_under(amd, oracle, monkeypatch, batch, m, lanes, switches, kernel=None, 
     assert_ran_on(oracle, sim, batch, m, lanes, switches, kernel)
     assert_equal_to_ref(res, reference(oracle, batch, m))
     return sim, res
-
-
-def run_to_end(sim, max_clock, cut):
-    launches = 0
-    while True:
-        left, res = sim.run_steps(max_clock, cut)
-        launches += 1
-        assert launches < 200000
-        if left == 0:
-            return res
 
 
 # steps per launch of the stepped runs: two launches before a flip or a checkpoint, then launches of `resume` steps to the end (the four

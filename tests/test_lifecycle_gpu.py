@@ -3,29 +3,17 @@ mid-run state, runs cut into pieces and resumed from checkpoints, checkpoints lo
 oracle -- and, once, horizon changes (calendar <-> heap relayout), changes between node-level sessions and runs, and every refused call.
 The device state is only ever what this library's own kernels wrote (tests/test_dirty_state_host.py starts the same logic on arbitrary
 patterns, on the CPU)."""
-import os
-import sys
 import zlib
 
 import numpy as np
 import pytest
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-
-from test_gpu_parity import CASES, HOST_THREADS, assert_equal_to_oracle, run_gpu  # noqa: E402
+from support import amd, oracle_cfg, run_to_end  # noqa: F401
+from test_gpu_parity import CASES, HOST_THREADS, assert_equal_to_oracle, run_gpu
 
 pytestmark = pytest.mark.gpu
 
 RESULT_COUNTERS = ("events", "rng_draws", "rounds", "commits", "events_scheduled")
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import librabft_simulator_amd as L
-    L.lib()
-    return L
 
 
 # kernel_class word of lbft_batch_layout: class | heap << 8 | calendar << 9 | lean << 10 | cooperative ring << 11 | record exchange << 12 |
@@ -92,7 +80,6 @@ class SetsRow(Row):
         return amd.BatchSimulator.with_param_sets(seeds, 4, self.param_sets(amd), self.set_of, **self.sim_kw, **geometry)
 
     def oracle_check(self, oracle, res, seeds):
-        from test_param_sets_gpu import oracle_cfg
         import librabft_simulator_amd as amd
         ref = {k: np.zeros_like(v) for k, v in (("commit_counts", res.commit_counts), ("active_rounds", res.active_rounds),
                                                 ("last_states", res.last_committed_states), ("histories", res.committed_histories(256)))}
@@ -134,16 +121,6 @@ def same_extras(a, b):
     assert a.keys() == b.keys()
     for k in a:
         assert (a[k] == b[k]).all() if isinstance(a[k], np.ndarray) else a[k] == b[k], k
-
-
-def run_to_end(sim, max_clock, cut):
-    launches = 0
-    while True:
-        left, res = sim.run_steps(max_clock, cut)
-        launches += 1
-        assert launches < 200000
-        if left == 0:
-            return res
 
 
 def steps_then_save(sim, max_clock, cuts, path):

@@ -11,15 +11,9 @@ import sys
 import numpy as np
 import pytest
 
+from support import hiplib, other_libs  # noqa: F401
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def hiplib():
-    from librabft_simulator_amd import build
-    build.build()
-    from librabft_simulator_amd import _lib
-    return _lib
 
 
 def test_param_set_symbols_are_declared_and_exported(hiplib):
@@ -105,7 +99,6 @@ def test_grid_cli_does_not_import_the_oracle():
 
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf"), reason="needs the ROCm LLVM binutils")
 def test_param_set_kernels_are_a_separate_code_object_without_scratch(hiplib):
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
     from test_abi import _kernel_metadata
     from librabft_simulator_amd import build
     assert os.path.exists(build.PS_OUT)
@@ -119,8 +112,9 @@ def test_param_set_kernels_are_a_separate_code_object_without_scratch(hiplib):
     for k, v in ps.items():
         cap = run0[0] if "ps_run0" in k else run1[0] if "ps_run1" in k else {"private_segment_fixed_size": 0}
         assert v["private_segment_fixed_size"] <= cap["private_segment_fixed_size"], (k, v, cap)
-    # none of them went into liblbft_hip.so
-    assert not any("lbft_k_ps_" in k for k in base)
+    # none of them went into liblbft_hip.so or into another side library
+    for other in other_libs("paramsets"):
+        assert not any("lbft_k_ps_" in k for k in _kernel_metadata(other)), other
 
 
 def test_main_library_machine_code_is_unchanged(hiplib):

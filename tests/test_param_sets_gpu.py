@@ -9,19 +9,12 @@ import sys
 import numpy as np
 import pytest
 
+from support import amd, oracle_cfg, plain  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST_THREADS = min(os.cpu_count() or 8, 32)
 MAX_CLOCK = 1000
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import librabft_simulator_amd as L
-    L.lib()
-    return L
 
 
 def small_grid(amd):
@@ -35,22 +28,9 @@ def small_grid(amd):
     return sets
 
 
-def oracle_cfg(oc, n, ps, **kw):
-    d, nc = ps.network_delay, ps.node_config
-    part = ps.partition or (0, 0, 0)
-    return oc.make_config(num_nodes=n, mean=d.mean, variance=d.variance, delay_model=d.model, uniform_lo=d.lo, uniform_hi=d.hi,
-                          target_commit_interval=nc.target_commit_interval, delta=nc.delta, gamma=nc.gamma, lambda_=nc.lambda_,
-                          drop_per_million=ps.drop_per_million, partition_size=part[0], partition_start=part[1], partition_end=part[2],
-                          math_mode=1, **kw)
-
-
 def assignment(n_sets, per_set, how):
     k = np.arange(n_sets * per_set)
     return (k // per_set if how == "blocked" else k % n_sets).astype(np.uint32)
-
-
-def plain(amd, seeds, n, ps, **kw):
-    return amd.BatchSimulator.new(seeds, n, ps.network_delay, ps.node_config, drop_per_million=ps.drop_per_million, partition=ps.partition, **kw)
 
 
 @pytest.mark.parametrize("how", ["blocked", "interleaved"])

@@ -3,13 +3,12 @@
 commit counts, active rounds, last states, histories.  Drawn: network sizes, both delay models, delta / gamma / lambda /
 target_commit_interval, loss and partitions (the mid class), equivocators, blocked and interleaved assignment."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import build_shim, set_oracle_cfg
+
 SIZES = (3, 4, 7, 16, 20, 32)
 
 
@@ -20,10 +19,7 @@ def harness(tmp_path_factory):
 
 def load_harness(directory):
     """Compiles the host model into `directory` and binds it."""
-    out = str(directory / "libps_hostmodel.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-pthread", "-w",
-                           os.path.join(ROOT, "tests", "param_sets_host_model.cpp"), "-o", out])
-    L = C.CDLL(out)
+    L = build_shim(directory, "param_sets_host_model.cpp", "libps_hostmodel.so", "-ffp-contract=off", "-pthread", "-w")
     vp = C.c_void_p
     L.ps_hostmodel_run.argtypes = [vp, vp, C.c_uint32, vp, vp, C.c_size_t, C.c_int64, C.c_uint32, vp, vp, vp, vp, C.c_size_t, vp, C.c_uint32]
     L.ps_hostmodel_run.restype = C.c_int
@@ -78,14 +74,6 @@ def draw_batch(rng, n):
     return base, sets
 
 
-def oracle_cfg(oc, base, s):
-    return oc.make_config(num_nodes=base.num_nodes, mean=s.mean, variance=s.variance, delay_model=base.delay_model, uniform_lo=s.uniform_lo,
-                          uniform_hi=s.uniform_hi, commands_per_epoch=base.commands_per_epoch, target_commit_interval=s.target_commit_interval,
-                          delta=s.delta, gamma=s.gamma, lambda_=s.lambda_, quirks=base.quirks, equivocate_every=base.equivocate_every,
-                          drop_per_million=s.drop_per_million, partition_size=s.partition_size, partition_start=s.partition_start,
-                          partition_end=s.partition_end)
-
-
 def test_mixed_set_batches_equal_the_oracle_per_instance(harness, oracle):
     rng = np.random.default_rng(20261015)
     configs = compared = 0
@@ -105,7 +93,7 @@ def test_mixed_set_batches_equal_the_oracle_per_instance(harness, oracle):
         classes.add(cls)
         for j, s in enumerate(sets):
             idx = np.nonzero(set_of == j)[0]
-            ref = oracle.run_batch(oracle_cfg(oracle, base, s), seeds[idx], max_clock, history_cap=32)
+            ref = oracle.run_batch(set_oracle_cfg(oracle, base, s), seeds[idx], max_clock, history_cap=32)
             ok = got["faults"][idx] == 0  # (capacity faults are the device's, not the protocol's: compared where none was raised)
             for key in ("commit_counts", "active_rounds", "last_states", "histories"):
                 assert (got[key][idx][ok] == ref[key][ok]).all(), (batch, n, how, j, key)

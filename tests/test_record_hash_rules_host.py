@@ -6,10 +6,11 @@ sequences of bytes, words, options and lengths (every byte phase)."""
 import ctypes as C
 import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
+
+from support import build_shim
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 M64 = (1 << 64) - 1
@@ -18,10 +19,7 @@ VOTE_COUNTS = (0, 1, 3, 63, 64, 65, 127, 128)
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("rh_rules") / "librh_rules.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-w",
-                           os.path.join(ROOT, "tests", "record_hash_rules_host.cpp"), "-o", out])
-    L = C.CDLL(out)
+    L = build_shim(tmp_path_factory.mktemp("rh_rules"), "record_hash_rules_host.cpp", "librh_rules.so", "-ffp-contract=off", "-w")
     u64, u32, vp = C.c_uint64, C.c_uint32, C.c_void_p
     L.rhr_epoch_id.argtypes = [u64, vp]
     L.rhr_block.argtypes = [u64, u64, u32, u64, u64, u64, vp]

@@ -11,17 +11,10 @@ import sys
 import numpy as np
 import pytest
 
+from support import Stub, hiplib, other_libs  # noqa: F401
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "lbft_batch_chain_record_hashes"
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-
-@pytest.fixture(scope="module")
-def hiplib():
-    from librabft_simulator_amd import build
-    build.build()
-    from librabft_simulator_amd import _lib
-    return _lib
 
 
 def test_symbol_is_declared_exported_and_bound(hiplib):
@@ -38,7 +31,7 @@ def test_symbol_is_declared_exported_and_bound(hiplib):
     assert fields == list(hiplib.CHAIN_HEAD_DTYPE.names)
     assert (build.RH_SRC, build.RH_OUT, build.RH_DEPS) in build.LIBS and os.path.basename(build.RH_OUT) == "liblbft_record_hashes.so"
     assert hasattr(ctypes.CDLL(build.RH_OUT), "lbft_rh_launch_chain")
-    for other in (hiplib.LIB_PATH, build.PS_OUT, build.CT_OUT, build.RS_OUT, build.CS_OUT):
+    for other in (hiplib.LIB_PATH, *other_libs("record_hashes")):
         assert not hasattr(ctypes.CDLL(other), "lbft_rh_launch_chain"), other
     csrc = os.path.join(ROOT, "librabft_simulator_amd", "csrc")
     iface = open(os.path.join(csrc, "lbft_record_hashes.h")).read()
@@ -62,10 +55,6 @@ def test_arguments_are_refused_without_a_gpu(hiplib):
     assert heads.tobytes() == np.full(1, 7, dtype=hiplib.CHAIN_HEAD_DTYPE).tobytes()
 
 
-class Stub:  # (no batch behind it: the checks run before any library call)
-    _h, _max_clock, param_sets, num_instances, num_nodes = None, 1000, None, 1, 4
-
-
 def test_python_methods_refuse_bad_arguments_before_the_device():
     from librabft_simulator_amd.simulator import BatchResult
     res = BatchResult(Stub())
@@ -85,7 +74,7 @@ def test_kernel_is_in_its_own_library_without_scratch(hiplib, capsys):
     assert len(mine) == 1 and len([k for k in rh if "lbft_k_" in k]) == 1, sorted(rh)
     assert mine[0]["private_segment_fixed_size"] == 0 and mine[0]["vgpr_spill_count"] == 0, mine[0]
     assert mine[0]["vgpr_count"] <= 128 and mine[0]["group_segment_fixed_size"] == 0, mine[0]  # four wavefronts per SIMD, no LDS
-    for other in (build.OUT, build.PS_OUT, build.CT_OUT, build.RS_OUT, build.CS_OUT):
+    for other in other_libs("record_hashes"):
         assert not any("lbft_k_rh_" in k for k in _kernel_metadata(other)), other
     # the register tool lists it
     sys.path.insert(0, os.path.join(ROOT, "tools"))

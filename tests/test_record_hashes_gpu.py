@@ -4,27 +4,15 @@ last entry and node_prefix equals commit_counts; for the listed seeds the entrie
 smallest at which the mapping can go wrong: segments of 4, 8 and 64 lanes, more segments than two wavefronts hold, an idle lane per
 segment, block seams every four entries and the 64-entry seam, one to four voter words, two voter rounds, 64-wide tiles, parameter sets,
 empty chains, a capacity below the chains, heads alone, checkpoints, reset, the refusals, and 4 096 instances."""
-import os
-import sys
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+from support import amd  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 FIELDS = ("block_hash", "state", "qc_hash", "num_votes")
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import librabft_simulator_amd as L
-    L.lib()
-    return L
 
 
 def make(amd, kw, seeds, **sim_kw):

@@ -12,6 +12,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from support import build_shim
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "record_hashes_host_model.cpp")
 WIDTHS = (4, 8, 64)
@@ -31,9 +33,7 @@ BAD_ID = 4
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("rh_host") / "librh_hostmodel.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-pthread", "-w", SRC, "-o", out])
-    L = C.CDLL(out)
+    L = build_shim(tmp_path_factory.mktemp("rh_host"), "record_hashes_host_model.cpp", "librh_hostmodel.so", "-ffp-contract=off", "-pthread", "-w")
     vp, u32 = C.c_void_p, C.c_uint32
     L.rhm_create.argtypes = [vp, vp, C.c_size_t, C.c_int64, u32, vp]
     L.rhm_create.restype = vp

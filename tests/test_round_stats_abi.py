@@ -6,22 +6,14 @@ import ctypes
 import json
 import os
 import re
-import sys
 
 import numpy as np
 import pytest
 
+from support import Stub, hiplib, other_libs  # noqa: F401
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("lbft_batch_round_stats", "lbft_batch_round_switches_all")
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-
-@pytest.fixture(scope="module")
-def hiplib():
-    from librabft_simulator_amd import build
-    build.build()
-    from librabft_simulator_amd import _lib
-    return _lib
 
 
 def test_round_stats_symbols_are_declared_and_exported(hiplib):
@@ -36,7 +28,7 @@ def test_round_stats_symbols_are_declared_and_exported(hiplib):
     assert re.search(r"#define LBFT_ROUND_STATS 16\b", header) and hiplib.ROUND_STATS == 16
     assert (build.RS_SRC, build.RS_OUT, build.RS_DEPS) in build.LIBS and os.path.basename(build.RS_OUT) == "liblbft_round_stats.so"
     assert hasattr(ctypes.CDLL(build.RS_OUT), "lbft_rs_launch_rounds")
-    for other in (hiplib.LIB_PATH, build.PS_OUT, build.CT_OUT):
+    for other in (hiplib.LIB_PATH, *other_libs("round_stats")):
         assert not hasattr(ctypes.CDLL(other), "lbft_rs_launch_rounds"), other
     csrc = os.path.join(ROOT, "librabft_simulator_amd", "csrc")
     assert "lbft_rs_rounds_fn" in open(os.path.join(csrc, "lbft_round_stats.h")).read()
@@ -59,10 +51,6 @@ def test_arguments_are_refused_without_a_gpu(hiplib):
     assert L.lbft_batch_round_switches_all(None, out.ctypes.data, 4, mr.ctypes.data, None) == hiplib.LBFT_ERR_INVALID
     assert L.lbft_batch_round_switches_all(None, None, 4, None, None) == hiplib.LBFT_ERR_INVALID
     assert not stay.any() and not skew.any() and not stats.any() and not out.any()
-
-
-class Stub:  # (no batch behind it: the checks run before any library call)
-    _h, _max_clock, param_sets, num_instances, num_nodes = None, 1000, None, 1, 4
 
 
 def test_python_methods_refuse_bad_arguments_before_the_device():
@@ -94,7 +82,7 @@ def test_round_stats_kernel_is_in_its_own_library_without_scratch(hiplib):
     assert len(mine) == 1 and len([k for k in rs if "lbft_k_rs_" in k]) == 1, sorted(rs)
     assert mine[0]["private_segment_fixed_size"] == 0 and mine[0]["vgpr_spill_count"] == 0, mine[0]
     assert not any("lbft_k_run" in k or "lbft_k_ct_" in k or "lbft_k_ps_" in k for k in rs), sorted(rs)
-    for other in (build.OUT, build.PS_OUT, build.CT_OUT):
+    for other in other_libs("round_stats"):
         assert not any("lbft_k_rs_" in k for k in _kernel_metadata(other)), other
 
 

@@ -12,45 +12,13 @@ import sys
 import numpy as np
 import pytest
 
+import round_stats_reference as ref
+from support import amd, binning, oracle_cfg, plain, same  # noqa: F401
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import round_stats_reference as ref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 TRACE_OVERFLOW = 1 << 11  # LBFT_FAULT_TRACE_OVERFLOW
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import librabft_simulator_amd as L
-    L.lib()
-    return L
-
-
-def oracle_cfg(oc, n, ps, quirks=0):
-    d, nc = ps.network_delay, ps.node_config
-    part = ps.partition or (0, 0, 0)
-    return oc.make_config(num_nodes=n, mean=d.mean, variance=d.variance, delay_model=d.model, uniform_lo=d.lo, uniform_hi=d.hi,
-                          target_commit_interval=nc.target_commit_interval, delta=nc.delta, gamma=nc.gamma, lambda_=nc.lambda_,
-                          drop_per_million=ps.drop_per_million, partition_size=part[0], partition_start=part[1], partition_end=part[2],
-                          quirks=quirks, math_mode=1)
-
-
-def plain(amd, seeds, n, ps, **kw):
-    return amd.BatchSimulator.new(np.asarray(seeds, dtype=np.uint64), n, ps.network_delay, ps.node_config, drop_per_million=ps.drop_per_million,
-                                  partition=ps.partition, **kw)
-
-
-def binning(max_clock, width, bins):
-    """latency_histogram's defaults: width 1 up to 65 536 bins, above that the smallest width that fits."""
-    span = max_clock + 1
-    if width is None:
-        width = -(-span // bins) if bins else max(1, -(-span // (1 << 16)))
-    if bins is None:
-        bins = -(-span // width)
-    return width, bins
 
 
 def check_tables(res, want, clean=None):
@@ -90,7 +58,7 @@ JUMPS = dict(n=4, quirks=3, partition=(1, 300, 600), max_clock=1000, seeds=np.ar
 @pytest.fixture(scope="module")
 def jumps_oracle(amd, oracle):
     ps = amd.ParamSet(partition=JUMPS["partition"])
-    return ref.oracle_tables(oracle, oracle_cfg(oracle, JUMPS["n"], ps, JUMPS["quirks"]), JUMPS["seeds"], JUMPS["max_clock"])
+    return ref.oracle_tables(oracle, oracle_cfg(oracle, JUMPS["n"], ps, quirks=JUMPS["quirks"]), JUMPS["seeds"], JUMPS["max_clock"])
 
 
 def jumps_batch(amd):
@@ -132,7 +100,7 @@ def test_parameter_sets_interleaved(amd, oracle):
     from librabft_simulator_amd import grid
     set_of, seed_index = grid.set_assignment(len(sets), per, "interleaved")
     seeds = (1 + seed_index).astype(np.uint64)
-    per_set = [ref.oracle_tables(oracle, oracle_cfg(oracle, n, ps, 3), np.arange(1, per + 1), max_clock) for ps in sets]
+    per_set = [ref.oracle_tables(oracle, oracle_cfg(oracle, n, ps, quirks=3), np.arange(1, per + 1), max_clock) for ps in sets]
     rows = max(t.shape[1] for t, _, _ in per_set)
     tables_o = np.full((len(set_of), rows, n), ref.EMPTY, dtype=np.int64)
     max_rounds_o = np.zeros(len(set_of), dtype=np.uint64)
@@ -211,7 +179,7 @@ def test_tables_of_three_chunks_with_a_jump_over_a_chunk_seam(amd, oracle, parti
     # jumps over that row when it catches up
     n, max_clock, seeds = 4, 5000, np.arange(1, 9, dtype=np.uint64)
     ps = amd.ParamSet(partition=partition)
-    want = ref.oracle_tables(oracle, oracle_cfg(oracle, n, ps, 3), seeds, max_clock)
+    want = ref.oracle_tables(oracle, oracle_cfg(oracle, n, ps, quirks=3), seeds, max_clock)
     assert int(want[1].min()) > 128 and seam_pairs(want[0], want[1], seam)
     sim = plain(amd, seeds, n, ps, quirks=3)
     res = sim.loop_until(max_clock, round_trace=256)
@@ -268,10 +236,6 @@ def test_faulted_instances_are_skipped(amd, jumps_oracle):
 # ---- case 7: lifecycle ----
 def arrays(res):
     return list(res.round_tables()) + list(res.round_histogram()) + list(res.round_histogram(9, 30))
-
-
-def same(a, b):
-    return len(a) == len(b) and all(x.shape == y.shape and (x == y).all() for x, y in zip(a, b))
 
 
 def test_reset_steps_and_checkpoint_give_the_same_arrays(amd, jumps, tmp_path):

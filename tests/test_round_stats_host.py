@@ -4,16 +4,14 @@ definitions (tests/round_stats_reference.py) -- on drawn traces that hit every e
 and on the oracle's own tables of a network with a partition, where nodes do jump rounds."""
 import ctypes as C
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import round_stats_reference as ref
+from support import build_shim
 
-import round_stats_reference as ref  # noqa: E402
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 NONE = 0xffffffff  # an empty cell as the device stores it
 CHUNKS = (1, 64, 32, 5)  # lanes side by side in the shim's node-major walk (the kernel: 64)
@@ -21,10 +19,7 @@ CHUNKS = (1, 64, 32, 5)  # lanes side by side in the shim's node-major walk (the
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("rtl_host") / "librtl_host.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Werror", os.path.join(ROOT, "tests", "round_stats_host.cpp"),
-                           "-o", out])
-    L = C.CDLL(out)
+    L = build_shim(tmp_path_factory.mktemp("rtl_host"), "round_stats_host.cpp", "librtl_host.so", "-Wall", "-Werror")
     vp = C.c_void_p
     L.rtl_host.argtypes = [vp, vp, vp, vp] + [C.c_uint32] * 7 + [vp, vp, vp]
     L.rtl_host.restype = C.c_int

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Register budget of the run kernels and of the statistic kernels (lbft_k_ct_*, lbft_k_rs_rounds, lbft_k_cs_chain, lbft_k_rh_chain) in a built library: VGPRs, SGPRs, spilled
+"""Register budget of the run kernels and of the side libraries' kernels (the prefixes of build.TABLE) in a built library: VGPRs, SGPRs, spilled
 registers, scratch and LDS bytes per kernel, read from
 the AMDGPU metadata note of the gfx950 code object (no GPU needed).  The register-pressure work of DESIGN.md section 4 is
 this loop: build one kernel class alone with a piece of source disabled (seconds instead of minutes)
@@ -18,10 +18,13 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 def main():
     from test_abi import _kernel_metadata
-    libs = sys.argv[1:] or [os.path.join(ROOT, "librabft_simulator_amd", "liblbft_hip.so")]
+    from librabft_simulator_amd import build
+    # the run kernels and the side libraries' (build.TABLE); liblbft_paramsets.so's have never been listed, and listing them would change the output
+    listed = ("lbft_k_run",) + tuple(lib.prefix for lib in build.TABLE if lib.prefix and lib.tag != "paramsets")
+    libs = sys.argv[1:] or [build.OUT]
     for path in libs:
         for name, v in sorted(_kernel_metadata(path).items()):
-            if ("lbft_k_run" in name or "lbft_k_rs_" in name or "lbft_k_ct_" in name or "lbft_k_cs_" in name or "lbft_k_rh_" in name) and v["vgpr_count"]:
+            if any(prefix in name for prefix in listed) and v["vgpr_count"]:
                 print("%-28s %-44s vgprs %3d  sgprs %3d  spilled %3d  scratch %4d B  lds %5d B" % (
                     os.path.basename(path), name[:44], v["vgpr_count"], v["sgpr_count"], v["vgpr_spill_count"], v["private_segment_fixed_size"],
                     v["group_segment_fixed_size"]))
