@@ -19,21 +19,17 @@ using namespace lbft;
 
 #include "lbft_launch.h"
 #include "lbft_run_body.h"  // run_body
-static_assert(run_lane_private<K_SMALL_TIMED> && run_lane_private<K_MID_TIMED> && run_lane_private<K_SMALL_SETS_TIMED> && run_lane_private<K_MID_SETS_TIMED>,
-              "lane-private classes only");
 
 // Small class (lbft_k_run0's geometry: two wavefronts per SIMD) and mid class (lbft_k_run<1>'s: one wavefront per SIMD, the whole register
 // file), each plain and with parameter sets.
-__global__ __launch_bounds__(LBFT_RUN_BLOCK) __attribute__((amdgpu_waves_per_eu(LBFT_RUN_WAVES_PER_SIMD, LBFT_RUN_WAVES_PER_SIMD)))
-void lbft_k_ct_run0(Params p, u32* __restrict__ state, u32* __restrict__ unfinished, i32* __restrict__ ctimes) {
+__global__ LBFT_TWO_WAVE_BOUNDS void lbft_k_ct_run0(Params p, u32* __restrict__ state, u32* __restrict__ unfinished, i32* __restrict__ ctimes) {
   run_body<K_SMALL_TIMED>(p, state, unfinished, nullptr, nullptr, ctimes);
 }
 __global__ __launch_bounds__(64 * LBFT_RUN_WAVES_FULL)
 void lbft_k_ct_run1(Params p, u32* __restrict__ state, u32* __restrict__ unfinished, i32* __restrict__ ctimes) {
   run_body<K_MID_TIMED>(p, state, unfinished, nullptr, nullptr, ctimes);
 }
-__global__ __launch_bounds__(LBFT_RUN_BLOCK) __attribute__((amdgpu_waves_per_eu(LBFT_RUN_WAVES_PER_SIMD, LBFT_RUN_WAVES_PER_SIMD)))
-void lbft_k_ct_ps_run0(Params p, u32* __restrict__ state, u32* __restrict__ unfinished, const ParamSetDev* __restrict__ sets, const u8* __restrict__ set_of,
+__global__ LBFT_TWO_WAVE_BOUNDS void lbft_k_ct_ps_run0(Params p, u32* __restrict__ state, u32* __restrict__ unfinished, const ParamSetDev* __restrict__ sets, const u8* __restrict__ set_of,
                        i32* __restrict__ ctimes) {
   run_body<K_SMALL_SETS_TIMED>(p, state, unfinished, sets, set_of, ctimes);
 }

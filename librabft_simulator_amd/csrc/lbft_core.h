@@ -31,6 +31,8 @@
 #include <stdint.h>
 #include <math.h>
 
+#include <type_traits>
+
 #include "lbft_math.h"
 
 namespace lbft {
@@ -690,7 +692,7 @@ struct Actions {  // NodeUpdateActions (interfaces.rs:12-21); should_send has at
 
 // The step's specialisations by name (round-5 review: "magic class numbers"); the values are the template arguments they always were -- the kernels' names
 // (lbft_k_run0 / 0q / 0s / 0u / 1l / 2l / 2q, lbft_k_run<1>, lbft_k_run<2>) and machine code are unchanged.  sim_class() returns K_SMALL / K_MID / K_LARGE for a
-// batch; lbft_hip.hip picks the specialisation of that class (sim_quad, sim_lean, sim_lean_q1, sim_lean1, the batch's size).
+// batch; lbft_plan.h picks the specialisation of that class (pick_run_kernel: sim_quad, sim_lean, sim_lean_q1, sim_lean1, the batch's size).
 enum KernelClass : int {
   K_SMALL = 0,           // lbft_k_run0:  n <= 16, honest nodes, lossless network, reference routing; packed queue behind the LDS front
   K_MID = 1,             // lbft_k_run<1>: n <= 32, one mask word; every feature
@@ -4480,6 +4482,12 @@ struct SimTTimed : SimTSets<KCLS> {
   using SimTSets<KCLS>::SimTSets;
   LBFT_HD void attach_commit_times(i32* base, u32 row) { ctimes = base; crow = row; }
 };
+// What the event loop of class KCLS runs on: SimT, with the lane's parameter set (SimTSets) or also its commit-time rows (SimTTimed)
+template <int KCLS>
+using RunSim = std::conditional_t<SimT<KCLS>::CTIME, SimTTimed<KCLS>, std::conditional_t<SimT<KCLS>::PSET, SimTSets<KCLS>, SimT<KCLS>>>;
+// The classes whose every lane runs its own event loop (run_body's last branch): what K_PARAM_SETS / K_COMMIT_TIMES may be added to.
+template <int CLS>
+constexpr bool run_lane_private = !SimT<CLS>::COOP && !SimT<CLS>::POPC && !SimT<CLS>::WUNI && !SimT<CLS>::QUAD;
 // The class lbft_k_run (and the host model) executes a batch with.
 inline int sim_class(const Params& p) {
   if (p.n > 32) return K_LARGE;

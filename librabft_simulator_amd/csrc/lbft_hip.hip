@@ -58,27 +58,20 @@ __global__ __launch_bounds__(LBFT_BLOCK) void lbft_k_init(Params p, u32* __restr
 #endif
 // Class 0 (the headline small-network path) is compiled for two wavefronts per SIMD; classes 1 and 2 run one 8- or 16-lane
 // wavefront per SIMD and may use the whole register file (VGPRs + AGPRs).
-__global__ __launch_bounds__(LBFT_RUN_BLOCK) __attribute__((amdgpu_waves_per_eu(LBFT_RUN_WAVES_PER_SIMD, LBFT_RUN_WAVES_PER_SIMD)))
-void lbft_k_run0(Params p, u32* __restrict__ state, u32* __restrict__ unfinished) { LBFT_DEV_ONLY(K_SMALL) run_body<K_SMALL>(p, state, unfinished); }
+__global__ LBFT_TWO_WAVE_BOUNDS void lbft_k_run0(Params p, u32* __restrict__ state, u32* __restrict__ unfinished) { LBFT_DEV_ONLY(K_SMALL) run_body<K_SMALL>(p, state, unfinished); }
 // ... the same kernel with the headline network fixed at compile time (4 nodes, unit voting rights, log-normal delays: SimT<K_HEADLINE>, sim_quad())
-__global__ __launch_bounds__(LBFT_RUN_BLOCK) __attribute__((amdgpu_waves_per_eu(LBFT_RUN_WAVES_PER_SIMD, LBFT_RUN_WAVES_PER_SIMD)))
-void lbft_k_run0q(Params p, u32* __restrict__ state, u32* __restrict__ unfinished) { LBFT_DEV_ONLY(K_HEADLINE) run_body<K_HEADLINE>(p, state, unfinished); }
+__global__ LBFT_TWO_WAVE_BOUNDS void lbft_k_run0q(Params p, u32* __restrict__ state, u32* __restrict__ unfinished) { LBFT_DEV_ONLY(K_HEADLINE) run_body<K_HEADLINE>(p, state, unfinished); }
 // ... and for small batches (at most LBFT_POPC_MAX_LPW networks per wavefront): the pop's scan by all 64 lanes (SimT<K_SMALL_WAVE_POP>)
-__global__ __launch_bounds__(LBFT_RUN_BLOCK) __attribute__((amdgpu_waves_per_eu(LBFT_RUN_WAVES_PER_SIMD, LBFT_RUN_WAVES_PER_SIMD)))
-void lbft_k_run0s(Params p, u32* __restrict__ state, u32* __restrict__ unfinished) { LBFT_DEV_ONLY(K_SMALL_WAVE_POP) run_body<K_SMALL_WAVE_POP>(p, state, unfinished); }
+__global__ LBFT_TWO_WAVE_BOUNDS void lbft_k_run0s(Params p, u32* __restrict__ state, u32* __restrict__ unfinished) { LBFT_DEV_ONLY(K_SMALL_WAVE_POP) run_body<K_SMALL_WAVE_POP>(p, state, unfinished); }
 // ... and for ONE network per wavefront (batches of <= 2 048 networks), as wavefront-uniform code on the scalar unit (SimT<K_SMALL_UNIFORM>; round 5, measured: 256 / 1 024 / 2 048 x 4
 // networks 4.77 / 4.88 / 4.91 ms against 5.81 / 5.27 / 5.28 ms on lbft_k_run0s; LBFT_NO_UNI=1 falls back to that kernel)
-__global__ __launch_bounds__(LBFT_RUN_BLOCK) __attribute__((amdgpu_waves_per_eu(LBFT_RUN_WAVES_PER_SIMD, LBFT_RUN_WAVES_PER_SIMD)))
-void lbft_k_run0u(Params p, u32* __restrict__ state, u32* __restrict__ unfinished) { LBFT_DEV_ONLY(K_SMALL_UNIFORM) run_body<K_SMALL_UNIFORM>(p, state, unfinished); }
+__global__ LBFT_TWO_WAVE_BOUNDS void lbft_k_run0u(Params p, u32* __restrict__ state, u32* __restrict__ unfinished) { LBFT_DEV_ONLY(K_SMALL_UNIFORM) run_body<K_SMALL_UNIFORM>(p, state, unfinished); }
 // Large networks without record exchange / trace / lossy network (sim_lean()): also two wavefronts per SIMD (4 spilled registers)
-__global__ __launch_bounds__(LBFT_RUN_BLOCK) __attribute__((amdgpu_waves_per_eu(LBFT_RUN_WAVES_PER_SIMD, LBFT_RUN_WAVES_PER_SIMD)))
-void lbft_k_run2l(Params p, u32* __restrict__ state, u32* __restrict__ unfinished) { LBFT_DEV_ONLY(K_LARGE_LEAN) run_body<K_LARGE_LEAN>(p, state, unfinished); }
+__global__ LBFT_TWO_WAVE_BOUNDS void lbft_k_run2l(Params p, u32* __restrict__ state, u32* __restrict__ unfinished) { LBFT_DEV_ONLY(K_LARGE_LEAN) run_body<K_LARGE_LEAN>(p, state, unfinished); }
 // ... and with the record exchange of quirks bit 0 (sim_lean_q1(): requests answered by the peer, responses inserted): 24 spilled registers
-__global__ __launch_bounds__(LBFT_RUN_BLOCK) __attribute__((amdgpu_waves_per_eu(LBFT_RUN_WAVES_PER_SIMD, LBFT_RUN_WAVES_PER_SIMD)))
-void lbft_k_run2q(Params p, u32* __restrict__ state, u32* __restrict__ unfinished) { LBFT_DEV_ONLY(K_LARGE_EXCHANGE) run_body<K_LARGE_EXCHANGE>(p, state, unfinished); }
+__global__ LBFT_TWO_WAVE_BOUNDS void lbft_k_run2q(Params p, u32* __restrict__ state, u32* __restrict__ unfinished) { LBFT_DEV_ONLY(K_LARGE_EXCHANGE) run_body<K_LARGE_EXCHANGE>(p, state, unfinished); }
 // ... and class 1 without them (networks of <= 32 nodes with equivocators, a heap / calendar queue, ...): 22 spilled registers
-__global__ __launch_bounds__(LBFT_RUN_BLOCK) __attribute__((amdgpu_waves_per_eu(LBFT_RUN_WAVES_PER_SIMD, LBFT_RUN_WAVES_PER_SIMD)))
-void lbft_k_run1l(Params p, u32* __restrict__ state, u32* __restrict__ unfinished) { LBFT_DEV_ONLY(K_MID_LEAN) run_body<K_MID_LEAN>(p, state, unfinished); }
+__global__ LBFT_TWO_WAVE_BOUNDS void lbft_k_run1l(Params p, u32* __restrict__ state, u32* __restrict__ unfinished) { LBFT_DEV_ONLY(K_MID_LEAN) run_body<K_MID_LEAN>(p, state, unfinished); }
 template <int CLS>
 __global__ __launch_bounds__(64 * LBFT_RUN_WAVES_FULL)
 #if LBFT_BIG_WAVES_PER_SIMD > 1
@@ -935,9 +928,9 @@ int lbft_batch_run_until(lbft_batch* b, int64_t max_clock) {
   return finalize_run(b, grid_full, launches);
 }
 
-// One launch of the batch's run kernel (LaunchPlan::kernel): the kernels of this library, or a side library's lane-private twins --
-// a parameter-set batch's (lbft_k_ps_run0 / 1) or, recording commit times, a plain or parameter-set batch's (lbft_k_ct_run0 / 1,
-// lbft_k_ct_ps_run0 / 1).
+// One launch of the batch's run kernel (LaunchPlan::kernel), as its row of lbft_plan.h's table says: a kernel of this library, or a
+// lane-private twin through its library's launcher, which is told the class (K_SMALL or K_MID) and given the batch's parameter sets
+// (none: a null pointer) and commit-time buffer.
 static int launch_run(lbft_batch* b) {
   Params& p = b->p;
   const size_t lds = b->launch.lds_bytes;
@@ -945,29 +938,13 @@ static int launch_run(lbft_batch* b) {
   u32 grid_run = (u32)((b->m + (size_t)nwaves * p.lpw - 1) / ((size_t)nwaves * p.lpw));
   HIP_TRY(hipMemsetAsync(b->d_unfinished, 0, sizeof(u32), b->stream));
   b->generation++;
-  auto launch = [&](auto kernel) { return launch_run_kernel(kernel, grid_run, block, lds, b->stream, p, b->d_state, b->d_unfinished); };
-  const int cls = sim_class(p);  // (the twins: K_SMALL or K_MID)
-  switch (b->launch.kernel) {
-    case RK_RUN0: HIP_TRY(launch(lbft_k_run0)); break;
-    case RK_RUN0Q: HIP_TRY(launch(lbft_k_run0q)); break;
-    case RK_RUN0S: HIP_TRY(launch(lbft_k_run0s)); break;
-    case RK_RUN0U: HIP_TRY(launch(lbft_k_run0u)); break;
-    case RK_RUN1L: HIP_TRY(launch(lbft_k_run1l)); break;
-    case RK_RUN1: HIP_TRY(launch(lbft_k_run<K_MID>)); break;
-    case RK_RUN2L: HIP_TRY(launch(lbft_k_run2l)); break;
-    case RK_RUN2Q: HIP_TRY(launch(lbft_k_run2q)); break;
-    case RK_RUN2: HIP_TRY(launch(lbft_k_run<K_LARGE>)); break;
-    case RK_PS_RUN0: case RK_PS_RUN1:
-      HIP_TRY(g_ps_run(cls, &p, b->d_state, b->d_unfinished, b->d_psets, b->d_set_of, grid_run, block, lds, b->stream));
-      break;
-    case RK_CT_RUN0: case RK_CT_RUN1:
-      HIP_TRY(g_ct_run(cls, &p, b->d_state, b->d_unfinished, nullptr, nullptr, b->d_ctimes, grid_run, block, lds, b->stream));
-      break;
-    case RK_CT_PS_RUN0: case RK_CT_PS_RUN1:
-      HIP_TRY(g_ct_run(cls, &p, b->d_state, b->d_unfinished, b->d_psets, b->d_set_of, b->d_ctimes, grid_run, block, lds, b->stream));
-      break;
-    default: g_err = "no launch for this run kernel"; return LBFT_ERR_UNSUPPORTED;
-  }
+  const int cls = sim_class(p);
+#define LBFT_LAUNCH_LIB_HIP(KERNEL) launch_run_kernel(KERNEL, grid_run, block, lds, b->stream, p, b->d_state, b->d_unfinished)
+#define LBFT_LAUNCH_LIB_PARAMSETS(KERNEL) g_ps_run(cls, &p, b->d_state, b->d_unfinished, b->d_psets, b->d_set_of, grid_run, block, lds, b->stream)
+#define LBFT_LAUNCH_LIB_COMMIT_TIMES(KERNEL) \
+  g_ct_run(cls, &p, b->d_state, b->d_unfinished, b->d_psets, b->d_set_of, b->d_ctimes, grid_run, block, lds, b->stream)
+#define LBFT_RK_LAUNCH(TAG, KERNEL, KCLS, TWO_WAVE, FLAGS, LIB) case TAG: HIP_TRY(LBFT_LAUNCH_##LIB(KERNEL)); break;
+  switch (b->launch.kernel) { LBFT_RUN_KERNELS(LBFT_RK_LAUNCH) }
   return LBFT_OK;
 }
 
@@ -1028,7 +1005,7 @@ static void fill_header(const lbft_batch* b, CheckpointHeader& h) {
   h.equiv = p.equiv; h.m = b->m; h.cpe = c.commands_per_epoch; h.max_clock = b->started_max_clock; h.tci = c.target_commit_interval;
   h.delta = c.delta; h.uni_lo = c.uniform_lo; h.uni_hi = c.uniform_hi; h.mean = c.mean; h.variance = c.variance; h.gamma = c.gamma;
   h.lambda = c.lambda; h.delay_model = c.delay_model; h.weights_hash = weights_hash(b->weights) ^ (p.rot * 0x9e3779b9u);
-  h.quirks = p.quirks; h.drop_ppm = p.drop_ppm; h.part_size = p.part_size; h.rot = p.rot; h.sim_class = (u32)sim_class(p) | ((run_kernel_info(plain_kernel(b)).flags & (1u << 10)) ? 256u : 0u);
+  h.quirks = p.quirks; h.drop_ppm = p.drop_ppm; h.part_size = p.part_size; h.rot = p.rot; h.sim_class = (u32)sim_class(p) | ((run_kernel_info(plain_kernel(b)).flags & LF_LEAN) ? 256u : 0u);
   h.qpack = p.qpack; h.qcal = p.qcal; h.qheap = p.qheap; h.ecap = p.ecap; h.tw = p.tw | (p.ring << 8); h.part_start = c.partition_start; h.part_end = c.partition_end;
   if (!b->psets.empty()) {  // (a parameter-set batch: the sets and the instances' assignment, folded into the same header words)
     u32 sh = 2166136261u;

@@ -55,6 +55,8 @@ inline hipError_t launch_run_kernel(void (*kernel)(KArgs...), u32 grid, u32 bloc
 #define LBFT_RUN_WAVES_PER_SIMD 2  // register budget of the class-0 run kernel: 512 / 2 = 256 VGPRs + AGPRs per lane (the
                                    // large-network classes run one 8- or 16-lane wavefront per SIMD and may use all 512)
 #endif
+// the launch bounds of a run kernel compiled for two wavefronts per SIMD (lbft_plan.h's table of run kernels says which are)
+#define LBFT_TWO_WAVE_BOUNDS __launch_bounds__(LBFT_RUN_BLOCK) __attribute__((amdgpu_waves_per_eu(LBFT_RUN_WAVES_PER_SIMD, LBFT_RUN_WAVES_PER_SIMD)))
 #ifndef LBFT_BIG_WAVES_PER_SIMD
 #define LBFT_BIG_WAVES_PER_SIMD 1  // classes 1-2: wavefronts per SIMD the kernels are compiled for (1 = the whole register file;
                                    // measured with 2 -- half the lanes per wavefront, 167 spilled registers: 16384 x 64 nodes

@@ -17,7 +17,6 @@ using namespace lbft;
 
 #include "lbft_launch.h"
 #include "lbft_run_body.h"  // run_body
-static_assert(run_lane_private<K_SMALL_SETS> && run_lane_private<K_MID_SETS>, "lane-private classes only");
 
 // Simulator::new for every instance: init() draws the startup times with the set's delay parameters.
 __global__ __launch_bounds__(LBFT_BLOCK) void lbft_k_ps_init(Params p, u32* __restrict__ state, const u64* __restrict__ seeds,
@@ -30,8 +29,7 @@ __global__ __launch_bounds__(LBFT_BLOCK) void lbft_k_ps_init(Params p, u32* __re
 }
 
 // Small class (lbft_k_run0's geometry: two wavefronts per SIMD): n <= 16, honest, lossless, no trace, reference routing.
-__global__ __launch_bounds__(LBFT_RUN_BLOCK) __attribute__((amdgpu_waves_per_eu(LBFT_RUN_WAVES_PER_SIMD, LBFT_RUN_WAVES_PER_SIMD)))
-void lbft_k_ps_run0(Params p, u32* __restrict__ state, u32* __restrict__ unfinished, const ParamSetDev* __restrict__ sets, const u8* __restrict__ set_of) {
+__global__ LBFT_TWO_WAVE_BOUNDS void lbft_k_ps_run0(Params p, u32* __restrict__ state, u32* __restrict__ unfinished, const ParamSetDev* __restrict__ sets, const u8* __restrict__ set_of) {
   run_body<K_SMALL_SETS>(p, state, unfinished, sets, set_of);
 }
 // Mid class (lbft_k_run<1>'s geometry: one wavefront per SIMD, the whole register file): n <= 32, every feature.

@@ -5,19 +5,13 @@
 //   K_PARAM_SETS classes: the lane's set (`sets`, `set_of`) is loaded at entry; there is no LDS copy of the duration table -- each lane
 //                         reads its set's table from HBM (L2-resident).  The other classes keep the batch's first LBFT_LDS_DURS entries in LDS.
 //   K_COMMIT_TIMES classes: the lane's rows of the commit-time buffer (`ctimes`, [instance][node][lcap] i32) are attached at entry.
-// Both flags go with the lane-private classes only (run_lane_private: the side libraries assert it for what they instantiate); the plain
+// Both flags go with the lane-private classes only (run_lane_private: asserted below, and for every row of lbft_plan.h's table); the plain
 // classes ignore the three arguments.
 // (Included under `using namespace lbft`, after lbft_launch.h.)
 #ifndef LBFT_RUN_BODY_H
 #define LBFT_RUN_BODY_H
 
-#include <type_traits>
-
 #include "lbft_core.h"
-
-// The classes whose every lane runs its own event loop (run_body's last branch): what K_PARAM_SETS / K_COMMIT_TIMES may be added to.
-template <int CLS>
-constexpr bool run_lane_private = !SimT<CLS>::COOP && !SimT<CLS>::POPC && !SimT<CLS>::WUNI && !SimT<CLS>::QUAD;
 
 // Phase timers (-DLBFT_PHASE_TIMERS, LBFT_MARK of lbft_core.h): `wprof` = the wavefront's accumulators in LDS.  No-ops in product builds.
 template <class S>
@@ -192,8 +186,7 @@ __device__ __forceinline__ void run_body(const Params& p, u32* __restrict__ stat
   if (active) {
     // Every lane its own event loop: SimT, with the lane's parameter set (SimTSets) or also its commit-time rows (SimTTimed).
     // (instance-major classes: lane j's instance sits j instances behind the wavefront's first one -- folded into the lane's 32-bit column offset)
-    using S = std::conditional_t<CTIME, SimTTimed<CLS>, std::conditional_t<PSET, SimTSets<CLS>, SimT<CLS>>>;
-    S s(p, tile, SimT<CLS>::IMAJOR ? lane * (p.total_words * 4u) : (i & (tw - 1u)) * 4u, 0);
+    RunSim<CLS> s(p, tile, SimT<CLS>::IMAJOR ? lane * (p.total_words * 4u) : (i & (tw - 1u)) * 4u, 0);
     if (s.ld(I_DONE) == 0) {
       if constexpr (PSET) s.load_set(sets[set_of[i]]);
       if constexpr (CTIME) s.attach_commit_times(ctimes, i * p.n);

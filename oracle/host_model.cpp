@@ -7,7 +7,6 @@
 #include <cstddef>
 #include <cstring>
 #include <thread>
-#include <type_traits>
 #include <vector>
 
 #include "host_model_common.h"
@@ -137,26 +136,21 @@ int lbft_hostmodel_run_batch(const lbft_oracle_config* cfg, const lbft_hostmodel
 
   if (threads == 0) threads = 1;
   if (p.n > 32) p.qheap = 1;  // as the device host code does
-  // the step runs as the size class the device would pick (SimT<0..2>); init and read-back use the generic class
-  auto run = [&](auto& s) {
-    using S = typename std::remove_reference<decltype(s)>::type;
-    const bool coop = run_one(s, p, fill);
-    g_last_class.store((uint32_t)S::CLS | (coop ? 256u : 0u) | (p.qheap ? 512u : 0u) | (p.qcal ? 1024u : 0u));
-  };
-  int cls = caps->force_generic ? 3 : sim_class(p);
-  if (cls <= 2) set_tile_width(p, layout_tile_width(p));
+  // The step runs as the class of the kernel the planner picks for the batch; init and read-back use the generic class.  The host's
+  // knobs: no_popc, since the wavefront-wide pops (SimT::POPC / WUNI / PAIR) are device-only and the host has none to run -- and p.lpw
+  // is 0 (fill_params), so a class-0 batch is the headline kernel's whenever it is the headline network, K_SMALL's otherwise.
+  // force_generic: the run-time-generic class, which has no run kernel.
+  PlanKnobs knobs;
+  knobs.no_popc = true;
+  const RunKernel kernel = pick_run_kernel(p, false, false, knobs);
+  const bool generic = caps->force_generic != 0;
+  if (!generic) set_tile_width(p, layout_tile_width(p));
   dirty_state(p, state, fill);
   auto worker = [&](u32 tid) {
     for (size_t i = tid; i < n_instances; i += threads) {
-      { Sim s0(p, state.data(), (u32)i); s0.init(seeds[i]); }
-      if (cls == K_SMALL && LBFT_C0_QUAD && sim_quad(p)) { SimT<K_HEADLINE> s(p, state.data(), (u32)i); run(s); }  // as the device dispatches (large batches)
-      else if (cls == K_SMALL) { SimT<K_SMALL> s(p, state.data(), (u32)i); run(s); }
-      else if (cls == K_MID && sim_lean1(p)) { SimT<K_MID_LEAN> s(p, state.data(), (u32)i); run(s); }  // as the device dispatches
-      else if (cls == K_MID) { SimT<K_MID> s(p, state.data(), (u32)i); run(s); }
-      else if (cls == K_LARGE && sim_lean_q1(p)) { SimT<K_LARGE_EXCHANGE> s(p, state.data(), (u32)i); run(s); }  // as the device dispatches
-      else if (cls == K_LARGE && sim_lean(p)) { SimT<K_LARGE_LEAN> s(p, state.data(), (u32)i); run(s); }
-      else if (cls == K_LARGE) { SimT<K_LARGE> s(p, state.data(), (u32)i); run(s); }
-      else { Sim s(p, state.data(), (u32)i); run(s); }
+      init_instance(p, state.data(), (u32)i, seeds[i]);
+      const bool coop = generic ? [&] { Sim s(p, state.data(), (u32)i); return run_one(s, p, fill); }() : run_instance<LIB_HIP>(kernel, p, state.data(), (u32)i, fill);
+      g_last_class.store((uint32_t)(generic ? K_GENERIC : run_kernel_info(kernel).cls) | (coop ? 256u : 0u) | (p.qheap ? 512u : 0u) | (p.qcal ? 1024u : 0u));
     }
   };
   std::vector<std::thread> ts;
@@ -420,5 +414,8 @@ int lbft_hostmodel_plan(const lbft_oracle_config* cfg, const uint32_t* capacitie
   return lbft_hostmodel_plan_knobs(cfg, capacities, n_instances, max_clock, lanes, n_sets, commit_times, keep_stores, calendar_queue, avail_bytes,
                                    nullptr, out);
 }
+
+// Row k (in RunKernel's order) of lbft_plan.h's table of run kernels, NULL past the last: mirrored by oracle_ctypes.HostModelRunKernel
+const RunKernelInfo* lbft_hostmodel_run_kernel(uint32_t k) { return k < N_RUN_KERNELS ? &RUN_KERNEL_TABLE[k] : nullptr; }
 
 }  // extern "C"

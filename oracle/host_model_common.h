@@ -61,6 +61,23 @@ static bool run_one(S& s, const Params& p, u32 fill) {
   return coop;
 }
 
+// Simulator::new of instance `i`: the generic class, with the instance's parameter set `set` when the batch has sets
+inline void init_instance(const Params& p, u32* state, u32 i, u64 seed, const ParamSetDev* set = nullptr) {
+  if (set) { SimTSets<K_GENERIC_SETS> s(p, state, i); s.load_set(*set); s.init(seed); }
+  else { Sim s(p, state, i); s.init(seed); }
+}
+// Instance `i`'s event loop as the planned run kernel `k` of library LIB runs it (run_body's lane-private branch): the class of k's row
+// of lbft_plan.h's table, with the instance's set and the batch's commit-time buffer where the class reads them.  Returns as run_one.
+template <RunLib LIB>
+static bool run_instance(RunKernel k, const Params& p, u32* state, u32 i, u32 fill, const ParamSetDev* set = nullptr, i32* ctimes = nullptr) {
+  return with_run_class<LIB>(k, [&](auto cls) {
+    RunSim<decltype(cls)::value> s(p, state, i);
+    if constexpr (s.PSET) s.load_set(*set);
+    if constexpr (s.CTIME) s.attach_commit_times(ctimes, i * p.n);
+    return run_one(s, p, fill);
+  });
+}
+
 // The committed history of `node` (up to `cap` entries into `out`, a lbft_commit / lbft_oracle_commit array or NULL) and the Sip13
 // State over it, as lbft_k_finalize computes it -> commit count.  `s`: the instance, scalars loaded.
 template <class Commit>

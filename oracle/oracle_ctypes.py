@@ -4,6 +4,7 @@ TEST INFRASTRUCTURE: imported only by tests/, __graft_entry__.smoke() and bench.
 leg.  The product package (librabft_simulator_amd/) never imports this module.
 """
 import ctypes as C
+import itertools
 import os
 import subprocess
 
@@ -509,6 +510,21 @@ def plan(cfg, n_instances, max_clock, queue_capacity=0, snapshot_capacity=0, blo
     d = {n: getattr(out, n) for n, _ in HostModelPlan._fields_}
     d["layout"] = [int(v) for v in out.layout]
     return d
+
+
+class HostModelRunKernel(C.Structure):
+    """RunKernelInfo, a row of csrc/lbft_plan.h's table of run kernels."""
+    _fields_ = [("name", C.c_char_p), ("cls", C.c_int), ("two_wave", C.c_bool), ("flags", C.c_uint32), ("lib", C.c_int)]
+
+
+def run_kernels():
+    """The table of run kernels of csrc/lbft_plan.h, one dict per row in RunKernel's order (a plan's ``kernel`` indexes it): ``name`` as
+    the codegen manifest prints it (lbft_k_run0q, lbft_k_run<1>, lbft_k_ps_run0 ...), ``cls`` the KernelClass of its step, ``two_wave``,
+    ``flags`` its bits 10-17 of lbft_batch_layout's flag word, ``lib`` the index of its library in librabft_simulator_amd.build.TABLE."""
+    row = hostmodel_lib().lbft_hostmodel_run_kernel
+    row.argtypes, row.restype = [C.c_uint32], C.POINTER(HostModelRunKernel)
+    rows = (p.contents for p in itertools.takewhile(bool, map(row, itertools.count())))
+    return [dict(name=r.name.decode(), cls=r.cls, two_wave=r.two_wave, flags=r.flags, lib=r.lib) for r in rows]
 
 
 def manual_caps(num_nodes, quirks, max_clock, snapshot_capacity=0, keep_stores=0, block_capacity=0):

@@ -9,14 +9,6 @@
 
 using namespace lbft;
 
-template <int KCLS>
-static void run_timed(const Params& p, u32* state, u32 i, const ParamSetDev* set, i32* ctimes, u32 state_fill) {
-  SimTTimed<KCLS> s(p, state, i);
-  if constexpr (SimT<KCLS>::PSET) s.load_set(*set);
-  s.attach_commit_times(ctimes, i * p.n);
-  run_one(s, p, state_fill);
-}
-
 extern "C" {
 
 // A batch of `base` (n_sets == 0: a plain batch) or of parameter sets over `base`, run to max_clock with commit times recorded.
@@ -33,6 +25,7 @@ int ct_hostmodel_run(const lbft_config* base, const lbft_param_set* sets, uint32
   if (cls < 0) return cls;
   const Params& p = tb.p;
   const std::vector<ParamSetDev>& dev = tb.dev;
+  const RunKernel kernel = pick_run_kernel(p, n_sets != 0, true, PlanKnobs());
   // state_fill: the word the state rows and the emulated LDS hold before Simulator::new runs (0 = fresh pages; these classes never use the
   // calendar queue, the one region the device's host code clears before a run)
   std::vector<u32> state(state_words(p), state_fill);
@@ -41,12 +34,8 @@ int ct_hostmodel_run(const lbft_config* base, const lbft_param_set* sets, uint32
   auto worker = [&](u32 tid) {
     for (size_t i = tid; i < m; i += threads) {
       const ParamSetDev* d = n_sets ? &dev[set_of[i]] : nullptr;
-      if (n_sets) { SimTSets<K_GENERIC_SETS> s0(p, state.data(), (u32)i); s0.load_set(*d); s0.init(seeds[i]); }
-      else { Sim s0(p, state.data(), (u32)i); s0.init(seeds[i]); }
-      if (n_sets && cls == K_SMALL) run_timed<K_SMALL_SETS_TIMED>(p, state.data(), (u32)i, d, ct.data(), state_fill);
-      else if (n_sets) run_timed<K_MID_SETS_TIMED>(p, state.data(), (u32)i, d, ct.data(), state_fill);
-      else if (cls == K_SMALL) run_timed<K_SMALL_TIMED>(p, state.data(), (u32)i, nullptr, ct.data(), state_fill);
-      else run_timed<K_MID_TIMED>(p, state.data(), (u32)i, nullptr, ct.data(), state_fill);
+      init_instance(p, state.data(), (u32)i, seeds[i], d);
+      run_instance<LIB_COMMIT_TIMES>(kernel, p, state.data(), (u32)i, state_fill, d, ct.data());
     }
   };
   std::vector<std::thread> ts;

@@ -24,16 +24,15 @@ int ps_hostmodel_run(const lbft_config* base, const lbft_param_set* sets, uint32
   if (cls < 0) return cls;
   const Params& p = tb.p;
   const std::vector<ParamSetDev>& dev = tb.dev;
+  const RunKernel kernel = pick_run_kernel(p, true, false, PlanKnobs());
   // state_fill: the word the state rows and the emulated LDS hold before Simulator::new runs (0 = fresh pages; these classes never use the
   // calendar queue, the one region the device's host code clears before a run)
   std::vector<u32> state(state_words(p), state_fill);
   if (threads == 0) threads = 1;
   auto worker = [&](u32 tid) {
     for (size_t i = tid; i < m; i += threads) {
-      const ParamSetDev& d = dev[set_of[i]];
-      { SimTSets<K_GENERIC_SETS> s0(p, state.data(), (u32)i); s0.load_set(d); s0.init(seeds[i]); }
-      if (cls == K_SMALL) { SimTSets<K_SMALL_SETS> s(p, state.data(), (u32)i); s.load_set(d); run_one(s, p, state_fill); }
-      else { SimTSets<K_MID_SETS> s(p, state.data(), (u32)i); s.load_set(d); run_one(s, p, state_fill); }
+      init_instance(p, state.data(), (u32)i, seeds[i], &dev[set_of[i]]);
+      run_instance<LIB_PARAMSETS>(kernel, p, state.data(), (u32)i, state_fill, &dev[set_of[i]]);
     }
   };
   std::vector<std::thread> ts;

@@ -5,16 +5,21 @@ the device rows of tests/test_kernel_switches_gpu.py, which takes the flag word 
 A batch: ``kw`` = the configuration in oracle_ctypes.make_config's spelling, ``max_clock``, ``caps`` = the capacities both the planner
 and the device library are given (0 / absent = automatic)."""
 
-# RunKernel of csrc/lbft_plan.h, in the enum's order
-RUN_KERNELS = ("run0", "run0q", "run0s", "run0u", "run1l", "run1", "run2l", "run2q", "run2", "ps_run0", "ps_run1", "ct_run0", "ct_run1",
-               "ct_ps_run0", "ct_ps_run1")
-RK = {name: k for k, name in enumerate(RUN_KERNELS)}
-
-# bits 10-17 of lbft_batch_layout's flag word that name the kernel (include/lbft.h; lbft_plan.h run_kernel_info)
-KERNEL_FLAGS = dict(run0=0, run0q=1 << 14, run0s=1 << 13, run0u=(1 << 13) | (1 << 15), run1l=1 << 10, run1=0, run2l=1 << 10,
-                    run2q=(1 << 10) | (1 << 12), run2=0, ps_run0=1 << 16, ps_run1=1 << 16, ct_run0=1 << 17, ct_run1=1 << 17,
-                    ct_ps_run0=(1 << 16) | (1 << 17), ct_ps_run1=(1 << 16) | (1 << 17))
 HEAP, CALENDAR, RING = 1 << 8, 1 << 9, 1 << 11
+
+
+def __getattr__(name):
+    """RUN_KERNELS (short names -- run0q, run1 for lbft_k_run<1>, ps_run0 -- indexed by a plan's ``kernel``), RK (name -> that index) and
+    KERNEL_FLAGS (name -> the bits 10-17 of lbft_batch_layout's flag word that name the kernel): the rows of csrc/lbft_plan.h's table of
+    run kernels, read from the host-model library when a test first asks."""
+    if name not in ("RUN_KERNELS", "RK", "KERNEL_FLAGS"):
+        raise AttributeError(name)
+    import oracle_ctypes
+    rows = oracle_ctypes.run_kernels()
+    short = tuple(r["name"][len("lbft_k_"):].replace("<", "").replace(">", "") for r in rows)
+    globals().update(RUN_KERNELS=short, RK={n: k for k, n in enumerate(short)}, KERNEL_FLAGS={n: r["flags"] for n, r in zip(short, rows)})
+    return globals()[name]
+
 
 NO_QUAD, NO_POPC, NO_UNI, NO_LEAN = (dict([(name, "1")]) for name in ("LBFT_NO_QUAD", "LBFT_NO_POPC", "LBFT_NO_UNI", "LBFT_NO_LEAN"))
 LEAN2_OFF = dict(LBFT_LEAN2="0")

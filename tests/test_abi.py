@@ -196,6 +196,22 @@ def test_side_kernels_carry_their_prefix_and_stay_out_of_every_other_library(hip
             assert tag == lib.tag or not any(lib.prefix in k for k in names), (lib.prefix, tag, names)
 
 
+@pytest.mark.skipif(not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf"), reason="needs the ROCm LLVM binutils")
+def test_table_of_run_kernels_names_the_run_kernels_of_the_built_libraries(hiplib, oracle):
+    """csrc/lbft_plan.h's table against the binaries: every row's name is a kernel of the row's library, and no library holds a run
+    kernel the table lacks."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import kernel_manifest
+    from librabft_simulator_amd import build
+    rows = oracle.run_kernels()
+    for k, lib in enumerate(build.TABLE):
+        built = {kernel_manifest.short(name) for name in _kernel_metadata(lib.out)}
+        in_table = {r["name"] for r in rows if r["lib"] == k}
+        assert in_table == {name for name in built if "_run" in name}, (lib.tag, sorted(in_table), sorted(built))
+    assert len({r["name"] for r in rows}) == len(rows) == 15 and {r["lib"] for r in rows} == {0, 1, 2}
+
+
 def test_table_names_the_files_and_launchers_the_host_code_opens():
     """The Python table cannot drift from csrc: the side libraries' file names are the LBFT_*_LIB macros of their headers, the launchers
     the strings lbft_hip.hip passes to load_side_lib."""
@@ -265,6 +281,13 @@ def test_kernel_names_from_the_layout_flag_word():
                      (2 | 256 | 512 | 1024 | 2048, "lbft_k_run2l"), (2 | 256 | 512 | 1024 | 2048 | 4096, "lbft_k_run2q")):
         assert bench.run_kernel_name(kc) == name
         assert configs.kernel_name({"kernel_class": kc}) == name
+    # ... and every row of csrc/lbft_plan.h's table of run kernels, its word put together from the size class in its name and its flag
+    # bits: the decoders know the main library's kernels; a twin (bits 16 / 17) reads as the plain kernel whose geometry it borrows
+    import oracle_ctypes
+    for r in oracle_ctypes.run_kernels():
+        size = int(re.search(r"run<?(\d)", r["name"]).group(1))
+        want = r["name"] if r["lib"] == 0 else ("lbft_k_run0", "lbft_k_run<1>")[size]
+        assert bench.run_kernel_name(size | r["flags"]) == configs.kernel_name({"kernel_class": size | r["flags"]}) == want, r
 
 
 def test_hip_soname_reader_reads_only_the_dynamic_section_and_refuses_garbage(hiplib, tmp_path):

@@ -143,3 +143,9 @@ def test_quantile_rule_is_numpy_inverted_cdf():
             assert histogram_quantile(hist, 1, q) == int(np.quantile(x, q, method="inverted_cdf")), (trial, q)
     assert histogram_quantile(np.zeros(4, dtype=np.uint64), 1, 0.5) is None
     assert histogram_quantile(np.array([0, 3, 1]), 5, 0.9) == 10  # (bin k starts at k * width)
+
+
+@pytest.mark.parametrize("equivocate_every,n_sets", [(0, 0), (0, 2), (3, 0), (3, 2)], ids=["class0", "class0-sets", "class1", "class1-sets"])
+def test_returned_class_is_the_one_from_before_the_table_of_run_kernels(harness, equivocate_every, n_sets):
+    from test_host_dispatch import TWIN_CLASS, twin_batch
+    assert run_host(harness, *twin_batch(equivocate_every, n_sets), 0, 4)[0] == TWIN_CLASS[equivocate_every, n_sets]

@@ -101,3 +101,9 @@ def test_mixed_set_batches_equal_the_oracle_per_instance(harness, oracle):
             configs += 1
     assert classes == {0, 1}, classes  # both the small and the mid class ran
     assert compared >= 500, compared
+
+
+@pytest.mark.parametrize("equivocate_every", [0, 3], ids=["class0", "class1"])
+def test_returned_class_is_the_one_from_before_the_table_of_run_kernels(harness, equivocate_every):
+    from test_host_dispatch import TWIN_CLASS, twin_batch
+    assert run_host(harness, *twin_batch(equivocate_every, 2), 0, 4)[0] == TWIN_CLASS[equivocate_every, 2]
