@@ -391,6 +391,47 @@ int lbft_batch_round_switches_all(const lbft_batch* b, int64_t* out, size_t cap_
 #define LBFT_CHAIN_STATS 24
 int lbft_batch_chain_stats(const lbft_batch* b, uint32_t bin_width, uint32_t bins, uint64_t* interval_hist, uint64_t* author_blocks, uint64_t* stats);
 
+/* Commit finality: when is an entry final in the network -- committed by the first node, by nodes holding a quorum of the voting rights,
+ * by every node -- per group, computed on the device from the recorded commit times, the commit logs, the block pool, the startup times,
+ * the voting rights and the fault words.  The per-node statistics (latency histogram, timelines) never look across the nodes of one
+ * entry; this call does.  It applies to a batch that records commit times.  For instance i without a fault (a non-zero fault word skips
+ * the instance):
+ *   nc_j, the reference node `ref` and L = nc_ref are those of the chain statistics (lbft_batch_chain_stats above).
+ *   Entry k < L is block b_k = log[ref][k]; its proposal time g_k = startup[author of b_k] + time of b_k (the quantity the latency
+ *   histogram subtracts).
+ *   Node j is a committer of k if k < nc_j and its recorded commit time c_j(k) >= 0.
+ *   Voting rights at k: w_j(k) = voting_rights[(j + e_k * rights_rotation) % num_nodes] with e_k = k / commands_per_epoch (the rule of
+ *   rights_rotation above: a chain's blocks of epoch e have depths e * commands_per_epoch + 1 .. (e + 1) * commands_per_epoch, so the
+ *   entry's index gives its block's epoch).  With unit rights every w_j is 1.
+ *   For a threshold T, time_T(k) is the smallest t such that the committers with c_j(k) <= t hold voting rights of at least T; nodes with
+ *   equal times count together.  It is undefined if all committers together hold less than T.  With total = the sum of the voting rights
+ *   and quorum = 2 * total / 3 + 1:
+ *     first:  the minimum of the committers' times (T = 1 when every right is positive); defined with at least one committer
+ *     valid:  T = total - quorum + 1, so that at least one honest node is among the committers
+ *     quorum: T = quorum
+ *     all:    defined only when all num_nodes nodes are committers, and then the maximum of their times.
+ * Groups are those of the latency histogram (the parameter sets, or one group for a plain batch).  Six sample families, each reported as
+ * stats[g * LBFT_FINALITY_STATS + 4 * family + {0, 1, 2, 3}] = samples, sum, min, max (min = max = 0 without samples):
+ *   family 0, first:  time_first(k) - g_k, one sample per entry with at least one committer
+ *   family 1, valid:  time_valid(k) - g_k, one sample per entry where it is defined
+ *   family 2, quorum: time_quorum(k) - g_k, one sample per entry where it is defined; also binned,
+ *                     finality_hist[g * bins + min(sample / bin_width, bins - 1)]
+ *   family 3, all:    time_all(k) - g_k, one sample per entry every node committed
+ *   family 4, spread: time_all(k) - time_first(k), the same entries as family 3; also binned into spread_hist in the same way
+ *   family 5, open:   one sample per instance, the number of k < L with at least one committer whose time_quorum(k) is undefined: the
+ *                     chain's tip that is not yet final when the run ends
+ * Every sample lies in [0, max_clock]; nothing is clamped (a commit time before its entry's proposal time would show as a sample above
+ * max_clock).  first_committer[g * num_nodes + j] = the entries for which j is the lowest-numbered committer with c_j(k) ==
+ * time_first(k); a group's row sums to family 0's sample count.
+ * bin_width >= 1, bins >= 1, groups * bins <= 2^31 (LBFT_ERR_INVALID otherwise, and for NULL arguments, before any HIP call);
+ * LBFT_ERR_STATE when the batch does not record commit times, or before a finished run (lbft_batch_run_until, lbft_batch_run_steps once
+ * it reports 0, also on a timed batch that loaded a checkpoint).  The call changes no state.  Computed on the device
+ * (lbft_k_ct_finality, liblbft_commit_times.so; the arithmetic is csrc/lbft_commit_finality.h); every accumulation is an integer add, min
+ * or max: bit-reproducible. */
+#define LBFT_FINALITY_STATS 24
+int lbft_batch_commit_finality(const lbft_batch* b, uint32_t bin_width, uint32_t bins, uint64_t* finality_hist, uint64_t* spread_hist,
+                               uint64_t* first_committer, uint64_t* stats);
+
 /* Record hashes of every committed chain of a batch in one device call: what lbft_batch_committed_record_hashes gives for one
  * (instance, node), for the chain of every instance.  The nodes of an instance share one block pool (equal id = equal block = equal
  * QC) and every history is a prefix of its instance's chain (chain statistics, family 4), so an instance's records are hashed once.

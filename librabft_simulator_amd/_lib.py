@@ -73,6 +73,7 @@ class LbftParamSet(C.Structure):
 MAX_PARAM_SETS = 256  # LBFT_MAX_PARAM_SETS
 STALL_STATS = 16  # LBFT_STALL_STATS: (samples, sum, min, max) of the gaps / first / tail / longest families
 ROUND_STATS = 16  # LBFT_ROUND_STATS: (samples, sum, min, max) of the stay / skipped / skew / reach families
+FINALITY_STATS = 24  # LBFT_FINALITY_STATS: (samples, sum, min, max) of the first / valid / quorum / all / spread / open families
 CHAIN_STATS = 24  # LBFT_CHAIN_STATS: (samples, sum, min, max) of the interval / length / lag / tenure / differing / inversions families
 
 
@@ -143,7 +144,7 @@ CHAIN_HEAD_DTYPE = np.dtype([("block_hash", "<u8"), ("state", "<u8"), ("qc_hash"
 # every symbol include/lbft.h declares (tests check that the library exports all of them)
 ABI_SYMBOLS = [
     "lbft_batch_create", "lbft_batch_create_param_sets", "lbft_batch_record_commit_times", "lbft_batch_commit_times",
-    "lbft_batch_commit_latency_histogram", "lbft_batch_commit_series", "lbft_batch_commit_stalls", "lbft_batch_run_until", "lbft_batch_reset", "lbft_batch_commit_counts",
+    "lbft_batch_commit_latency_histogram", "lbft_batch_commit_series", "lbft_batch_commit_stalls", "lbft_batch_commit_finality", "lbft_batch_run_until", "lbft_batch_reset", "lbft_batch_commit_counts",
     "lbft_batch_active_rounds", "lbft_batch_committed_history", "lbft_batch_committed_histories", "lbft_batch_committed_record_hashes",
     "lbft_batch_last_committed_states", "lbft_batch_last_committed_state", "lbft_batch_save_node", "lbft_batch_load_node", "lbft_batch_startup_times", "lbft_batch_epochs", "lbft_batch_counters",
     "lbft_batch_faults", "lbft_batch_destroy", "lbft_batch_stream", "lbft_batch_last_run_ms",
@@ -264,6 +265,8 @@ def lib():
     L.lbft_batch_commit_series.restype = C.c_int
     L.lbft_batch_commit_stalls.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, vp]
     L.lbft_batch_commit_stalls.restype = C.c_int
+    L.lbft_batch_commit_finality.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
+    L.lbft_batch_commit_finality.restype = C.c_int
     L.lbft_batch_run_until.argtypes = [vp, C.c_int64]
     L.lbft_batch_run_until.restype = C.c_int
     L.lbft_batch_reset.argtypes = [vp]

@@ -32,6 +32,14 @@ typedef hipError_t (*lbft_ct_timeline_fn)(const lbft::Params* p, const lbft::u32
                                           const lbft::u32* grp_off, lbft::u32 n_groups, lbft::u32 max_group, int stalls,
                                           const lbft::i32* since_of, lbft::u32 bin_width, lbft::u32 bins, unsigned long long* hist,
                                           unsigned long long* stats, hipStream_t stream);
+// Commit finality of a finished run (lbft_k_ct_finality; groups as above, every output zeroed by the caller): per entry of an instance's
+// chain the times at which the first node, nodes holding `valid` and `quorum` voting rights and every node had committed it
+// (lbft_commit_finality.h; include/lbft.h: lbft_batch_commit_finality).  finality_hist / spread_hist[group * bins + bin],
+// first_committer[group * p->n + node], stats[group * LBFT_FINALITY_STATS + family * 4 + {samples, sum, ~min, max}].  p->n <= 32.
+typedef hipError_t (*lbft_ct_finality_fn)(const lbft::Params* p, const lbft::u32* state, const lbft::i32* ctimes, const lbft::u32* grp_inst,
+                                          const lbft::u32* grp_off, lbft::u32 n_groups, lbft::u32 max_group, lbft::u32 bin_width, lbft::u32 bins,
+                                          unsigned long long* finality_hist, unsigned long long* spread_hist, unsigned long long* first_committer,
+                                          unsigned long long* stats, hipStream_t stream);
 }
 
 #endif  // LBFT_COMMIT_TIMES_H

@@ -5,7 +5,8 @@
 // commit-time buffer ([instance][node][lcap] i32, the log's index).  Their run body (lbft_run_body.h) and LDS layout (lbft_launch.h) are
 // those of lbft_k_run0 / lbft_k_run<1> and the parameter-set kernels, so the host side of liblbft_hip.so sizes them as those.
 // The histogram kernel turns a finished run's logs and commit times into commit-latency histograms per group (parameter set); the
-// timeline kernel turns the commit times alone into commits over time and the statistics of the commit-free intervals.
+// timeline kernel turns the commit times alone into commits over time and the statistics of the commit-free intervals; the finality
+// kernel looks across the nodes of every chain entry: when the first node, a quorum of the voting rights and every node committed it.
 // Built as a library of its own (build.py): the code object of liblbft_hip.so, whose kernels are pinned byte for byte by the codegen
 // manifest, does not change.
 #include <hip/hip_runtime.h>
@@ -14,6 +15,8 @@
 #include "lbft_core.h"
 #include "lbft_commit_times.h"
 #include "lbft_commit_timeline.h"
+#include "lbft_chain_rules.h"
+#include "lbft_commit_finality.h"
 
 using namespace lbft;
 
@@ -189,6 +192,109 @@ __global__ __launch_bounds__(LBFT_TL_BLOCK) void lbft_k_ct_timeline(Params p, co
   }
 }
 
+// Commit finality (lbft_batch_commit_finality): per entry of an instance's chain, the commit times of all its nodes -- an order
+// statistic under the voting rights (lbft_commit_finality.h).  One wavefront per instance, through the generic Sim accessors (timed
+// batches: instance-major rows or 64-wide tiles).
+//   node pass (lane = node, n <= LBFT_FN_MAX_NODES): nc_j = min(NF_NCOMMITS, lcap); a butterfly over the keys (nc_j, ~j) gives the
+//     chain's length L and the reference node, as in lbft_k_cs_chain.
+//   chain pass (lane = entry, 64 at a time): the n rows ctimes[i][j][c0 .. c0 + 63] -- a row load of the wavefront is 256 contiguous
+//     bytes -- go into the wavefront's [n][64] LDS tile, FIN_NONE where the node is no committer of the entry; b = log[ref][k] and the
+//     dependent gathers B_LINK, B_TIME and startup[author] give the proposal time g_k.  Each lane then walks its own column of the tile
+//     (fin_entry: n^2 LDS reads at consecutive addresses across the lanes, no bank conflict, no sort, no per-lane array).  A lane reads
+//     only what it wrote itself: the tile needs no barrier.
+// The rights table (at most LBFT_FN_MAX_NODES words) is copied into LDS once per workgroup; with unit rights it is not read.
+// grid = (workgroups per group, groups); a workgroup's LBFT_FN_WAVES wavefronts stride over the instances of its group and accumulate by
+// the scheme of lbft_group_stats.h: two LDS histograms (quorum finality and spread) in passes of LBFT_FN_LDS_BINS bins, the first
+// committers (n bins) in the first pass, the statistics in registers in the first pass.  Instances with a non-zero fault word are
+// skipped.  LDS: tile 4 x 32 x 64 x 4 B = 32 KiB, histograms 2 x 16 KiB, 128 B first committers, 128 B rights, 192 B statistics:
+// 65 984 B, two workgroups per CU.
+#define LBFT_FN_BLOCK 256
+#define LBFT_FN_WAVES (LBFT_FN_BLOCK / 64)
+#define LBFT_FN_MAX_NODES 32  // (timed batches have at most 32 nodes: lbft_batch_record_commit_times)
+#define LBFT_FN_LDS_BINS 4096  // each of the two histograms: 16 KiB of u32 counts
+#define LBFT_FN_WORKGROUPS 1024u
+static_assert(LBFT_FINALITY_STATS == FIN_FAMILIES * 4, "six families of (samples, sum, min, max)");
+
+__global__ __launch_bounds__(LBFT_FN_BLOCK) void lbft_k_ct_finality(Params p, const u32* __restrict__ state, const i32* __restrict__ ctimes,
+                                                                    const u32* __restrict__ grp_inst, const u32* __restrict__ grp_off,
+                                                                    u32 bin_width, u32 bins, unsigned long long* __restrict__ finality_hist,
+                                                                    unsigned long long* __restrict__ spread_hist,
+                                                                    unsigned long long* __restrict__ first_committer,
+                                                                    unsigned long long* __restrict__ stats) {
+  __shared__ i32 tile[LBFT_FN_WAVES][LBFT_FN_MAX_NODES][64];
+  __shared__ u32 h_fin[LBFT_FN_LDS_BINS], h_spr[LBFT_FN_LDS_BINS], h_fc[LBFT_FN_MAX_NODES], s_rights[LBFT_FN_MAX_NODES];
+  __shared__ unsigned long long s_stat[LBFT_FINALITY_STATS];
+  const u32 g = blockIdx.y;
+  const uint2 grp = gs_group(grp_inst, grp_off, g, p.m);
+  const u32 first = grp.x, cnt = grp.y;
+  if (blockIdx.x * LBFT_FN_WAVES >= cnt) return;  // (the whole workgroup: its group has fewer instances)
+  const u32 wave = threadIdx.x / 64, lane = threadIdx.x % 64;
+  const u32 n = p.n, lcap = p.lcap, lg = p.off_log;
+  const u32 cpe = fin_cpe32(p.cpe), rot = p.rot;
+  const u32 t_quorum = p.quorum, t_valid = fin_valid_threshold(p.total_votes, p.quorum);
+  const u32* rights = p.unit_weights ? nullptr : s_rights;
+  i32* col = &tile[wave][0][lane];  // this lane's column: node j at col[j * 64]
+  if (threadIdx.x < n) s_rights[threadIdx.x] = p.weights[threadIdx.x];  // (read after the pass loop's first barrier)
+  gs_stats_clear<LBFT_FINALITY_STATS>(s_stat);
+  GsStat st[FIN_FAMILIES] = {};
+  for (u32 base = 0; base < bins; base += LBFT_FN_LDS_BINS) {
+    const u32 span = bins - base < LBFT_FN_LDS_BINS ? bins - base : LBFT_FN_LDS_BINS;
+    const bool stat_pass = base == 0;
+    gs_lds_clear<LBFT_FN_BLOCK>(h_fin, span);
+    gs_lds_clear<LBFT_FN_BLOCK>(h_spr, span);
+    if (stat_pass) gs_lds_clear<LBFT_FN_BLOCK>(h_fc, n);
+    __syncthreads();
+    for (u32 q = blockIdx.x * LBFT_FN_WAVES + wave; q < cnt; q += gridDim.x * LBFT_FN_WAVES) {  // (one instance per wavefront: uniform in it)
+      const u32 i = gs_instance(grp_inst, first, q);
+      Sim s(p, const_cast<u32*>(state), i);
+      if (s.ld(I_FAULT) != 0) continue;
+      // node pass
+      const u32 nc = lane < n ? chn_commits(s.nfm(lane, NF_NCOMMITS), lcap) : 0;
+      u64 best = lane < n ? chn_ref_key(nc, lane) : 0;
+      for (int d = 32; d; d >>= 1) best = chn_ref_max(best, (u64)__shfl_xor((unsigned long long)best, d, 64));
+      const u32 L = chn_ref_len(best), ref = chn_ref_node(best);
+      // chain pass
+      u32 open = 0;
+      for (u32 c0 = 0; c0 < L; c0 += 64) {
+        const u32 k = c0 + lane;
+        const bool have = k < L;
+        for (u32 j = 0; j < n; j++) {
+          const u32 ncj = (u32)__shfl((int)nc, (int)j, 64);
+          const i32 c = k < ncj ? ctimes[((size_t)i * n + j) * lcap + k] : FIN_NONE;  // (k < nc_j <= lcap: inside the row)
+          col[j * 64] = fin_committer(k, ncj, c) ? c : FIN_NONE;
+        }
+        if (!have) continue;
+        const u32 b = s.ld(lg + ref * lcap + k);
+        const u32 a = s.blk_author(b);
+        const i32 gt = (i32)(s.nfm(a, NF_STARTUP) + s.bf(b, B_TIME));
+        const FinEntry e = fin_entry(col, 64u, n, rights, fin_rights_shift(k, cpe, rot, n), t_valid, t_quorum);
+        const i32 all = fin_all(e, n);
+        if (e.quorum >= 0) gs_lds_count(h_fin, fin_after(e.quorum, gt), bin_width, bins, base, span);
+        if (all >= 0) gs_lds_count(h_spr, fin_after(all, e.first), bin_width, bins, base, span);
+        if (!stat_pass) continue;
+        if (e.committers) { gs_stat_add(st[FIN_FIRST], fin_after(e.first, gt)); gs_lds_count(h_fc, e.first_node, 1u, n, 0u, n); }
+        if (e.valid >= 0) gs_stat_add(st[FIN_VALID], fin_after(e.valid, gt));
+        if (e.quorum >= 0) gs_stat_add(st[FIN_QUORUM], fin_after(e.quorum, gt));
+        if (all >= 0) { gs_stat_add(st[FIN_ALL], fin_after(all, gt)); gs_stat_add(st[FIN_SPREAD], fin_after(all, e.first)); }
+        open += fin_open(e) ? 1u : 0u;
+      }
+      if (stat_pass) {
+        for (int d = 32; d; d >>= 1) open += (u32)__shfl_xor((int)open, d, 64);
+        if (lane == 0) gs_stat_add(st[FIN_OPEN], open);  // one sample per instance
+      }
+    }
+    if (stat_pass) gs_reduce_to_lds<FIN_FAMILIES>(st, s_stat, lane == 0);
+    __syncthreads();
+    gs_lds_flush<LBFT_FN_BLOCK>(h_fin, finality_hist, g, bins, base, span);
+    gs_lds_flush<LBFT_FN_BLOCK>(h_spr, spread_hist, g, bins, base, span);
+    if (stat_pass) {
+      gs_lds_flush<LBFT_FN_BLOCK>(h_fc, first_committer, g, n, 0u, n);
+      gs_stats_out<LBFT_FINALITY_STATS>(s_stat, stats, g);
+    }
+    __syncthreads();  // (before the next pass clears the histograms)
+  }
+}
+
 extern "C" {
 
 __attribute__((visibility("default"))) hipError_t lbft_ct_launch_run(int cls, const Params* p, u32* state, u32* unfinished, const ParamSetDev* sets,
@@ -219,6 +325,21 @@ __attribute__((visibility("default"))) hipError_t lbft_ct_launch_timeline(const 
   const u64 gx = gs_workgroups(LBFT_TL_WORKGROUPS, n_groups, (rows + LBFT_TL_ROWS - 1) / LBFT_TL_ROWS, rows * p->lcap);
   lbft_k_ct_timeline<<<dim3((u32)gx, n_groups), LBFT_TL_BLOCK, 0, stream>>>(*p, state, ctimes, grp_inst, grp_off, stalls, since_of, bin_width, bins, hist,
                                                                           stats);
+  return hipGetLastError();
+}
+
+__attribute__((visibility("default"))) hipError_t lbft_ct_launch_finality(const Params* p, const u32* state, const i32* ctimes, const u32* grp_inst,
+                                                                         const u32* grp_off, u32 n_groups, u32 max_group, u32 bin_width, u32 bins,
+                                                                         unsigned long long* finality_hist, unsigned long long* spread_hist,
+                                                                         unsigned long long* first_committer, unsigned long long* stats,
+                                                                         hipStream_t stream) {
+  if (bin_width == 0 || bins == 0 || n_groups == 0 || max_group == 0 || p->n > LBFT_FN_MAX_NODES || !ctimes || !finality_hist || !spread_hist ||
+      !first_committer || !stats)
+    return hipErrorInvalidValue;
+  // (an instance of the largest group gives at most lcap samples to a bin of a histogram)
+  const u64 gx = gs_workgroups(LBFT_FN_WORKGROUPS, n_groups, ((u64)max_group + LBFT_FN_WAVES - 1) / LBFT_FN_WAVES, (u64)max_group * p->lcap);
+  lbft_k_ct_finality<<<dim3((u32)gx, n_groups), LBFT_FN_BLOCK, 0, stream>>>(*p, state, ctimes, grp_inst, grp_off, bin_width, bins, finality_hist, spread_hist,
+                                                                         first_committer, stats);
   return hipGetLastError();
 }
 

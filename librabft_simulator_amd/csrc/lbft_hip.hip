@@ -465,9 +465,10 @@ static int launch_init(lbft_batch* b, u32 grid_init) {
 static lbft_ct_run_fn g_ct_run = nullptr;
 static lbft_ct_hist_fn g_ct_hist = nullptr;
 static lbft_ct_timeline_fn g_ct_timeline = nullptr;
+static lbft_ct_finality_fn g_ct_finality = nullptr;
 static int load_commit_times_lib() {
   return load_side_lib(LBFT_COMMIT_TIMES_LIB, "commit times", {{"lbft_ct_launch_run", (void**)&g_ct_run}, {"lbft_ct_launch_histogram", (void**)&g_ct_hist},
-                                                               {"lbft_ct_launch_timeline", (void**)&g_ct_timeline}});
+                                                               {"lbft_ct_launch_timeline", (void**)&g_ct_timeline}, {"lbft_ct_launch_finality", (void**)&g_ct_finality}});
 }
 // A run starts with every entry unrecorded (-1)
 static int fill_commit_times(lbft_batch* b) {
@@ -1305,6 +1306,23 @@ int lbft_batch_commit_series(const lbft_batch* b, uint32_t bin_width, uint32_t b
 int lbft_batch_commit_stalls(const lbft_batch* b, const int64_t* since, uint32_t bin_width, uint32_t bins, uint64_t* hist, uint64_t* stats) {
   int rc = refuse_grouped(b, hist && stats, bin_width, bins, true);
   return rc != LBFT_OK ? rc : commit_timeline(b, since, bin_width, bins, hist, stats, "commit stalls");
+}
+
+// Commit finality per group, computed on the device from the commit-time rows, the reference node's log, the block pool, the startup
+// times and the voting rights (lbft_k_ct_finality): when the first node, a quorum of the voting rights and every node had committed an
+// entry.  Arguments are checked before the first HIP call; the call changes no state of the batch.
+int lbft_batch_commit_finality(const lbft_batch* b, uint32_t bin_width, uint32_t bins, uint64_t* finality_hist, uint64_t* spread_hist,
+                               uint64_t* first_committer, uint64_t* stats) {
+  int rc = refuse_grouped(b, finality_hist && spread_hist && first_committer && stats, bin_width, bins, true);
+  if (rc != LBFT_OK) return rc;
+  const size_t groups = group_count(b);
+  HIP_TRY(hipSetDevice(b->device));
+  GroupedCall gc(b);
+  unsigned long long *d_fin = gc.out(finality_hist, groups * bins), *d_spr = gc.out(spread_hist, groups * bins);
+  unsigned long long *d_fc = gc.out(first_committer, groups * b->p.n), *d_stats = gc.out(stats, groups * LBFT_FINALITY_STATS, true);
+  if (gc.e == hipSuccess) gc.e = g_ct_finality(&b->p, b->d_state, b->d_ctimes, gc.d_inst, gc.d_off, (u32)groups, gc.gi.max_group, bin_width, bins, d_fin, d_spr, d_fc,
+                                               d_stats, b->stream);
+  return gc.finish("commit finality");
 }
 
 // ---- round statistics (lbft_batch_round_stats) ----

@@ -16,6 +16,9 @@ ticks (BatchResult.commit_series).
 instance that passes it counts as faulted and gives no sample) and adds a ``"round_stats"`` object (BatchResult.rounds_by_param_set: how
 long nodes stay in a round, how many rounds they jump, how far apart the nodes of a network enter a round and how many of them enter it);
 ``"rounds"``, the final active round's mean / min / max, stays as it is.
+``--finality`` records commit times and adds a ``"finality"`` object (BatchResult.finality_by_param_set: how long after its proposal an
+entry is committed by the first node, by a quorum of the voting rights and by every node, the spread between the first and the last
+commit, which node commits first and how many entries no quorum had committed at the end).
 ``--chain`` adds a ``"chain"`` object (BatchResult.chain_by_param_set: the intervals between the proposals of consecutive blocks of the
 committed chain, its length, the nodes' lag behind it, the leaders' tenure, the blocks per proposer and whether every node's history is
 a prefix of the chain); it needs neither commit times nor the trace and leaves the batch on the kernel it would run anyway.
@@ -103,6 +106,7 @@ def main(argv=None):
     ap.add_argument("--partition", type=_partitions, default=None, help="grid axis: SIZE:START:END[,...], 'none' allowed as a value")
     ap.add_argument("--stalls", action="store_true", help="record commit times and add each point's stall / recovery summary")
     ap.add_argument("--series", type=int, default=None, metavar="WIDTH", help="record commit times and add each point's commits per WIDTH ticks")
+    ap.add_argument("--finality", action="store_true", help="record commit times and add each point's commit-finality summary")
     ap.add_argument("--rounds", action="store_true", help="record the round-switch trace and add each point's round statistics")
     ap.add_argument("--chain", action="store_true", help="add each point's chain statistics (agreement, chain quality, block cadence)")
     ap.add_argument("--round-trace", type=int, default=None, metavar="N", help="with --rounds: rounds per node the trace keeps")
@@ -121,13 +125,14 @@ def main(argv=None):
                      drop_per_million=pt["drop_per_million"], partition=pt.get("partition")) for pt in points]
     set_of, seed_index = set_assignment(len(points), args.seeds_per_point, args.assign)
     seeds = (args.first_seed + seed_index).astype(np.uint64)
-    kw = {"commit_times": True} if args.latency or args.stalls or args.series is not None else {}
+    kw = {"commit_times": True} if args.latency or args.stalls or args.finality or args.series is not None else {}
     sim = BatchSimulator.with_param_sets(seeds, args.nodes, sets, set_of, commands_per_epoch=args.commands_per_epoch, device=args.device, **kw)
     try:
         res = sim.loop_until(args.max_clock, allow_faults=True, round_trace=round_trace_capacity(args.max_clock, args.round_trace) if args.rounds else None)
         latency = res.latency_by_param_set() if args.latency else None
         stalls = res.stalls_by_param_set(since="partition_end") if args.stalls else None
         series = res.commit_series(bin_width=args.series) if args.series is not None else None
+        finality = res.finality_by_param_set() if args.finality else None
         round_stats = res.rounds_by_param_set() if args.rounds else None
         chain = res.chain_by_param_set() if args.chain else None
         for k, (pt, row) in enumerate(zip(points, res.by_param_set())):
@@ -139,6 +144,8 @@ def main(argv=None):
                 line["stalls"] = stalls[k]
             if series is not None:
                 line["series"] = [int(v) for v in series[k]]
+            if finality is not None:
+                line["finality"] = finality[k]
             if round_stats is not None:
                 line["round_stats"] = round_stats[k]
             if chain is not None:

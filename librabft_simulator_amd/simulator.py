@@ -546,6 +546,48 @@ class BatchResult:
             out.append(row)
         return out
 
+    def finality_histogram(self, bin_width=None, bins=None):
+        """Commit finality computed on the device (lbft_batch_commit_finality), per group: ``(finality_hist, spread_hist, first_committer,
+        stats)``.  For every entry of an instance's chain (the log of its reference node, as ``chain_stats``) the commit times of all
+        its nodes give the time at which the ``first`` node had committed it, at which nodes holding ``valid`` (total - quorum + 1) and
+        ``quorum`` voting rights had, and at which ``all`` had (only where every node committed it); the rights of an entry are those
+        of its epoch (``rights_rotation``).  ``finality_hist[group, min(v // bin_width, bins - 1)]`` counts the quorum finality
+        (quorum time - the entry's proposal time ``startup_times[proposer] + time``), ``spread_hist`` the spread (all - first);
+        ``first_committer[group, j]`` the entries node ``j`` committed first (the lowest-numbered of a tie); ``stats[group]`` (24
+        uint64) holds ``(samples, sum, min, max)`` of six families: ``first``, ``valid``, ``quorum``, ``all`` (each after the proposal
+        time), ``spread`` and ``open`` (per instance, the entries at the chain's tip that no quorum had committed when the run ended).
+        Instances with a fault are skipped.  Needs a batch created with ``commit_times=True``.  Groups and default binning as
+        ``latency_histogram``."""
+        bin_width, bins = self._binning(bin_width, bins)
+        groups = self._groups()
+        fin = np.zeros((groups, bins), dtype=np.uint64)
+        spread = np.zeros((groups, bins), dtype=np.uint64)
+        first = np.zeros((groups, self._sim.num_nodes), dtype=np.uint64)
+        stats = np.zeros((groups, _lib.FINALITY_STATS), dtype=np.uint64)
+        check(_lib.lib().lbft_batch_commit_finality(self._sim._h, bin_width, bins, fin.ctypes.data, spread.ctypes.data, first.ctypes.data,
+                                                    stats.ctypes.data))
+        return fin, spread, first, stats
+
+    def finality_by_param_set(self, quantiles=(0.5, 0.9, 0.99)):
+        """Per group of ``finality_histogram`` (default, exact binning), in set order: ``first``, ``valid``, ``quorum``, ``all`` and
+        ``spread`` = samples, mean, min, max; ``quorum`` and ``spread`` also ``quantiles`` ({str(q): ticks}, the inverted-CDF rule of
+        ``histogram_quantile``); ``open`` = instances, mean, min, max; ``first_committer``, the entries per node that committed them
+        first, and ``first_share``, their fractions (``None`` without entries).  ``None`` where there are no samples."""
+        width, _ = self._binning(None, None)
+        fin, spread, first, stats = self.finality_histogram()
+        out = []
+        for g in range(fin.shape[0]):
+            row = {"set": g, **_families(stats[g], (("first", "samples"), ("valid", "samples"), ("quorum", "samples"), ("all", "samples"),
+                                                    ("spread", "samples"), ("open", "instances")))}
+            row["quorum"]["quantiles"] = {str(q): histogram_quantile(fin[g], width, q) for q in quantiles}
+            row["spread"]["quantiles"] = {str(q): histogram_quantile(spread[g], width, q) for q in quantiles}
+            counts = [int(v) for v in first[g]]
+            entries = sum(counts)
+            row["first_committer"] = counts
+            row["first_share"] = [c / entries for c in counts] if entries else None
+            out.append(row)
+        return out
+
     def contexts(self, instance=0):
         """The ``Vec<&Context>`` that ``Simulator::loop_until`` returns, for one instance."""
         return [SimulatedContextView(self, instance, n) for n in range(self._sim.num_nodes)]
