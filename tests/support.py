@@ -1,12 +1,16 @@
 """What more than one test module uses: the fixtures that load the package and its libraries, the oracle's configuration of a parameter
-set, small helpers of the statistics tests, and the g++ build of a host shim.  A plain module: tests import what they use, fixtures by
-name (they keep their module scope)."""
+set, small helpers of the statistics tests, the comparisons of the grouped device statistics with their numpy references, and the g++
+build of a host shim.  A plain module: tests import what they use, fixtures by name (they keep their module scope)."""
 import ctypes
 import os
 import subprocess
 
 import numpy as np
 import pytest
+
+import chain_stats_reference
+import commit_finality_reference
+import round_stats_reference
 
 TESTS = os.path.dirname(os.path.abspath(__file__))
 
@@ -74,6 +78,84 @@ def binning(max_clock, width, bins):
 
 def same(a, b):
     return len(a) == len(b) and all(x.shape == y.shape and (x == y).all() for x, y in zip(a, b))
+
+
+def check_chain_stats(res, want, max_clock, binnings=((None, None),), set_of=None, groups=1, faults=None, log_capacity=None):
+    """chain_stats() for every (width, bins) of `binnings` (None = the default) equals the reference on the oracle's histories, commit
+    counts and startup times.  Returns the reference's sample families and author counts and what the last binning gave."""
+    ref = chain_stats_reference
+    histories, counts, startup = want
+    n = counts.shape[1]
+    fam, authors_o = ref.samples(histories, counts, startup, faults, set_of, groups, log_capacity)
+    for width, bins in binnings:
+        hist, authors, stats = res.chain_stats(width, bins)
+        w, b = binning(max_clock, width, bins)
+        assert hist.shape == (groups, b) and authors.shape == (groups, n) and stats.shape == (groups, ref.CHAIN_STATS), (width, bins)
+        assert hist.dtype == authors.dtype == stats.dtype == np.uint64
+        want_hist, want_authors, want_stats = ref.bin_chain(fam, authors_o, w, b)
+        print("binning (%s, %s): stats %s authors %s" % (width, bins, stats.tolist(), authors.tolist()))
+        assert (stats == want_stats).all(), (width, bins, stats, want_stats)
+        assert (authors == want_authors).all(), (width, bins, authors, want_authors)
+        assert (hist == want_hist).all(), (width, bins)
+        assert (hist.sum(axis=1) == stats[:, 0]).all() and (authors.sum(axis=1) == stats[:, 4 * ref.LENGTH + 1]).all()
+    assert all(row["agreement"] is True for row in res.chain_by_param_set())
+    return fam, authors_o, hist, authors, stats
+
+
+def check_finality(res, max_clock, binnings=((None, None),), want=None, **kw):
+    """finality_histogram() for every (width, bins) of `binnings` (None = the default) equals the reference: `want` = (families, first
+    committers), or else the reference on the batch's own read-backs (kw: rights, rotation, commands_per_epoch, set_of, groups,
+    log_capacity).  Returns the reference's families and what the last binning gave."""
+    ref = commit_finality_reference
+    fam, fc = want if want is not None else ref.of_result(res, **kw)
+    groups, n = len(fam), fc.shape[1]
+    for width, bins in binnings:
+        fin, spread, first, stats = res.finality_histogram(width, bins)
+        w, b = binning(max_clock, width, bins)
+        assert fin.shape == spread.shape == (groups, b) and first.shape == (groups, n) and stats.shape == (groups, ref.FINALITY_STATS), (width, bins)
+        assert fin.dtype == spread.dtype == first.dtype == stats.dtype == np.uint64
+        want_fin, want_spread, want_first, want_stats = ref.bin_finality(fam, fc, w, b, max_clock)
+        print("binning (%s, %s): stats %s first %s" % (width, bins, stats.tolist(), first.tolist()))
+        assert (stats == want_stats).all(), (width, bins, stats, want_stats)
+        assert (first == want_first).all(), (width, bins, first, want_first)
+        assert (fin == want_fin).all() and (spread == want_spread).all(), (width, bins)
+        assert (fin.sum(axis=1) == stats[:, 4 * ref.QUORUM]).all() and (spread.sum(axis=1) == stats[:, 4 * ref.SPREAD]).all()
+        assert (first.sum(axis=1) == stats[:, 4 * ref.FIRST]).all()  # a group's row sums to family 0's sample count
+    return fam, fin, spread, first, stats
+
+
+def check_round_tables(res, want, clean=None):
+    """round_tables() is the oracle's tables: max_rounds, messages and every cell, for every instance (`clean`: for those instances)."""
+    ref = round_stats_reference
+    tables_o, max_rounds_o, messages_o = want
+    tables, max_rounds, messages = res.round_tables()
+    sel = slice(None) if clean is None else clean
+    assert tables.dtype == np.int64 and max_rounds.dtype == messages.dtype == np.uint64
+    assert (max_rounds[sel] == max_rounds_o[sel]).all() and (messages[sel] == messages_o[sel]).all()
+    rows = tables_o.shape[1]
+    assert tables[sel].shape[1] >= int(max_rounds_o[sel].max()) and (tables[sel][:, rows:] == ref.EMPTY).all()
+    assert (tables[sel][:, :rows] == tables_o[sel][:, :tables.shape[1]]).all()
+    return tables, max_rounds, messages
+
+
+def check_round_histograms(res, want, max_clock, binnings, set_of=None, groups=1):
+    """round_histogram() for every (width, bins) of `binnings` (None = the default) equals the reference on the tables `want` (the
+    oracle's, or the device's own read-back) and the device's fault words.  Returns the reference's sample families and what the last
+    binning gave."""
+    ref = round_stats_reference
+    tables_o, max_rounds_o, _ = want
+    fam = ref.samples(tables_o, max_rounds_o, res.faults, set_of, groups)
+    for width, bins in binnings:
+        stay, skew, stats = res.round_histogram(width, bins)
+        w, b = binning(max_clock, width, bins)
+        assert stay.shape == skew.shape == (groups, b) and stats.shape == (groups, 16), (width, bins)
+        assert stay.dtype == skew.dtype == stats.dtype == np.uint64
+        want_stay, want_skew, want_stats = ref.bin_rounds(fam, w, b)
+        print("binning (%s, %s): stats %s" % (width, bins, stats.tolist()))
+        assert (stats == want_stats).all(), (width, bins, stats, want_stats)
+        assert (stay == want_stay).all() and (skew == want_skew).all(), (width, bins)
+        assert (stay.sum(axis=1) == stats[:, 4 * ref.STAY]).all() and (skew.sum(axis=1) == stats[:, 4 * ref.SKEW]).all()
+    return fam, stay, skew, stats
 
 
 def run_to_end(sim, max_clock, cut):

@@ -14,33 +14,13 @@ import numpy as np
 import pytest
 
 import chain_stats_reference as ref
-from support import amd, binning, oracle_cfg, plain, same  # noqa: F401
+from support import amd, oracle_cfg, plain, same  # noqa: F401
+from support import check_chain_stats as check
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 pytestmark = pytest.mark.gpu
 LOG_OVERFLOW = 1 << 3  # LBFT_FAULT_LOG_OVERFLOW
-
-
-def check(res, want, max_clock, binnings=((None, None),), set_of=None, groups=1, faults=None, log_capacity=None):
-    """chain_stats() for every (width, bins) of `binnings` (None = the default) equals the reference on the oracle's histories, commit
-    counts and startup times.  Returns the reference's sample families and author counts and what the last binning gave."""
-    histories, counts, startup = want
-    n = counts.shape[1]
-    fam, authors_o = ref.samples(histories, counts, startup, faults, set_of, groups, log_capacity)
-    for width, bins in binnings:
-        hist, authors, stats = res.chain_stats(width, bins)
-        w, b = binning(max_clock, width, bins)
-        assert hist.shape == (groups, b) and authors.shape == (groups, n) and stats.shape == (groups, ref.CHAIN_STATS), (width, bins)
-        assert hist.dtype == authors.dtype == stats.dtype == np.uint64
-        want_hist, want_authors, want_stats = ref.bin_chain(fam, authors_o, w, b)
-        print("binning (%s, %s): stats %s authors %s" % (width, bins, stats.tolist(), authors.tolist()))
-        assert (stats == want_stats).all(), (width, bins, stats, want_stats)
-        assert (authors == want_authors).all(), (width, bins, authors, want_authors)
-        assert (hist == want_hist).all(), (width, bins)
-        assert (hist.sum(axis=1) == stats[:, 0]).all() and (authors.sum(axis=1) == stats[:, 4 * ref.LENGTH + 1]).all()
-    assert all(row["agreement"] is True for row in res.chain_by_param_set())
-    return fam, authors_o, hist, authors, stats
 
 
 def arrays(res):

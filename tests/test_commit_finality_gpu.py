@@ -15,33 +15,13 @@ import pytest
 
 import chain_stats_reference as chain_ref
 import commit_finality_reference as ref
-from support import amd, binning, oracle_cfg, plain, run_to_end, same  # noqa: F401
+from support import amd, oracle_cfg, plain, run_to_end, same  # noqa: F401
+from support import check_finality as check
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 pytestmark = pytest.mark.gpu
 LOG_OVERFLOW = 1 << 3  # LBFT_FAULT_LOG_OVERFLOW
-
-
-def check(res, max_clock, binnings=((None, None),), want=None, **kw):
-    """finality_histogram() for every (width, bins) of `binnings` (None = the default) equals the reference: `want` = (families, first
-    committers), or else the reference on the batch's own read-backs (kw: rights, rotation, commands_per_epoch, set_of, groups,
-    log_capacity).  Returns the reference's families and what the last binning gave."""
-    fam, fc = want if want is not None else ref.of_result(res, **kw)
-    groups, n = len(fam), fc.shape[1]
-    for width, bins in binnings:
-        fin, spread, first, stats = res.finality_histogram(width, bins)
-        w, b = binning(max_clock, width, bins)
-        assert fin.shape == spread.shape == (groups, b) and first.shape == (groups, n) and stats.shape == (groups, ref.FINALITY_STATS), (width, bins)
-        assert fin.dtype == spread.dtype == first.dtype == stats.dtype == np.uint64
-        want_fin, want_spread, want_first, want_stats = ref.bin_finality(fam, fc, w, b, max_clock)
-        print("binning (%s, %s): stats %s first %s" % (width, bins, stats.tolist(), first.tolist()))
-        assert (stats == want_stats).all(), (width, bins, stats, want_stats)
-        assert (first == want_first).all(), (width, bins, first, want_first)
-        assert (fin == want_fin).all() and (spread == want_spread).all(), (width, bins)
-        assert (fin.sum(axis=1) == stats[:, 4 * ref.QUORUM]).all() and (spread.sum(axis=1) == stats[:, 4 * ref.SPREAD]).all()
-        assert (first.sum(axis=1) == stats[:, 4 * ref.FIRST]).all()  # a group's row sums to family 0's sample count
-    return fam, fin, spread, first, stats
 
 
 def arrays(res):

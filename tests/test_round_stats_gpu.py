@@ -13,42 +13,13 @@ import numpy as np
 import pytest
 
 import round_stats_reference as ref
-from support import amd, binning, oracle_cfg, plain, same  # noqa: F401
+from support import amd, oracle_cfg, plain, same  # noqa: F401
+from support import check_round_histograms as check_histograms, check_round_tables as check_tables
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 pytestmark = pytest.mark.gpu
 TRACE_OVERFLOW = 1 << 11  # LBFT_FAULT_TRACE_OVERFLOW
-
-
-def check_tables(res, want, clean=None):
-    """round_tables() is the oracle's tables: max_rounds, messages and every cell, for every instance (`clean`: for those instances)."""
-    tables_o, max_rounds_o, messages_o = want
-    tables, max_rounds, messages = res.round_tables()
-    sel = slice(None) if clean is None else clean
-    assert tables.dtype == np.int64 and max_rounds.dtype == messages.dtype == np.uint64
-    assert (max_rounds[sel] == max_rounds_o[sel]).all() and (messages[sel] == messages_o[sel]).all()
-    rows = tables_o.shape[1]
-    assert tables[sel].shape[1] >= int(max_rounds_o[sel].max()) and (tables[sel][:, rows:] == ref.EMPTY).all()
-    assert (tables[sel][:, :rows] == tables_o[sel][:, :tables.shape[1]]).all()
-    return tables, max_rounds, messages
-
-
-def check_histograms(res, want, max_clock, binnings, set_of=None, groups=1):
-    """round_histogram() for every (width, bins) of `binnings` (None = the default) equals the reference on the oracle's tables and the
-    device's fault words.  Returns the reference's sample families and what the last binning gave."""
-    tables_o, max_rounds_o, _ = want
-    fam = ref.samples(tables_o, max_rounds_o, res.faults, set_of, groups)
-    for width, bins in binnings:
-        stay, skew, stats = res.round_histogram(width, bins)
-        w, b = binning(max_clock, width, bins)
-        assert stay.shape == skew.shape == (groups, b) and stats.shape == (groups, 16), (width, bins)
-        assert stay.dtype == skew.dtype == stats.dtype == np.uint64
-        want_stay, want_skew, want_stats = ref.bin_rounds(fam, w, b)
-        print("binning (%s, %s): stats %s" % (width, bins, stats.tolist()))
-        assert (stats == want_stats).all(), (width, bins, stats, want_stats)
-        assert (stay == want_stay).all() and (skew == want_skew).all(), (width, bins)
-    return fam, stay, skew, stats
 
 
 # ---- case 1: class 1, a node that jumps rounds ----
