@@ -66,11 +66,11 @@ __global__ LBFT_TWO_WAVE_BOUNDS void lbft_k_run0s(Params p, u32* __restrict__ st
 // ... and for ONE network per wavefront (batches of <= 2 048 networks), as wavefront-uniform code on the scalar unit (SimT<K_SMALL_UNIFORM>; round 5, measured: 256 / 1 024 / 2 048 x 4
 // networks 4.77 / 4.88 / 4.91 ms against 5.81 / 5.27 / 5.28 ms on lbft_k_run0s; LBFT_NO_UNI=1 falls back to that kernel)
 __global__ LBFT_TWO_WAVE_BOUNDS void lbft_k_run0u(Params p, u32* __restrict__ state, u32* __restrict__ unfinished) { LBFT_DEV_ONLY(K_SMALL_UNIFORM) run_body<K_SMALL_UNIFORM>(p, state, unfinished); }
-// Large networks without record exchange / trace / lossy network (sim_lean()): also two wavefronts per SIMD (4 spilled registers)
+// Large networks without record exchange / trace / lossy network (sim_lean()): also two wavefronts per SIMD (spilled registers: tests/golden/kernel_manifest.json)
 __global__ LBFT_TWO_WAVE_BOUNDS void lbft_k_run2l(Params p, u32* __restrict__ state, u32* __restrict__ unfinished) { LBFT_DEV_ONLY(K_LARGE_LEAN) run_body<K_LARGE_LEAN>(p, state, unfinished); }
-// ... and with the record exchange of quirks bit 0 (sim_lean_q1(): requests answered by the peer, responses inserted): 24 spilled registers
+// ... and with the record exchange of quirks bit 0 (sim_lean_q1(): requests answered by the peer, responses inserted); spilled registers: tests/golden/kernel_manifest.json
 __global__ LBFT_TWO_WAVE_BOUNDS void lbft_k_run2q(Params p, u32* __restrict__ state, u32* __restrict__ unfinished) { LBFT_DEV_ONLY(K_LARGE_EXCHANGE) run_body<K_LARGE_EXCHANGE>(p, state, unfinished); }
-// ... and class 1 without them (networks of <= 32 nodes with equivocators, a heap / calendar queue, ...): 22 spilled registers
+// ... and class 1 without them (networks of <= 32 nodes with equivocators, a heap / calendar queue, ...); spilled registers: tests/golden/kernel_manifest.json
 __global__ LBFT_TWO_WAVE_BOUNDS void lbft_k_run1l(Params p, u32* __restrict__ state, u32* __restrict__ unfinished) { LBFT_DEV_ONLY(K_MID_LEAN) run_body<K_MID_LEAN>(p, state, unfinished); }
 template <int CLS>
 __global__ __launch_bounds__(64 * LBFT_RUN_WAVES_FULL)

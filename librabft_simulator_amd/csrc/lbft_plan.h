@@ -187,13 +187,11 @@ LBFT_RUN_KERNELS(LBFT_RK_CHECK)
 // more than 32 nodes are refused by both).
 //
 // Large networks without round trace / message loss run the two-wavefronts-per-SIMD kernels (lbft_k_run2l, with the record exchange
-// of quirks bit 0 lbft_k_run2q; 8 lanes per wavefront at 16 384 networks) WITHOUT the register-staged node sets and the calendar
-// fetch-ahead: two wavefronts overlap each other's dependent round trips, and at 256 registers every staged word is a spilled one
-// (16 384 x 64 nodes: 451 ms; with the staging 476-511 ms; the full-register kernel with twice the lanes 503 ms; 8 192 x 100 nodes:
-// 2.49 / 2.75-2.85 / 2.85 s).  Mid-size networks without them: lbft_k_run1l.
+// of quirks bit 0 lbft_k_run2q; 8 lanes per wavefront at 16 384 networks): two wavefronts overlap each other's dependent round trips
+// (what they stage in their 256 registers: EXPERIMENTS.md "Retired switches").  Mid-size networks without them: lbft_k_run1l.
 //
 // Class 0: large batches of the headline network (4 nodes, unit rights, log-normal delays) run lbft_k_run0q.  Its LDS queue columns
-// are 32 lanes apart at compile time (LBFT_QUAD_STRIDE32): 64 networks per wavefront -- batches beyond 131 072 networks, or a forced
+// are 32 lanes apart at compile time (SimT::QS32): 64 networks per wavefront -- batches beyond 131 072 networks, or a forced
 // lanes_per_wavefront -- run the generic class-0 kernel.  Since round 4's work on it the lane-private kernel beats the wavefront-wide
 // pop at EVERY batch size of the headline network -- 2 048 / 4 096 / 8 192 / 16 384 x 4: 4.78 / 6.48 / 8.23 / 10.36 ms against 4.90 /
 // 7.41 / 9.42 / 12.19 -- except the smallest batches: with one network per wavefront and fewer than 1 024 of them lbft_k_run0u wins --
@@ -213,14 +211,14 @@ inline RunKernel pick_run_kernel(const Params& p, bool param_sets, bool commit_t
   if (cls == K_MID) return RK_RUN1;
   if (cls != K_SMALL) return RK_RUN2;
   const bool tiny = p.lpw == 1 && p.m < 1024;
-  if (LBFT_C0_QUAD && sim_quad(p) && !tiny && !(LBFT_QUAD_STRIDE32 && p.lpw > 32) && !k.no_quad) return RK_RUN0Q;
-  if (LBFT_C0_POPC && p.lpw <= LBFT_POPC_MAX_LPW && !k.no_popc) return (p.lpw == 1 && !k.no_uni) ? RK_RUN0U : RK_RUN0S;
+  if (sim_quad(p) && !tiny && p.lpw <= 32 && !k.no_quad) return RK_RUN0Q;
+  if (p.lpw <= LBFT_POPC_MAX_LPW && !k.no_popc) return (p.lpw == 1 && !k.no_uni) ? RK_RUN0U : RK_RUN0S;
   return RK_RUN0;
 }
 // [tables][queue keys][queue metas][diagnostics: LBFT_NPHASES u64 per wavefront][n > 16: one 128-byte receiver list per instance]
 // `slot_bytes`: 12 (key + meta) or 8 (packed one-word entries, kernel class 0)
 // `hcbr_lds`: class 0 with networks of <= 4 nodes keeps the nodes' hcbr buffers in LDS -- except lbft_k_run0q, which carries them in
-// registers with the node burst (LBFT_C0_HCREG)
+// registers with the node burst (SimT::HCREG)
 inline size_t run_lds_bytes(u32 ql, u32 lpw, u32 n, u32 slot_bytes, u32 nwaves, bool hcbr_lds = true) {
   return (size_t)LBFT_TABLE_U64 * 8 + (size_t)nwaves * ql * lpw * slot_bytes + (size_t)nwaves * LBFT_NPHASES * 8 + 8 +
          (n > 16 ? (size_t)nwaves * lpw * LBFT_MAX_NODES : 0) +
@@ -368,8 +366,8 @@ inline int plan_launch(Params& p, u32 lpw, int ql_asked, bool param_sets, bool c
   // 2 KiB slack per workgroup: with less, two workgroups of 32-lane wavefronts do not become co-resident on a CU
   u32 slot_bytes = p.qpack ? 8u : 12u;  // kernel class 0 keeps one-word entries
   const bool quadk = out.kernel == RK_RUN0Q;
-  const bool hcbr_lds = !(LBFT_C0_IMAJOR && LBFT_C0_HCREG && quadk);
-  const u32 qcols = (quadk && LBFT_QUAD_STRIDE32) ? 32u : lpw;  // queue columns per wavefront in LDS (SimT::QS32)
+  const bool hcbr_lds = !quadk;
+  const u32 qcols = quadk ? 32u : lpw;  // queue columns per wavefront in LDS (SimT::QS32)
   u32 ql_auto = (u32)((budget - run_lds_bytes(0, qcols, n, slot_bytes, nwaves, hcbr_lds) - 2048) / (slot_bytes * nwaves * qcols));  // (run_lds_bytes(0, ..) includes the lane padding)
   const u32 ql_max = quadk ? LBFT_PACKED_QL_QUAD : LBFT_PACKED_QL_MAX, pop_batch = quadk ? LBFT_POP_BATCH_QUAD : LBFT_POP_BATCH;
   if (p.qpack && ql_auto > ql_max) ql_auto = ql_max;
@@ -401,9 +399,9 @@ inline int plan_launch(Params& p, u32 lpw, int ql_asked, bool param_sets, bool c
 // only touched where a timeout is inserted or copied -- for networks of <= 4 nodes they live in LDS for the whole launch.  A
 // notification snapshot: its fixed words + set extension words; for <= 4 nodes also its 2n hcbr words (always fetched with it), for
 // larger networks the hcbr words an event happens to carry are NOT counted (the figure is a lower bound there).
-// `headline_burst`: lbft_k_run0q's node burst (LBFT_C0_HCREG: the node's 2n hcbr words ride in it -- hc_load / hc_store -- and are counted)
+// `headline_burst`: lbft_k_run0q's node burst (SimT::HCREG: the node's 2n hcbr words ride in it -- hc_load / hc_store -- and are counted)
 inline void layout_words(const Params& p, RunKernel kernel, bool headline_burst, u32* out) {
-  out[0] = (NF_FIXED_WORDS + 4 * (p.mw - 1) + ((headline_burst && LBFT_C0_HCREG) ? 2 * p.n : 0)) * 4;
+  out[0] = (NF_FIXED_WORDS + 4 * (p.mw - 1) + (headline_burst ? 2 * p.n : 0)) * 4;
   out[1] = (p.qpack ? 8 : p.qcal ? 4 : 12);  // (the calendar keeps no key: an entry is the 4-byte meta word, plus 1/31 of a chunk's link word)
   out[2] = (S_FIXED_WORDS + 2 * (p.mw - 1) + (p.n <= 4 ? 2 * p.n : 0)) * 4;
   out[3] = (B_WORDS + 4 * (p.mw - 1)) * 4;   // bytes of one block record

@@ -73,7 +73,7 @@ __device__ __forceinline__ void run_body(const Params& p, u32* __restrict__ stat
   };
   u32 wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const u32 qslots = p.ql;  // u64 words per instance in the key area
-  const u32 qcols = SimT<CLS>::QS32 ? 32u : p.lpw;  // queue columns per wavefront (lbft_k_run0q: always 32, see LBFT_QUAD_STRIDE32)
+  const u32 qcols = SimT<CLS>::QS32 ? 32u : p.lpw;  // queue columns per wavefront (lbft_k_run0q: always 32, see SimT::QS32)
   u64* keys = lds + LBFT_TABLE_U64 + (size_t)wave * p.ql * qcols + lane;
   u32* metas = reinterpret_cast<u32*>(lds + LBFT_TABLE_U64 + (size_t)nwaves * qslots * qcols) + (size_t)wave * p.ql * qcols + lane;  // (CLS 0: unused, not allocated)
   // diagnostic builds: per-wavefront phase accumulators behind the queue columns (8-byte aligned: the meta area is a multiple of 8 words)
@@ -86,9 +86,8 @@ __device__ __forceinline__ void run_body(const Params& p, u32* __restrict__ stat
   u32 i = (blockIdx.x * nwaves + wave) * p.lpw + lane;
   bool active = lane < p.lpw && i < p.m;
   bool done = true;
-  // lpw divides 64, so a wavefront's instances share one tile: its base is wavefront-uniform (SGPRs) and
-  // every row access is saddr + 32-bit voffset
-  // (tile width tw: 64 for the small-network classes -- two 32-lane wavefronts share a tile --, otherwise tw == lpw: one tile per wavefront)
+  // lpw divides 64, so a wavefront's instances share one tile: its base is wavefront-uniform (SGPRs) and every row access is saddr + 32-bit
+  // voffset (tile width tw: 64 for the mid-size classes; class 0 and the large networks are instance-major, tw = 1)
   const u32 tw = SimT<CLS>::TILE64 ? 64u : SimT<CLS>::IMAJOR ? 1u : p.tw;
   u32 tile_idx = __builtin_amdgcn_readfirstlane(((blockIdx.x * nwaves + wave) * p.lpw) / tw);
   char* tile = reinterpret_cast<char*>(state) + (size_t)tile_idx * p.total_words * ((size_t)4 * tw);

@@ -46,7 +46,7 @@ CONFIGS = {
 HBM_PEAK_GBS = 8000.0
 # Share of a configuration's notifications / responses that the cooperative runs retire -- such an event writes its node's timer words, not its row (roofline()).
 # Since the round's last session COUNTED ON THE DEVICE, every instance of the full-size run (liblbft_hip_runcount.so = -DLBFT_PHASE_TIMERS -DLBFT_RUN_COUNT, LDS counters
-# per wavefront; tools/gpu_r06_run_counts.sh -> profiles/r06/run_counts_on_the_device.jsonl: retired events / the kind's events, same counters and commits as the
+# per wavefront; tools/gpu_r06_run_counts.sh (removed; commit a4b977d is the last that holds it) -> profiles/r06/run_counts_on_the_device.jsonl: retired events / the kind's events, same counters and commits as the
 # product library in the same call).  The host build of the kernel logic (64-lane segments, one or two instances: tests/tools/run_stats.cpp ->
 # profiles/r06/cooperative_runs_final_c5_c4_c4live_c5live_c5named.jsonl) had given 0.8283 / 0.8763, 0.9618 / 0.9952, 0.8870 / 0.8201, 0.9506 / 0.9941, 0.9678 / 0.9927.
 RUN_SHARES = {
