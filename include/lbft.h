@@ -432,6 +432,26 @@ int lbft_batch_chain_stats(const lbft_batch* b, uint32_t bin_width, uint32_t bin
 int lbft_batch_commit_finality(const lbft_batch* b, uint32_t bin_width, uint32_t bins, uint64_t* finality_hist, uint64_t* spread_hist,
                                uint64_t* first_committer, uint64_t* stats);
 
+/* Per-instance statistics: the spread across seeds.  Every statistic above pools its samples over the instances of a group; samples
+ * inside one instance are correlated, so an error bar and the worst seeds need the instance as the unit.
+ * rows[i * LBFT_INSTANCE_STATS + 4 * f + {0, 1, 2, 3}] = samples, sum, min, max of family f restricted to instance i: what
+ * lbft_batch_commit_latency_histogram, lbft_batch_commit_stalls and lbft_batch_commit_finality would report if instance i were a group
+ * of its own (min = max = 0 without samples).  The row of an instance with a non-zero fault word is all zero (those calls skip it).
+ *   family 0, latency: the latency histogram's sample, one per (node, committed entry): the commit time after the proposal time of the
+ *                      block in the node's own log
+ *   families 1 .. 4:   gaps, first, tail, longest -- families 0 .. 3 of lbft_batch_commit_stalls
+ *   families 5 .. 10:  first, valid, quorum, all, spread, open -- families 0 .. 5 of lbft_batch_commit_finality, under the voting rights
+ *                      of the entry's epoch (rights_rotation included)
+ * since[g] is applied to every instance of group g (the parameter sets, or one group for a plain batch) as in lbft_batch_commit_stalls;
+ * NULL = 0.  Refused in this order, before any HIP call and with nothing written: NULL b or rows (LBFT_ERR_INVALID); a batch that does
+ * not record commit times, or before a finished run (LBFT_ERR_STATE; legal after lbft_batch_run_until, lbft_batch_run_steps once it
+ * reports 0, and on a timed batch that loaded a checkpoint); a since[g] outside [0, max_clock] (LBFT_ERR_INVALID).  The call changes no
+ * state.  Computed on the device (lbft_k_ct_instances, liblbft_commit_times.so; the arithmetic is csrc/lbft_instance_stats.h and the
+ * rule headers it includes), one wavefront per instance and one writer per row, without atomics: bit-reproducible. */
+#define LBFT_INSTANCE_FAMILIES 11
+#define LBFT_INSTANCE_STATS 44 /* 11 families x {samples, sum, min, max} */
+int lbft_batch_instance_stats(const lbft_batch* b, const int64_t* since, uint64_t* rows /* [n_instances * LBFT_INSTANCE_STATS] */);
+
 /* Record hashes of every committed chain of a batch in one device call: what lbft_batch_committed_record_hashes gives for one
  * (instance, node), for the chain of every instance.  The nodes of an instance share one block pool (equal id = equal block = equal
  * QC) and every history is a prefix of its instance's chain (chain statistics, family 4), so an instance's records are hashed once.

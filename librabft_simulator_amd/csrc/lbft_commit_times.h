@@ -40,6 +40,12 @@ typedef hipError_t (*lbft_ct_finality_fn)(const lbft::Params* p, const lbft::u32
                                           const lbft::u32* grp_off, lbft::u32 n_groups, lbft::u32 max_group, lbft::u32 bin_width, lbft::u32 bins,
                                           unsigned long long* finality_hist, unsigned long long* spread_hist, unsigned long long* first_committer,
                                           unsigned long long* stats, hipStream_t stream);
+// Per-instance statistics of a finished run (lbft_k_ct_instances; groups as above, rows zeroed by the caller): rows[instance *
+// LBFT_INSTANCE_STATS + family * 4 + {samples, sum, min, max}] of the latency, the four stall and the six finality families, the minimum
+// as itself (include/lbft.h: lbft_batch_instance_stats).  since_of[group] in [0, p->max_clock], NULL = 0 for every group.  p->n <= 32.
+typedef hipError_t (*lbft_ct_instances_fn)(const lbft::Params* p, const lbft::u32* state, const lbft::i32* ctimes, const lbft::u32* grp_inst,
+                                           const lbft::u32* grp_off, lbft::u32 n_groups, lbft::u32 max_group, const lbft::i32* since_of,
+                                           unsigned long long* rows, hipStream_t stream);
 }
 
 #endif  // LBFT_COMMIT_TIMES_H

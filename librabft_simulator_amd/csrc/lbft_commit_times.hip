@@ -6,7 +6,8 @@
 // those of lbft_k_run0 / lbft_k_run<1> and the parameter-set kernels, so the host side of liblbft_hip.so sizes them as those.
 // The histogram kernel turns a finished run's logs and commit times into commit-latency histograms per group (parameter set); the
 // timeline kernel turns the commit times alone into commits over time and the statistics of the commit-free intervals; the finality
-// kernel looks across the nodes of every chain entry: when the first node, a quorum of the voting rights and every node committed it.
+// kernel looks across the nodes of every chain entry: when the first node, a quorum of the voting rights and every node committed it;
+// the instance kernel takes the samples of all three and keeps them per instance (lbft_batch_instance_stats).
 // Built as a library of its own (build.py): the code object of liblbft_hip.so, whose kernels are pinned byte for byte by the codegen
 // manifest, does not change.
 #include <hip/hip_runtime.h>
@@ -17,6 +18,7 @@
 #include "lbft_commit_timeline.h"
 #include "lbft_chain_rules.h"
 #include "lbft_commit_finality.h"
+#include "lbft_instance_stats.h"
 
 using namespace lbft;
 
@@ -295,6 +297,120 @@ __global__ __launch_bounds__(LBFT_FN_BLOCK) void lbft_k_ct_finality(Params p, co
   }
 }
 
+// Per-instance statistics (lbft_batch_instance_stats): the samples of the three kernels above, with the instance as the unit -- no
+// histogram, no atomic, one writer per row (lbft_instance_stats.h).  One wavefront per instance, IST_WAVES per workgroup, striding over
+// the instances of the workgroup's group (a group matters for `since` alone), through the generic Sim accessors.
+//   node pass and chain pass: lbft_k_ct_finality's -- the reference node, L, nc_j; 64 entries at a time, the n commit-time rows staged
+//     in the wavefront's [n][64] LDS tile, g_k from the reference node's log.  While row j of a chunk is staged, its entries also give
+//     the timeline samples -- the predecessor c_j(k - 1) is the lower lane's entry (__shfl_up; lane 0 reads the row's word before the
+//     chunk, so no carry is kept), ctl_entry makes the gap sample, and the chunk's CtlRow is reduced by a butterfly and merged into lane
+//     j's (lane = node) -- and the latency sample c_j(k) - g_k where log[j][k] == log[ref][k], else after the proposal time of the node's
+//     own block.  Lane k then walks its column of the tile (fin_entry) for the six finality quantities.  A lane reads only LDS words it
+//     wrote itself: no barrier.
+//   closing pass (lane = node): the row's first / tail / longest samples.
+// Every family is accumulated per lane (IstStat), reduced by butterflies once per instance, and the row's IST_WORDS words are stored by
+// as many lanes: 352 contiguous bytes.  The row of an instance with a non-zero fault word is left as the caller zeroed it.
+// LDS: the tile, 4 x 32 x 64 x 4 B = 32 KiB, and 128 B of rights.
+#define LBFT_IS_BLOCK (64 * IST_WAVES)
+static_assert(LBFT_INSTANCE_STATS == IST_WORDS && LBFT_INSTANCE_FAMILIES == IST_FAMILIES, "eleven families of (samples, sum, min, max)");
+static_assert(LBFT_STALL_STATS == CTL_FAMILIES * 4, "the stall families");
+
+__device__ __forceinline__ IstStat ist_wave_reduce(IstStat s) {
+  for (int d = 32; d; d >>= 1) {
+    IstStat o;
+    o.cnt = (u32)__shfl_xor((int)s.cnt, d, 64);
+    o.min = (u32)__shfl_xor((int)s.min, d, 64);
+    o.max = (u32)__shfl_xor((int)s.max, d, 64);
+    o.sum = (u64)__shfl_xor((unsigned long long)s.sum, d, 64);
+    s = ist_merge(s, o);
+  }
+  return s;
+}
+
+__global__ __launch_bounds__(LBFT_IS_BLOCK) void lbft_k_ct_instances(Params p, const u32* __restrict__ state, const i32* __restrict__ ctimes,
+                                                                     const u32* __restrict__ grp_inst, const u32* __restrict__ grp_off,
+                                                                     const i32* __restrict__ since_of, unsigned long long* __restrict__ rows) {
+  __shared__ i32 tile[IST_WAVES][LBFT_FN_MAX_NODES][64];
+  __shared__ u32 s_rights[LBFT_FN_MAX_NODES];
+  const u32 g = blockIdx.y;
+  const uint2 grp = gs_group(grp_inst, grp_off, g, p.m);
+  const u32 first = grp.x, cnt = grp.y;
+  if (blockIdx.x * IST_WAVES >= cnt) return;  // (the whole workgroup: its group has fewer instances)
+  const u32 wave = threadIdx.x / 64, lane = threadIdx.x % 64;
+  const u32 n = p.n, lcap = p.lcap, lg = p.off_log;
+  const u32 cpe = fin_cpe32(p.cpe), rot = p.rot;
+  const u32 t_quorum = p.quorum, t_valid = fin_valid_threshold(p.total_votes, p.quorum);
+  const u32* rights = p.unit_weights ? nullptr : s_rights;
+  const i32 since = since_of ? since_of[g] : 0;
+  i32* col = &tile[wave][0][lane];  // this lane's column: node j at col[j * 64]
+  if (threadIdx.x < n) s_rights[threadIdx.x] = p.weights[threadIdx.x];
+  __syncthreads();
+  for (u32 q = blockIdx.x * IST_WAVES + wave; q < cnt; q += gridDim.x * IST_WAVES) {  // (one instance per wavefront: uniform in it)
+    const u32 i = gs_instance(grp_inst, first, q);
+    Sim s(p, const_cast<u32*>(state), i);
+    if (s.ld(I_FAULT) != 0) continue;
+    // node pass
+    const u32 nc = lane < n ? chn_commits(s.nfm(lane, NF_NCOMMITS), lcap) : 0;
+    u64 best = lane < n ? chn_ref_key(nc, lane) : 0;
+    for (int d = 32; d; d >>= 1) best = chn_ref_max(best, (u64)__shfl_xor((unsigned long long)best, d, 64));
+    const u32 L = chn_ref_len(best), ref = chn_ref_node(best);
+    // chain pass
+    IstStat st[IST_FAMILIES];
+    for (u32 f = 0; f < IST_FAMILIES; f++) st[f] = ist_empty();
+    CtlRow row = ctl_empty();  // of node `lane`
+    u32 open = 0;
+    for (u32 c0 = 0; c0 < L; c0 += 64) {
+      const u32 k = c0 + lane;
+      const bool have = k < L;
+      u32 b = 0;
+      i32 gt = 0;
+      if (have) {
+        b = s.ld(lg + ref * lcap + k);
+        gt = (i32)(s.nfm(s.blk_author(b), NF_STARTUP) + s.bf(b, B_TIME));
+      }
+      for (u32 j = 0; j < n; j++) {
+        const u32 ncj = (u32)__shfl((int)nc, (int)j, 64);
+        const i32* ct = ctimes + ((size_t)i * n + j) * lcap;
+        i32 c = k < ncj ? ct[k] : FIN_NONE;  // (k < nc_j <= lcap: inside the row)
+        c = fin_committer(k, ncj, c) ? c : FIN_NONE;
+        col[j * 64] = c;
+        i32 prev = __shfl_up(c, 1, 64);
+        if (lane == 0) prev = c0 && k < ncj ? ct[k - 1] : -1;  // the last entry of the row's previous chunk
+        CtlRow r = ctl_empty();
+        const u32 gap = ctl_entry(r, c, prev, since);
+        if (gap) ist_add(st[IST_STALLS + CTL_GAPS], gap);
+        for (int d = 32; d; d >>= 1) {
+          CtlRow o;
+          o.longest = (u32)__shfl_xor((int)r.longest, d, 64);
+          o.last = __shfl_xor(r.last, d, 64);
+          o.first = (u32)__shfl_xor((int)r.first, d, 64);
+          r = ctl_merge(r, o);
+        }
+        if (lane == j) row = ctl_merge(row, r);
+        if (c >= 0) {  // (then k < nc_j <= L: b and gt are the chain's)
+          const u32 bj = s.ld(lg + j * lcap + k);
+          i32 gj = gt;
+          if (bj != b) gj = (i32)(s.nfm(s.blk_author(bj), NF_STARTUP) + s.bf(bj, B_TIME));  // (the node's own block)
+          ist_add(st[IST_LATENCY], ist_latency(c, gj));
+        }
+      }
+      if (have) open += ist_column(st, fin_entry(col, 64u, n, rights, fin_rights_shift(k, cpe, rot, n), t_valid, t_quorum), n, gt);
+    }
+    // closing pass
+    if (lane < n) ist_node(st, row, p.max_clock);
+    for (int d = 32; d; d >>= 1) open += (u32)__shfl_xor((int)open, d, 64);
+    if (lane == 0) ist_add(st[IST_FINALITY + FIN_OPEN], open);  // one sample per instance
+    // reduction and store
+    unsigned long long word = 0;
+#pragma unroll
+    for (u32 f = 0; f < IST_FAMILIES; f++) {
+      const IstStat t = ist_wave_reduce(st[f]);
+      if (lane / 4 == f) word = ist_word(t, lane % 4);
+    }
+    if (lane < IST_WORDS) rows[(size_t)i * IST_WORDS + lane] = word;
+  }
+}
+
 extern "C" {
 
 __attribute__((visibility("default"))) hipError_t lbft_ct_launch_run(int cls, const Params* p, u32* state, u32* unfinished, const ParamSetDev* sets,
@@ -340,6 +456,17 @@ __attribute__((visibility("default"))) hipError_t lbft_ct_launch_finality(const 
   const u64 gx = gs_workgroups(LBFT_FN_WORKGROUPS, n_groups, ((u64)max_group + LBFT_FN_WAVES - 1) / LBFT_FN_WAVES, (u64)max_group * p->lcap);
   lbft_k_ct_finality<<<dim3((u32)gx, n_groups), LBFT_FN_BLOCK, 0, stream>>>(*p, state, ctimes, grp_inst, grp_off, bin_width, bins, finality_hist, spread_hist,
                                                                          first_committer, stats);
+  return hipGetLastError();
+}
+
+// rows[instance * LBFT_INSTANCE_STATS ..], zeroed by the caller.  The kernel writes the minimum itself, not its complement: a row has
+// one writer, so the caller's GroupedCall::finish() has nothing to undo (the output is no `stats` buffer).  Grid: ist_workgroups.
+__attribute__((visibility("default"))) hipError_t lbft_ct_launch_instances(const Params* p, const u32* state, const i32* ctimes, const u32* grp_inst,
+                                                                          const u32* grp_off, u32 n_groups, u32 max_group, const i32* since_of,
+                                                                          unsigned long long* rows, hipStream_t stream) {
+  if (n_groups == 0 || max_group == 0 || p->n > LBFT_FN_MAX_NODES || !ctimes || !rows) return hipErrorInvalidValue;
+  const u64 gx = ist_workgroups(n_groups, max_group);
+  lbft_k_ct_instances<<<dim3((u32)gx, n_groups), LBFT_IS_BLOCK, 0, stream>>>(*p, state, ctimes, grp_inst, grp_off, since_of, rows);
   return hipGetLastError();
 }
 

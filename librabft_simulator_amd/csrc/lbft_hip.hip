@@ -466,9 +466,11 @@ static lbft_ct_run_fn g_ct_run = nullptr;
 static lbft_ct_hist_fn g_ct_hist = nullptr;
 static lbft_ct_timeline_fn g_ct_timeline = nullptr;
 static lbft_ct_finality_fn g_ct_finality = nullptr;
+static lbft_ct_instances_fn g_ct_instances = nullptr;
 static int load_commit_times_lib() {
   return load_side_lib(LBFT_COMMIT_TIMES_LIB, "commit times", {{"lbft_ct_launch_run", (void**)&g_ct_run}, {"lbft_ct_launch_histogram", (void**)&g_ct_hist},
-                                                               {"lbft_ct_launch_timeline", (void**)&g_ct_timeline}, {"lbft_ct_launch_finality", (void**)&g_ct_finality}});
+                                                               {"lbft_ct_launch_timeline", (void**)&g_ct_timeline}, {"lbft_ct_launch_finality", (void**)&g_ct_finality},
+                                                               {"lbft_ct_launch_instances", (void**)&g_ct_instances}});
 }
 // A run starts with every entry unrecorded (-1)
 static int fill_commit_times(lbft_batch* b) {
@@ -1278,19 +1280,25 @@ int lbft_batch_commit_latency_histogram(const lbft_batch* b, uint32_t bin_width,
   return gc.finish("commit latency histogram");
 }
 
+// `since` of the stall statistics as the kernels take it: one i32 per group, each checked to lie in [0, max_clock]; empty for NULL (0).
+static int since_per_group(const lbft_batch* b, const int64_t* since, std::vector<i32>& since_of) {
+  if (!since) return LBFT_OK;
+  since_of.resize(group_count(b));
+  for (size_t g = 0; g < since_of.size(); g++) {
+    if (since[g] < 0 || since[g] > (int64_t)b->p.max_clock) { g_err = "since[" + std::to_string(g) + "] outside [0, max_clock]"; return LBFT_ERR_INVALID; }
+    since_of[g] = (i32)since[g];
+  }
+  return LBFT_OK;
+}
+
 // Commit timelines per group, computed on the device from the commit-time rows alone (lbft_k_ct_timeline): the series (stats == NULL)
 // or the stall statistics.  Arguments are checked before the first HIP call, `since` before anything is written.
 static int commit_timeline(const lbft_batch* b, const int64_t* since, uint32_t bin_width, uint32_t bins, uint64_t* hist, uint64_t* stats,
                            const char* what) {
   const size_t groups = group_count(b);
   std::vector<i32> since_of;
-  if (since) {
-    since_of.resize(groups);
-    for (size_t g = 0; g < groups; g++) {
-      if (since[g] < 0 || since[g] > (int64_t)b->p.max_clock) { g_err = "since[" + std::to_string(g) + "] outside [0, max_clock]"; return LBFT_ERR_INVALID; }
-      since_of[g] = (i32)since[g];
-    }
-  }
+  int rc = since_per_group(b, since, since_of);
+  if (rc != LBFT_OK) return rc;
   HIP_TRY(hipSetDevice(b->device));
   GroupedCall gc(b);
   unsigned long long *d_hist = gc.out(hist, groups * bins), *d_stats = gc.out(stats, groups * LBFT_STALL_STATS, true);
@@ -1323,6 +1331,23 @@ int lbft_batch_commit_finality(const lbft_batch* b, uint32_t bin_width, uint32_t
   if (gc.e == hipSuccess) gc.e = g_ct_finality(&b->p, b->d_state, b->d_ctimes, gc.d_inst, gc.d_off, (u32)groups, gc.gi.max_group, bin_width, bins, d_fin, d_spr, d_fc,
                                                d_stats, b->stream);
   return gc.finish("commit finality");
+}
+
+// Per-instance statistics (lbft_k_ct_instances): the samples of the three calls above with the instance as the unit, one row of
+// LBFT_INSTANCE_STATS words per instance.  Arguments are checked before the first HIP call, `since` before anything is written; the
+// call changes no state of the batch.  The kernel writes every word as it is reported (the minimum included): rows is no `stats` output.
+int lbft_batch_instance_stats(const lbft_batch* b, const int64_t* since, uint64_t* rows) {
+  int rc = refuse_grouped(b, rows != nullptr, 1, 1, true);
+  if (rc != LBFT_OK) return rc;
+  std::vector<i32> since_of;
+  rc = since_per_group(b, since, since_of);
+  if (rc != LBFT_OK) return rc;
+  HIP_TRY(hipSetDevice(b->device));
+  GroupedCall gc(b);
+  unsigned long long* d_rows = gc.out(rows, b->m * LBFT_INSTANCE_STATS);
+  const i32* d_since = static_cast<const i32*>(gc.in(since_of.data(), since_of.size() * sizeof(i32)));
+  if (gc.e == hipSuccess) gc.e = g_ct_instances(&b->p, b->d_state, b->d_ctimes, gc.d_inst, gc.d_off, (u32)group_count(b), gc.gi.max_group, d_since, d_rows, b->stream);
+  return gc.finish("instance statistics");
 }
 
 // ---- round statistics (lbft_batch_round_stats) ----

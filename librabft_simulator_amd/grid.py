@@ -22,6 +22,9 @@ commit, which node commits first and how many entries no quorum had committed at
 ``--chain`` adds a ``"chain"`` object (BatchResult.chain_by_param_set: the intervals between the proposals of consecutive blocks of the
 committed chain, its length, the nodes' lag behind it, the leaders' tenure, the blocks per proposer and whether every node's history is
 a prefix of the chain); it needs neither commit times nor the trace and leaves the batch on the kernel it would run anyway.
+``--spread`` records commit times and adds a ``"spread"`` object (BatchResult.seed_spread with ``since="partition_end"``: per metric --
+commits, latency, longest stall, recovery, quorum finality, spread, open entries -- the mean over the point's seeds with its standard
+deviation and standard error, and the extremes with the seeds that attain them: the error bar of a point, and the seed to replay).
 """
 import argparse
 import itertools
@@ -107,6 +110,7 @@ def main(argv=None):
     ap.add_argument("--stalls", action="store_true", help="record commit times and add each point's stall / recovery summary")
     ap.add_argument("--series", type=int, default=None, metavar="WIDTH", help="record commit times and add each point's commits per WIDTH ticks")
     ap.add_argument("--finality", action="store_true", help="record commit times and add each point's commit-finality summary")
+    ap.add_argument("--spread", action="store_true", help="record commit times and add each point's spread across its seeds (error bars, worst seeds)")
     ap.add_argument("--rounds", action="store_true", help="record the round-switch trace and add each point's round statistics")
     ap.add_argument("--chain", action="store_true", help="add each point's chain statistics (agreement, chain quality, block cadence)")
     ap.add_argument("--round-trace", type=int, default=None, metavar="N", help="with --rounds: rounds per node the trace keeps")
@@ -125,7 +129,7 @@ def main(argv=None):
                      drop_per_million=pt["drop_per_million"], partition=pt.get("partition")) for pt in points]
     set_of, seed_index = set_assignment(len(points), args.seeds_per_point, args.assign)
     seeds = (args.first_seed + seed_index).astype(np.uint64)
-    kw = {"commit_times": True} if args.latency or args.stalls or args.finality or args.series is not None else {}
+    kw = {"commit_times": True} if args.latency or args.stalls or args.finality or args.spread or args.series is not None else {}
     sim = BatchSimulator.with_param_sets(seeds, args.nodes, sets, set_of, commands_per_epoch=args.commands_per_epoch, device=args.device, **kw)
     try:
         res = sim.loop_until(args.max_clock, allow_faults=True, round_trace=round_trace_capacity(args.max_clock, args.round_trace) if args.rounds else None)
@@ -133,6 +137,7 @@ def main(argv=None):
         stalls = res.stalls_by_param_set(since="partition_end") if args.stalls else None
         series = res.commit_series(bin_width=args.series) if args.series is not None else None
         finality = res.finality_by_param_set() if args.finality else None
+        spread = res.seed_spread(since="partition_end") if args.spread else None
         round_stats = res.rounds_by_param_set() if args.rounds else None
         chain = res.chain_by_param_set() if args.chain else None
         for k, (pt, row) in enumerate(zip(points, res.by_param_set())):
@@ -146,6 +151,8 @@ def main(argv=None):
                 line["series"] = [int(v) for v in series[k]]
             if finality is not None:
                 line["finality"] = finality[k]
+            if spread is not None:
+                line["spread"] = spread[k]
             if round_stats is not None:
                 line["round_stats"] = round_stats[k]
             if chain is not None:

@@ -588,6 +588,67 @@ class BatchResult:
             out.append(row)
         return out
 
+    def instance_stats(self, since=None):
+        """Per-instance statistics computed on the device (lbft_batch_instance_stats): ``[instances, 11, 4]`` uint64,
+        ``(samples, sum, min, max)`` of the families ``_lib.INSTANCE_FAMILIES`` restricted to one instance -- what ``latency_histogram``
+        (family 0), ``stall_histogram`` (families 1 to 4: gaps, first, tail, longest) and ``finality_histogram`` (families 5 to 10:
+        first, valid, quorum, all, spread, open) would report if the instance were a group of its own; min = max = 0 without samples.
+        ``since`` as ``stall_histogram``'s, applied to every instance of the group.  The row of an instance with a fault is all zero.
+        Needs a batch created with ``commit_times=True``."""
+        since = self._since(since)
+        rows = np.zeros((self._sim.num_instances, len(_lib.INSTANCE_FAMILIES), 4), dtype=np.uint64)
+        check(_lib.lib().lbft_batch_instance_stats(self._sim._h, None if since is None else since.ctypes.data, rows.ctypes.data))
+        return rows
+
+    def seed_spread(self, since=None):
+        """The spread of the per-instance values across the seeds of a group, in set order: one dict per group (parameter set, or the
+        one group of a plain batch) with ``set``, ``instances``, ``faulted`` and, per metric, ``{instances, mean, std, stderr, min, max,
+        min_seed, max_seed}`` over the group's instances without a fault that have a value.  ``std`` is numpy's ``ddof=1`` and
+        ``stderr = std / sqrt(instances)`` -- the error bar of ``mean`` (samples inside one instance are correlated: it cannot come from
+        a pooled sample count); both ``None`` below two instances, everything ``None`` without any.  ``min_seed`` / ``max_seed`` are
+        ``sim.seeds[i]`` of the lowest-numbered instance attaining the extreme: the seed to replay in ``Simulator.new``.  With
+        ``S = instance_stats(since)`` in float64, per instance i:
+          commits               commit_counts[i].min()
+          latency_mean          S[i, 0, 1] / S[i, 0, 0]   (a value where S[i, 0, 0] > 0, as for every quotient and extreme below)
+          latency_max           S[i, 0, 3]
+          longest_stall         S[i, 4, 3]
+          recovery              S[i, 2, 3]                (the slowest node's first commit at or after ``since``)
+          finality_quorum_mean  S[i, 7, 1] / S[i, 7, 0]
+          finality_quorum_max   S[i, 7, 3]
+          spread_max            S[i, 9, 3]
+          open                  S[i, 10, 1]"""
+        S = self.instance_stats(since).astype(np.float64)
+        m = self._sim.num_instances
+        seeds = np.asarray(self._sim.seeds)
+        faulted = np.asarray(self.faults) != 0
+        set_of = np.asarray(self._sim.set_of_instance) if self._sim.param_sets is not None else np.zeros(m, dtype=np.int64)
+
+        def quotient(f):
+            have = S[:, f, 0] > 0
+            return np.divide(S[:, f, 1], S[:, f, 0], out=np.zeros(m), where=have), have
+
+        def extreme(f):
+            return S[:, f, 3], S[:, f, 0] > 0
+        metrics = (("commits", (np.asarray(self.commit_counts).min(axis=1).astype(np.float64), np.ones(m, dtype=bool))),
+                   ("latency_mean", quotient(0)), ("latency_max", extreme(0)), ("longest_stall", extreme(4)), ("recovery", extreme(2)),
+                   ("finality_quorum_mean", quotient(7)), ("finality_quorum_max", extreme(7)), ("spread_max", extreme(9)),
+                   ("open", (S[:, 10, 1], S[:, 10, 0] > 0)))
+        out = []
+        for g in range(self._groups()):
+            in_group = set_of == g
+            row = {"set": g, "instances": int(in_group.sum()), "faulted": int((in_group & faulted).sum())}
+            for name, (value, have) in metrics:
+                idx = np.nonzero(in_group & ~faulted & have)[0]
+                v = value[idx]
+                k = len(v)
+                std = float(v.std(ddof=1)) if k >= 2 else None
+                row[name] = {"instances": k, "mean": float(v.mean()) if k else None, "std": std,
+                             "stderr": std / float(np.sqrt(k)) if k >= 2 else None,
+                             "min": float(v.min()) if k else None, "max": float(v.max()) if k else None,
+                             "min_seed": int(seeds[idx[np.argmin(v)]]) if k else None, "max_seed": int(seeds[idx[np.argmax(v)]]) if k else None}
+            out.append(row)
+        return out
+
     def contexts(self, instance=0):
         """The ``Vec<&Context>`` that ``Simulator::loop_until`` returns, for one instance."""
         return [SimulatedContextView(self, instance, n) for n in range(self._sim.num_nodes)]
