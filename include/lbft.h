@@ -452,6 +452,38 @@ int lbft_batch_commit_finality(const lbft_batch* b, uint32_t bin_width, uint32_t
 #define LBFT_INSTANCE_STATS 44 /* 11 families x {samples, sum, min, max} */
 int lbft_batch_instance_stats(const lbft_batch* b, const int64_t* since, uint64_t* rows /* [n_instances * LBFT_INSTANCE_STATS] */);
 
+/* Commit phases: the latency and the finality of the entries of one proposal-time window.  Every statistic above pools over the whole
+ * run; a partition, a warm-up or a cool-down are windows of the clock, and the entries proposed inside one are a cohort of their own.
+ * Groups are those of the latency histogram (the parameter sets, or one group for a plain batch); instances with a non-zero fault word
+ * are skipped.  Group g has phases - 1 edges e_0 <= e_1 <= ... at edges[g * (phases - 1) + q], each in [0, max_clock + 1].  The phase of
+ * a time t is #{q : e_q <= t}, so phase p covers [e_{p-1}, e_p): equal edges give an empty phase, an edge 0 leaves phase 0 empty, an edge
+ * max_clock + 1 is never reached.
+ * The phase of an entry is the phase of its proposal time, startup[author] + time of the block -- the origin the latency histogram and
+ * the finality subtract.  A cohort rule: an entry proposed during a partition belongs to "during" however late it commits.  For a
+ * latency sample the block is the one in the node's own log, for a finality sample the chain's b_k (lbft_batch_commit_finality above).
+ * Six families per (group, phase), stats[(g * phases + p) * LBFT_PHASE_STATS + 4 * f + {0, 1, 2, 3}] = samples, sum, min, max (min = max
+ * = 0 without samples):
+ *   family 0, latency: the sample set of lbft_batch_commit_latency_histogram; also binned,
+ *                      latency_hist[(g * phases + p) * bins + min(sample / bin_width, bins - 1)]
+ *   families 1 .. 5:   first, valid, quorum, all, spread -- families 0 .. 4 of lbft_batch_commit_finality, under the voting rights of the
+ *                      entry's epoch (rights_rotation included); the quorum family is also binned into finality_hist in the same way
+ * `open` and the first committers are not split: `open` is a quantity of an instance at its chain's tip, not of an entry's cohort; they
+ * stay with lbft_batch_commit_finality.
+ * With phases == 1 the outputs are, bit for bit, lbft_batch_commit_latency_histogram's (hist, stats) and lbft_batch_commit_finality's
+ * finality_hist and families 0 .. 4; for any edges the phases of a group add up to that: samples, sums and bins add, the least minimum
+ * and the largest maximum are taken over the phases with samples.
+ * Refused in this order, before any HIP call and with nothing written: NULL b or NULL output, phases == 0 or above LBFT_MAX_PHASES,
+ * edges == NULL with phases > 1, bin_width or bins of 0, groups * phases * bins > 2^31 (LBFT_ERR_INVALID); a batch that does not record
+ * commit times, or before a finished run (LBFT_ERR_STATE; legal wherever lbft_batch_commit_finality is); an edge outside [0, max_clock +
+ * 1] or below its predecessor (LBFT_ERR_INVALID).  The call changes no state.  Computed on the device (lbft_k_ct_phases,
+ * liblbft_commit_times.so; the arithmetic is csrc/lbft_commit_phases.h and the rule headers of the two calls); every accumulation is an
+ * integer add or max, the minimum carried as max(~sample): bit-reproducible. */
+#define LBFT_MAX_PHASES 8
+#define LBFT_PHASE_FAMILIES 6
+#define LBFT_PHASE_STATS 24 /* 6 families x {samples, sum, min, max} */
+int lbft_batch_commit_phases(const lbft_batch* b, const int64_t* edges /* [groups * (phases - 1)]; NULL iff phases == 1 */,
+                             uint32_t phases, uint32_t bin_width, uint32_t bins, uint64_t* latency_hist, uint64_t* finality_hist, uint64_t* stats);
+
 /* Record hashes of every committed chain of a batch in one device call: what lbft_batch_committed_record_hashes gives for one
  * (instance, node), for the chain of every instance.  The nodes of an instance share one block pool (equal id = equal block = equal
  * QC) and every history is a prefix of its instance's chain (chain statistics, family 4), so an instance's records are hashed once.

@@ -79,6 +79,9 @@ INSTANCE_STATS = 44  # LBFT_INSTANCE_STATS: (samples, sum, min, max) of the elev
 # LBFT_INSTANCE_FAMILIES, in the order of a row: the latency, the four stall families, the six finality families
 INSTANCE_FAMILIES = ("latency", "gaps", "first", "tail", "longest", "finality_first", "finality_valid", "finality_quorum", "finality_all",
                      "spread", "open")
+MAX_PHASES = 8  # LBFT_MAX_PHASES: at most 7 edges per group
+PHASE_STATS = 24  # LBFT_PHASE_STATS: (samples, sum, min, max) of the six families below, per (group, phase)
+PHASE_FAMILIES = ("latency", "first", "valid", "quorum", "all", "spread")  # LBFT_PHASE_FAMILIES: the latency, the finality's first five
 
 
 class LbftCounters(C.Structure):
@@ -148,7 +151,7 @@ CHAIN_HEAD_DTYPE = np.dtype([("block_hash", "<u8"), ("state", "<u8"), ("qc_hash"
 # every symbol include/lbft.h declares (tests check that the library exports all of them)
 ABI_SYMBOLS = [
     "lbft_batch_create", "lbft_batch_create_param_sets", "lbft_batch_record_commit_times", "lbft_batch_commit_times",
-    "lbft_batch_commit_latency_histogram", "lbft_batch_commit_series", "lbft_batch_commit_stalls", "lbft_batch_commit_finality", "lbft_batch_instance_stats", "lbft_batch_run_until", "lbft_batch_reset", "lbft_batch_commit_counts",
+    "lbft_batch_commit_latency_histogram", "lbft_batch_commit_series", "lbft_batch_commit_stalls", "lbft_batch_commit_finality", "lbft_batch_instance_stats", "lbft_batch_commit_phases", "lbft_batch_run_until", "lbft_batch_reset", "lbft_batch_commit_counts",
     "lbft_batch_active_rounds", "lbft_batch_committed_history", "lbft_batch_committed_histories", "lbft_batch_committed_record_hashes",
     "lbft_batch_last_committed_states", "lbft_batch_last_committed_state", "lbft_batch_save_node", "lbft_batch_load_node", "lbft_batch_startup_times", "lbft_batch_epochs", "lbft_batch_counters",
     "lbft_batch_faults", "lbft_batch_destroy", "lbft_batch_stream", "lbft_batch_last_run_ms",
@@ -273,6 +276,8 @@ def lib():
     L.lbft_batch_commit_finality.restype = C.c_int
     L.lbft_batch_instance_stats.argtypes = [vp, vp, vp]
     L.lbft_batch_instance_stats.restype = C.c_int
+    L.lbft_batch_commit_phases.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp]
+    L.lbft_batch_commit_phases.restype = C.c_int
     L.lbft_batch_run_until.argtypes = [vp, C.c_int64]
     L.lbft_batch_run_until.restype = C.c_int
     L.lbft_batch_reset.argtypes = [vp]

@@ -24,7 +24,7 @@ TABLE = (
     _lib("paramsets", "lbft_k_ps_", ("lbft_ps_launch_init", "lbft_ps_launch_run"),
          "the kernels of parameter-set batches (lbft_batch_create_param_sets)"),
     _lib("commit_times", "lbft_k_ct_", ("lbft_ct_launch_run", "lbft_ct_launch_histogram", "lbft_ct_launch_timeline", "lbft_ct_launch_finality",
-                                        "lbft_ct_launch_instances"),
+                                        "lbft_ct_launch_instances", "lbft_ct_launch_phases"),
          "the kernels of batches that record commit times (lbft_batch_record_commit_times)"),
     _lib("round_stats", "lbft_k_rs_", ("lbft_rs_launch_rounds",), "the kernel of lbft_batch_round_stats"),
     _lib("chain_stats", "lbft_k_cs_", ("lbft_cs_launch_chain",), "the kernel of lbft_batch_chain_stats"),

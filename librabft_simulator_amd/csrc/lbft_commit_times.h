@@ -46,6 +46,16 @@ typedef hipError_t (*lbft_ct_finality_fn)(const lbft::Params* p, const lbft::u32
 typedef hipError_t (*lbft_ct_instances_fn)(const lbft::Params* p, const lbft::u32* state, const lbft::i32* ctimes, const lbft::u32* grp_inst,
                                            const lbft::u32* grp_off, lbft::u32 n_groups, lbft::u32 max_group, const lbft::i32* since_of,
                                            unsigned long long* rows, hipStream_t stream);
+// Commit phases of a finished run (lbft_k_ct_phases; groups as above, every output zeroed by the caller): the latency histogram's samples
+// and the finality's families first .. spread per (group, phase), the phase of an entry being that of its proposal time among the
+// group's edges (lbft_commit_phases.h; include/lbft.h: lbft_batch_commit_phases).  edges[group * (phases - 1) + q], checked by the caller:
+// each in [0, p->max_clock + 1], none below its predecessor; NULL with phases == 1.  latency_hist / finality_hist[(group * phases +
+// phase) * bins + bin], stats[(group * phases + phase) * LBFT_PHASE_STATS + family * 4 + {samples, sum, ~min, max}].  1 <= phases <=
+// LBFT_MAX_PHASES, phases x bins < 2^32, p->n <= 32.
+typedef hipError_t (*lbft_ct_phases_fn)(const lbft::Params* p, const lbft::u32* state, const lbft::i32* ctimes, const lbft::u32* grp_inst,
+                                        const lbft::u32* grp_off, lbft::u32 n_groups, lbft::u32 max_group, const lbft::i32* edges, lbft::u32 phases,
+                                        lbft::u32 bin_width, lbft::u32 bins, unsigned long long* latency_hist, unsigned long long* finality_hist,
+                                        unsigned long long* stats, hipStream_t stream);
 }
 
 #endif  // LBFT_COMMIT_TIMES_H

@@ -7,7 +7,8 @@
 // The histogram kernel turns a finished run's logs and commit times into commit-latency histograms per group (parameter set); the
 // timeline kernel turns the commit times alone into commits over time and the statistics of the commit-free intervals; the finality
 // kernel looks across the nodes of every chain entry: when the first node, a quorum of the voting rights and every node committed it;
-// the instance kernel takes the samples of all three and keeps them per instance (lbft_batch_instance_stats).
+// the instance kernel takes the samples of all three and keeps them per instance (lbft_batch_instance_stats); the phase kernel splits
+// the latency and the finality by the phase of an entry's proposal time (lbft_batch_commit_phases).
 // Built as a library of its own (build.py): the code object of liblbft_hip.so, whose kernels are pinned byte for byte by the codegen
 // manifest, does not change.
 #include <hip/hip_runtime.h>
@@ -19,6 +20,7 @@
 #include "lbft_chain_rules.h"
 #include "lbft_commit_finality.h"
 #include "lbft_instance_stats.h"
+#include "lbft_commit_phases.h"
 
 using namespace lbft;
 
@@ -411,6 +413,133 @@ __global__ __launch_bounds__(LBFT_IS_BLOCK) void lbft_k_ct_instances(Params p, c
   }
 }
 
+// Commit phases (lbft_batch_commit_phases): the latency histogram's samples and the finality's families first .. spread, split by the
+// phase of the entry's proposal time (lbft_commit_phases.h) -- the second grouping axis.  The mapping is lbft_k_ct_finality's: one
+// wavefront per instance, LBFT_PH_WAVES per workgroup striding over the instances of the workgroup's group, the node pass, the chain 64
+// entries at a time through the wavefront's [n][64] LDS tile.  While row j of a chunk is staged, lane k also takes the latency sample
+// c_j(k) - proposal time of the block in node j's own log, as lbft_k_ct_instances does (on the device that block is the chain's b_k and
+// the sample's phase the lane's; a node whose log differs has its own); lane k then walks its column (fin_entry).  The group's edges are
+// copied into LDS once per workgroup.
+// Histograms: latency and quorum finality, each one virtual histogram of phases x bins bins (phase p's slice at p * bins), in passes of
+// LBFT_PH_LDS_BINS LDS bins by the scheme of lbft_group_stats.h; a group's slice of the global array is the virtual histogram itself.
+// Statistics, first pass: GsStat accumulators per phase in registers would be an array indexed by a run-time phase, which lands in
+// scratch; every sample goes, with four LDS integer atomics, into the workgroup's [phases][24] block of {samples, sum, max(~sample),
+// max} words, which is flushed once per workgroup by gs_stats_out's rule with the phase offset.  (The other form -- the lanes of a
+// chunk share one or two phases, so one butterfly per distinct phase and one lane's atomics -- is
+// profiles/commit_phases/ballot_prereduction.patch: faster with one phase, slower with three and eight, EXPERIMENTS.md "Commit
+// phases".)  Instances with a non-zero fault word are skipped.
+// LDS: tile 32 KiB, histograms 2 x 16 KiB, 128 B rights, 32 B edges, 1536 B statistics: 67 232 B, two workgroups per CU.
+#define LBFT_PH_BLOCK 256
+#define LBFT_PH_WAVES (LBFT_PH_BLOCK / 64)
+#define LBFT_PH_LDS_BINS 4096  // each of the two histograms: 16 KiB of u32 counts
+#define LBFT_PH_WORKGROUPS 1024u
+static_assert(LBFT_MAX_PHASES == CPH_MAX_PHASES && LBFT_PHASE_FAMILIES == CPH_FAMILIES && LBFT_PHASE_STATS == CPH_STATS, "include/lbft.h");
+static_assert(CPH_FINALITY + FIN_SPREAD + 1 == CPH_FAMILIES && CPH_MAX_PHASES * CPH_STATS <= LBFT_PH_BLOCK, "latency, first .. spread; a thread per word");
+
+// One sample into the workgroup's statistics.
+__device__ __forceinline__ void cph_sample_to_lds(unsigned long long* s_stat, u32 phase, u32 family, u32 v) {
+  atomicAdd(&s_stat[cph_word(phase, family, 0)], 1ull); atomicAdd(&s_stat[cph_word(phase, family, 1)], (unsigned long long)v);
+  atomicMax(&s_stat[cph_word(phase, family, 2)], ~(unsigned long long)v); atomicMax(&s_stat[cph_word(phase, family, 3)], (unsigned long long)v);
+}
+
+__global__ __launch_bounds__(LBFT_PH_BLOCK) void lbft_k_ct_phases(Params p, const u32* __restrict__ state, const i32* __restrict__ ctimes,
+                                                                  const u32* __restrict__ grp_inst, const u32* __restrict__ grp_off,
+                                                                  const i32* __restrict__ edges, u32 phases, u32 bin_width, u32 bins,
+                                                                  unsigned long long* __restrict__ latency_hist,
+                                                                  unsigned long long* __restrict__ finality_hist, unsigned long long* __restrict__ stats) {
+  __shared__ i32 tile[LBFT_PH_WAVES][LBFT_FN_MAX_NODES][64];
+  __shared__ u32 h_lat[LBFT_PH_LDS_BINS], h_fin[LBFT_PH_LDS_BINS], s_rights[LBFT_FN_MAX_NODES];
+  __shared__ i32 s_edges[CPH_MAX_PHASES];
+  __shared__ unsigned long long s_stat[CPH_MAX_PHASES * CPH_STATS];
+  const u32 g = blockIdx.y;
+  const uint2 grp = gs_group(grp_inst, grp_off, g, p.m);
+  const u32 first = grp.x, cnt = grp.y;
+  if (blockIdx.x * LBFT_PH_WAVES >= cnt) return;  // (the whole workgroup: its group has fewer instances)
+  const u32 wave = threadIdx.x / 64, lane = threadIdx.x % 64;
+  const u32 n = p.n, lcap = p.lcap, lg = p.off_log;
+  const u32 cpe = fin_cpe32(p.cpe), rot = p.rot;
+  const u32 t_quorum = p.quorum, t_valid = fin_valid_threshold(p.total_votes, p.quorum);
+  const u32* rights = p.unit_weights ? nullptr : s_rights;
+  const u32 n_edges = phases - 1u, vbins = phases * bins, words = phases * CPH_STATS;  // (phases x bins < 2^32: the launcher)
+  i32* col = &tile[wave][0][lane];  // this lane's column: node j at col[j * 64]
+  if (threadIdx.x < n) s_rights[threadIdx.x] = p.weights[threadIdx.x];  // (both read after the pass loop's first barrier)
+  if (threadIdx.x < CPH_MAX_PHASES) s_edges[threadIdx.x] = threadIdx.x < n_edges ? edges[g * n_edges + threadIdx.x] : CPH_NO_EDGE;
+  gs_stats_clear<CPH_MAX_PHASES * CPH_STATS>(s_stat);
+  for (u32 base = 0; base < vbins; base += LBFT_PH_LDS_BINS) {
+    const u32 span = vbins - base < LBFT_PH_LDS_BINS ? vbins - base : LBFT_PH_LDS_BINS;
+    const bool stat_pass = base == 0;
+    gs_lds_clear<LBFT_PH_BLOCK>(h_lat, span);
+    gs_lds_clear<LBFT_PH_BLOCK>(h_fin, span);
+    __syncthreads();
+    for (u32 q = blockIdx.x * LBFT_PH_WAVES + wave; q < cnt; q += gridDim.x * LBFT_PH_WAVES) {  // (one instance per wavefront: uniform in it)
+      const u32 i = gs_instance(grp_inst, first, q);
+      Sim s(p, const_cast<u32*>(state), i);
+      if (s.ld(I_FAULT) != 0) continue;
+      // node pass
+      const u32 nc = lane < n ? chn_commits(s.nfm(lane, NF_NCOMMITS), lcap) : 0;
+      u64 best = lane < n ? chn_ref_key(nc, lane) : 0;
+      for (int d = 32; d; d >>= 1) best = chn_ref_max(best, (u64)__shfl_xor((unsigned long long)best, d, 64));
+      const u32 L = chn_ref_len(best), ref = chn_ref_node(best);
+      // chain pass
+      for (u32 c0 = 0; c0 < L; c0 += 64) {
+        const u32 k = c0 + lane;
+        const bool have = k < L;
+        u32 b = 0;
+        i32 gt = 0;
+        if (have) {
+          b = s.ld(lg + ref * lcap + k);
+          gt = (i32)(s.nfm(s.blk_author(b), NF_STARTUP) + s.bf(b, B_TIME));
+        }
+        const u32 ph = cph_phase(s_edges, gt);
+        for (u32 j = 0; j < n; j++) {
+          const u32 ncj = (u32)__shfl((int)nc, (int)j, 64);
+          i32 c = k < ncj ? ctimes[((size_t)i * n + j) * lcap + k] : FIN_NONE;  // (k < nc_j <= lcap: inside the row)
+          c = fin_committer(k, ncj, c) ? c : FIN_NONE;
+          col[j * 64] = c;
+          if (c >= 0) {  // (then k < nc_j <= L: b, gt and ph are the chain's)
+            const u32 bj = s.ld(lg + j * lcap + k);
+            i32 gj = gt;
+            u32 pj = ph;
+            if (bj != b) {  // (the node's own block)
+              gj = (i32)(s.nfm(s.blk_author(bj), NF_STARTUP) + s.bf(bj, B_TIME));
+              pj = cph_phase(s_edges, gj);
+            }
+            const u32 l = fin_after(c, gj);
+            const u32 vb = cph_bin(pj, l, bin_width, bins);
+            if (cph_in_pass(vb, base, span)) atomicAdd(&h_lat[vb - base], 1u);
+            if (stat_pass) cph_sample_to_lds(s_stat, pj, CPH_LATENCY, l);
+          }
+        }
+        if (have) {
+          const FinEntry e = fin_entry(col, 64u, n, rights, fin_rights_shift(k, cpe, rot, n), t_valid, t_quorum);
+          const i32 all = fin_all(e, n);
+          if (e.quorum >= 0) {
+            const u32 vb = cph_bin(ph, fin_after(e.quorum, gt), bin_width, bins);
+            if (cph_in_pass(vb, base, span)) atomicAdd(&h_fin[vb - base], 1u);
+          }
+          if (stat_pass) {
+            if (e.committers) cph_sample_to_lds(s_stat, ph, CPH_FINALITY + FIN_FIRST, fin_after(e.first, gt));
+            if (e.valid >= 0) cph_sample_to_lds(s_stat, ph, CPH_FINALITY + FIN_VALID, fin_after(e.valid, gt));
+            if (e.quorum >= 0) cph_sample_to_lds(s_stat, ph, CPH_FINALITY + FIN_QUORUM, fin_after(e.quorum, gt));
+            if (all >= 0) {
+              cph_sample_to_lds(s_stat, ph, CPH_FINALITY + FIN_ALL, fin_after(all, gt));
+              cph_sample_to_lds(s_stat, ph, CPH_FINALITY + FIN_SPREAD, fin_after(all, e.first));
+            }
+          }
+        }
+      }
+    }
+    __syncthreads();
+    gs_lds_flush<LBFT_PH_BLOCK>(h_lat, latency_hist, g, vbins, base, span);
+    gs_lds_flush<LBFT_PH_BLOCK>(h_fin, finality_hist, g, vbins, base, span);
+    if (stat_pass && threadIdx.x < words && s_stat[threadIdx.x & ~3u]) {  // gs_stats_out's rule; a group's block is phases x CPH_STATS words
+      if ((threadIdx.x & 3u) < 2u) atomicAdd(&stats[(size_t)g * words + threadIdx.x], s_stat[threadIdx.x]);
+      else atomicMax(&stats[(size_t)g * words + threadIdx.x], s_stat[threadIdx.x]);
+    }
+    __syncthreads();  // (before the next pass clears the histograms)
+  }
+}
+
 extern "C" {
 
 __attribute__((visibility("default"))) hipError_t lbft_ct_launch_run(int cls, const Params* p, u32* state, u32* unfinished, const ParamSetDev* sets,
@@ -467,6 +596,21 @@ __attribute__((visibility("default"))) hipError_t lbft_ct_launch_instances(const
   if (n_groups == 0 || max_group == 0 || p->n > LBFT_FN_MAX_NODES || !ctimes || !rows) return hipErrorInvalidValue;
   const u64 gx = ist_workgroups(n_groups, max_group);
   lbft_k_ct_instances<<<dim3((u32)gx, n_groups), LBFT_IS_BLOCK, 0, stream>>>(*p, state, ctimes, grp_inst, grp_off, since_of, rows);
+  return hipGetLastError();
+}
+
+// edges[group * (phases - 1) ..]: the group's edges, each in [0, p->max_clock + 1] and none below its predecessor (the caller checked);
+// NULL with phases == 1.  Every output zeroed by the caller.  Grid: gs_workgroups, an instance giving a bin at most n x lcap samples.
+__attribute__((visibility("default"))) hipError_t lbft_ct_launch_phases(const Params* p, const u32* state, const i32* ctimes, const u32* grp_inst,
+                                                                       const u32* grp_off, u32 n_groups, u32 max_group, const i32* edges, u32 phases,
+                                                                       u32 bin_width, u32 bins, unsigned long long* latency_hist,
+                                                                       unsigned long long* finality_hist, unsigned long long* stats, hipStream_t stream) {
+  if (bin_width == 0 || bins == 0 || n_groups == 0 || max_group == 0 || p->n > LBFT_FN_MAX_NODES || !ctimes || !latency_hist || !finality_hist ||
+      !stats || phases == 0 || phases > CPH_MAX_PHASES || (phases > 1 && !edges) || (u64)phases * bins > 0xffffffffull)
+    return hipErrorInvalidValue;
+  const u64 gx = gs_workgroups(LBFT_PH_WORKGROUPS, n_groups, ((u64)max_group + LBFT_PH_WAVES - 1) / LBFT_PH_WAVES, (u64)max_group * p->n * p->lcap);
+  lbft_k_ct_phases<<<dim3((u32)gx, n_groups), LBFT_PH_BLOCK, 0, stream>>>(*p, state, ctimes, grp_inst, grp_off, edges, phases, bin_width, bins, latency_hist,
+                                                                        finality_hist, stats);
   return hipGetLastError();
 }
 

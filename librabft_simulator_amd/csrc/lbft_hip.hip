@@ -467,10 +467,11 @@ static lbft_ct_hist_fn g_ct_hist = nullptr;
 static lbft_ct_timeline_fn g_ct_timeline = nullptr;
 static lbft_ct_finality_fn g_ct_finality = nullptr;
 static lbft_ct_instances_fn g_ct_instances = nullptr;
+static lbft_ct_phases_fn g_ct_phases = nullptr;
 static int load_commit_times_lib() {
   return load_side_lib(LBFT_COMMIT_TIMES_LIB, "commit times", {{"lbft_ct_launch_run", (void**)&g_ct_run}, {"lbft_ct_launch_histogram", (void**)&g_ct_hist},
                                                                {"lbft_ct_launch_timeline", (void**)&g_ct_timeline}, {"lbft_ct_launch_finality", (void**)&g_ct_finality},
-                                                               {"lbft_ct_launch_instances", (void**)&g_ct_instances}});
+                                                               {"lbft_ct_launch_instances", (void**)&g_ct_instances}, {"lbft_ct_launch_phases", (void**)&g_ct_phases}});
 }
 // A run starts with every entry unrecorded (-1)
 static int fill_commit_times(lbft_batch* b) {
@@ -1214,10 +1215,11 @@ struct GroupIndex {
 static size_t group_count(const lbft_batch* b) { return b->psets.empty() ? 1 : b->psets.size(); }
 
 // What every statistic per group refuses before its first HIP call, in this order: a NULL argument (args_ok == false) or a zero
-// bin_width / bins, more than 2^31 bins in all, a batch without commit times where the statistic needs them, a batch that has not run.
-static int refuse_grouped(const lbft_batch* b, bool args_ok, uint32_t bin_width, uint32_t bins, bool needs_ctimes) {
+// bin_width / bins, more than 2^31 bins in all (a group holding `slices` histograms of `bins` bins side by side: the phases), a batch
+// without commit times where the statistic needs them, a batch that has not run.
+static int refuse_grouped(const lbft_batch* b, bool args_ok, uint32_t bin_width, uint32_t bins, bool needs_ctimes, uint32_t slices = 1) {
   if (!b || !args_ok || bin_width == 0 || bins == 0) { g_err = "NULL argument, or bin_width / bins of 0"; return LBFT_ERR_INVALID; }
-  if ((u64)group_count(b) * bins > (1ULL << 31)) { g_err = "groups x bins exceeds 2^31"; return LBFT_ERR_INVALID; }
+  if ((u64)group_count(b) * slices * bins > (1ULL << 31)) { g_err = "groups x bins exceeds 2^31"; return LBFT_ERR_INVALID; }
   if (needs_ctimes && !b->ctimes) { g_err = "the batch does not record commit times (lbft_batch_record_commit_times)"; return LBFT_ERR_STATE; }
   if (!b->ran) { g_err = "run the batch first"; return LBFT_ERR_STATE; }
   return LBFT_OK;
@@ -1348,6 +1350,33 @@ int lbft_batch_instance_stats(const lbft_batch* b, const int64_t* since, uint64_
   const i32* d_since = static_cast<const i32*>(gc.in(since_of.data(), since_of.size() * sizeof(i32)));
   if (gc.e == hipSuccess) gc.e = g_ct_instances(&b->p, b->d_state, b->d_ctimes, gc.d_inst, gc.d_off, (u32)group_count(b), gc.gi.max_group, d_since, d_rows, b->stream);
   return gc.finish("instance statistics");
+}
+
+// Commit phases (lbft_k_ct_phases): the latency histogram's samples and the finality's families first .. spread per (group, phase), the
+// phase of an entry being that of its proposal time among the group's edges.  Arguments are checked before the first HIP call, the
+// edges before anything is written; the call changes no state of the batch.
+int lbft_batch_commit_phases(const lbft_batch* b, const int64_t* edges, uint32_t phases, uint32_t bin_width, uint32_t bins, uint64_t* latency_hist,
+                             uint64_t* finality_hist, uint64_t* stats) {
+  const bool args_ok = latency_hist && finality_hist && stats && phases >= 1 && phases <= LBFT_MAX_PHASES && (edges || phases == 1);
+  int rc = refuse_grouped(b, args_ok, bin_width, bins, true, args_ok ? phases : 1);
+  if (rc != LBFT_OK) return rc;
+  const size_t groups = group_count(b), n_edges = phases - 1;
+  std::vector<i32> edge_of(groups * n_edges);
+  for (size_t q = 0; q < edge_of.size(); q++) {
+    if (edges[q] < 0 || edges[q] > (int64_t)b->p.max_clock + 1 || (q % n_edges && edges[q] < edges[q - 1])) {
+      g_err = "edges[" + std::to_string(q) + "] outside [0, max_clock + 1] or below its predecessor";
+      return LBFT_ERR_INVALID;
+    }
+    edge_of[q] = (i32)edges[q];  // (max_clock + 1 <= LBFT_MAX_CLOCK + 1 < 2^31)
+  }
+  HIP_TRY(hipSetDevice(b->device));
+  GroupedCall gc(b);
+  unsigned long long *d_lat = gc.out(latency_hist, groups * phases * bins), *d_fin = gc.out(finality_hist, groups * phases * bins);
+  unsigned long long* d_stats = gc.out(stats, groups * phases * LBFT_PHASE_STATS, true);
+  const i32* d_edges = static_cast<const i32*>(gc.in(edge_of.data(), edge_of.size() * sizeof(i32)));
+  if (gc.e == hipSuccess) gc.e = g_ct_phases(&b->p, b->d_state, b->d_ctimes, gc.d_inst, gc.d_off, (u32)groups, gc.gi.max_group, d_edges, phases, bin_width, bins, d_lat,
+                                             d_fin, d_stats, b->stream);
+  return gc.finish("commit phases");
 }
 
 // ---- round statistics (lbft_batch_round_stats) ----

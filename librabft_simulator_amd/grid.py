@@ -25,6 +25,10 @@ a prefix of the chain); it needs neither commit times nor the trace and leaves t
 ``--spread`` records commit times and adds a ``"spread"`` object (BatchResult.seed_spread with ``since="partition_end"``: per metric --
 commits, latency, longest stall, recovery, quorum finality, spread, open entries -- the mean over the point's seeds with its standard
 deviation and standard error, and the extremes with the seeds that attain them: the error bar of a point, and the seed to replay).
+``--phases E1,E2,...|partition`` records commit times and adds a ``"phases"`` list (BatchResult.phases_by_param_set: the commit latency
+and the finality of the entries PROPOSED in each window of the clock -- up to 7 edges in [0, max_clock + 1], not decreasing, or
+``partition`` for before / during / after each point's own partition; per phase ``from``, ``to``, the six families and the quantiles
+of the latency and of the quorum finality).  ``--phases WARM,END`` sets a warm-up and a cool-down apart.
 """
 import argparse
 import itertools
@@ -65,6 +69,19 @@ def _partitions(text):
     if not out:
         raise argparse.ArgumentTypeError("--partition needs at least one value")
     return out
+
+
+def _phases(text):
+    """``partition`` or up to 7 comma-separated, non-negative, non-decreasing ints."""
+    if text.strip().lower() == "partition":
+        return "partition"
+    try:
+        edges = [int(v) for v in text.split(",")]
+    except ValueError:
+        raise argparse.ArgumentTypeError("--phases takes E1,E2,... or partition, not %r" % text)
+    if not 1 <= len(edges) <= 7 or min(edges) < 0 or any(b < a for a, b in zip(edges, edges[1:])):
+        raise argparse.ArgumentTypeError("--phases takes 1 to 7 edges, none negative, none below its predecessor, not %r" % text)
+    return edges
 
 
 def grid_points(args):
@@ -111,6 +128,8 @@ def main(argv=None):
     ap.add_argument("--series", type=int, default=None, metavar="WIDTH", help="record commit times and add each point's commits per WIDTH ticks")
     ap.add_argument("--finality", action="store_true", help="record commit times and add each point's commit-finality summary")
     ap.add_argument("--spread", action="store_true", help="record commit times and add each point's spread across its seeds (error bars, worst seeds)")
+    ap.add_argument("--phases", type=_phases, default=None, metavar="E1,E2,...|partition",
+                    help="record commit times and add each point's latency and finality per proposal-time window")
     ap.add_argument("--rounds", action="store_true", help="record the round-switch trace and add each point's round statistics")
     ap.add_argument("--chain", action="store_true", help="add each point's chain statistics (agreement, chain quality, block cadence)")
     ap.add_argument("--round-trace", type=int, default=None, metavar="N", help="with --rounds: rounds per node the trace keeps")
@@ -119,6 +138,8 @@ def main(argv=None):
         ap.error("--round-trace N goes with --rounds and must be at least 1")
     if args.series is not None and args.series < 1:
         ap.error("--series WIDTH must be at least 1")
+    if args.phases is not None and args.phases != "partition" and args.phases[-1] > args.max_clock + 1:
+        ap.error("--phases: an edge lies in [0, max_clock + 1]")
     points = grid_points(args)
     if not 1 <= len(points) <= MAX_PARAM_SETS:
         ap.error("the grid has %d points; 1 to %d fit one batch" % (len(points), MAX_PARAM_SETS))
@@ -129,7 +150,7 @@ def main(argv=None):
                      drop_per_million=pt["drop_per_million"], partition=pt.get("partition")) for pt in points]
     set_of, seed_index = set_assignment(len(points), args.seeds_per_point, args.assign)
     seeds = (args.first_seed + seed_index).astype(np.uint64)
-    kw = {"commit_times": True} if args.latency or args.stalls or args.finality or args.spread or args.series is not None else {}
+    kw = {"commit_times": True} if args.latency or args.stalls or args.finality or args.spread or args.phases is not None or args.series is not None else {}
     sim = BatchSimulator.with_param_sets(seeds, args.nodes, sets, set_of, commands_per_epoch=args.commands_per_epoch, device=args.device, **kw)
     try:
         res = sim.loop_until(args.max_clock, allow_faults=True, round_trace=round_trace_capacity(args.max_clock, args.round_trace) if args.rounds else None)
@@ -138,6 +159,7 @@ def main(argv=None):
         series = res.commit_series(bin_width=args.series) if args.series is not None else None
         finality = res.finality_by_param_set() if args.finality else None
         spread = res.seed_spread(since="partition_end") if args.spread else None
+        phases = res.phases_by_param_set(args.phases) if args.phases is not None else None
         round_stats = res.rounds_by_param_set() if args.rounds else None
         chain = res.chain_by_param_set() if args.chain else None
         for k, (pt, row) in enumerate(zip(points, res.by_param_set())):
@@ -153,6 +175,8 @@ def main(argv=None):
                 line["finality"] = finality[k]
             if spread is not None:
                 line["spread"] = spread[k]
+            if phases is not None:
+                line["phases"] = phases[k]["phases"]
             if round_stats is not None:
                 line["round_stats"] = round_stats[k]
             if chain is not None:

@@ -649,6 +649,78 @@ class BatchResult:
             out.append(row)
         return out
 
+    def _phase_edges(self, edges):
+        """``edges`` of ``phase_histogram`` as int64 ``[groups, phases - 1]``; ValueError before any library call."""
+        groups, top = self._groups(), int(self._sim._max_clock) + 1
+        if isinstance(edges, str):
+            if edges != "partition":
+                raise ValueError("edges: a sequence of ints, one sequence per group or 'partition'")
+            sets = self._sim.param_sets
+            parts = [ps.partition for ps in sets] if sets is not None else [getattr(self._sim, "partition", None)]
+            rows = [[top, top] if p is None or p[0] == 0 else [min(max(int(p[1]), 0), top), min(max(int(p[1]), int(p[2]), 0), top)] for p in parts]
+        else:
+            rows = list(edges)
+            if all(np.ndim(r) == 0 for r in rows):  # (also []: one phase)
+                rows = [rows] * groups
+            elif not all(np.ndim(r) == 1 for r in rows):
+                raise ValueError("edges: a sequence of ints or one sequence of ints per group")
+            elif len(rows) != groups:
+                raise ValueError("edges needs one sequence per group (%d)" % groups)
+            rows = [[int(v) for v in r] for r in rows]
+        if len({len(r) for r in rows}) != 1:
+            raise ValueError("every group needs the same number of edges")
+        if len(rows[0]) > _lib.MAX_PHASES - 1:
+            raise ValueError("at most %d edges (%d phases)" % (_lib.MAX_PHASES - 1, _lib.MAX_PHASES))
+        out = np.array(rows, dtype=np.int64).reshape(groups, len(rows[0]))
+        if ((out < 0) | (out > top)).any() or (np.diff(out, axis=1) < 0).any():
+            raise ValueError("edges must lie in [0, max_clock + 1] and must not decrease")
+        return out
+
+    def phase_histogram(self, edges, bin_width=None, bins=None):
+        """Commit latency and finality per proposal-time window, computed on the device (lbft_batch_commit_phases): ``(latency_hist,
+        finality_hist, stats)`` with ``latency_hist[group, phase, min(v // bin_width, bins - 1)]``, ``finality_hist`` the same for the
+        quorum finality, and ``stats[group, phase, family] = (samples, sum, min, max)`` of the families ``_lib.PHASE_FAMILIES``: the
+        latency sample of ``latency_histogram`` and ``first``, ``valid``, ``quorum``, ``all``, ``spread`` of ``finality_histogram``
+        (uint64; min = max = 0 without samples).  A group's edges ``e_0 <= e_1 <= ...`` in ``[0, max_clock + 1]`` cut the clock into
+        phases, phase ``p`` covering ``[e_{p-1}, e_p)``; an entry belongs to the phase of its proposal time ``startup_times[proposer] +
+        time`` however late it commits.  ``edges``: a sequence of ints (the same for every group; ``[]``: one phase), one sequence
+        per group, or ``"partition"`` -- ``[start, end]`` of each set's (or the batch's) partition, and ``[max_clock + 1, max_clock +
+        1]`` without one, so that everything is "before".  ``edges=[warm, max_clock - cool]`` sets a warm-up and a cool-down apart:
+        phase 1 is the steady state.  With one phase the arrays are ``latency_histogram``'s and ``finality_histogram``'s; the phases
+        of a group add up to them.  ``open`` and the first committers are not split.  Instances with a fault are skipped.  Needs a
+        batch created with ``commit_times=True``.  Groups and default binning as ``latency_histogram``."""
+        bin_width, bins = self._binning(bin_width, bins)
+        edges = self._phase_edges(edges)
+        groups, phases = edges.shape[0], edges.shape[1] + 1
+        lat = np.zeros((groups, phases, bins), dtype=np.uint64)
+        fin = np.zeros((groups, phases, bins), dtype=np.uint64)
+        stats = np.zeros((groups, phases, len(_lib.PHASE_FAMILIES), 4), dtype=np.uint64)
+        check(_lib.lib().lbft_batch_commit_phases(self._sim._h, edges.ctypes.data if phases > 1 else None, phases, bin_width, bins, lat.ctypes.data,
+                                                  fin.ctypes.data, stats.ctypes.data))
+        return lat, fin, stats
+
+    def phases_by_param_set(self, edges, quantiles=(0.5, 0.9, 0.99)):
+        """Per group of ``phase_histogram`` (default, exact binning), in set order: ``set`` and ``phases``, a list with one dict per
+        phase: ``from`` and ``to`` (the phase covers ``[from, to)``; the first starts at 0, the last ends at ``max_clock + 1``), the six
+        families ``latency``, ``first``, ``valid``, ``quorum``, ``all``, ``spread`` = samples, mean, min, max, and ``quantiles``
+        ({str(q): ticks}, the inverted-CDF rule of ``histogram_quantile``) for ``latency`` and ``quorum``.  ``None`` where there are no
+        samples."""
+        width, _ = self._binning(None, None)
+        bounds = self._phase_edges(edges)
+        lat, fin, stats = self.phase_histogram(bounds)
+        top = int(self._sim._max_clock) + 1
+        out = []
+        for g in range(lat.shape[0]):
+            rows = []
+            for p in range(lat.shape[1]):
+                row = {"from": int(bounds[g, p - 1]) if p else 0, "to": int(bounds[g, p]) if p < bounds.shape[1] else top,
+                       **_families(stats[g, p].reshape(-1), tuple((name, "samples") for name in _lib.PHASE_FAMILIES))}
+                row["latency"]["quantiles"] = {str(q): histogram_quantile(lat[g, p], width, q) for q in quantiles}
+                row["quorum"]["quantiles"] = {str(q): histogram_quantile(fin[g, p], width, q) for q in quantiles}
+                rows.append(row)
+            out.append({"set": g, "phases": rows})
+        return out
+
     def contexts(self, instance=0):
         """The ``Vec<&Context>`` that ``Simulator::loop_until`` returns, for one instance."""
         return [SimulatedContextView(self, instance, n) for n in range(self._sim.num_nodes)]
