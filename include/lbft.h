@@ -232,7 +232,9 @@ int lbft_batch_committed_record_hashes(const lbft_batch* b, size_t inst, uint32_
 /* All histories: out[(inst * num_nodes + node) * cap_per_node + k], first min(len, cap_per_node) entries each. */
 int lbft_batch_committed_histories(const lbft_batch* b, lbft_commit* out, size_t cap_per_node);
 /* StateFinalizer::last_committed_state() (simulated_context.rs:194-196; State = SipHash-1-3 of the
- * history, :51-55), computed on the device: out[inst * num_nodes + node]. */
+ * history, :51-55), computed on the device: out[inst * num_nodes + node].  The hashes are computed at the first request after a
+ * run (a run itself reduces only the batch counters) and kept until the next one: they are those of the state the run finished in,
+ * also when calls accepted after it -- node-level calls, lbft_batch_load_node -- have changed the nodes since. */
 int lbft_batch_last_committed_states(const lbft_batch* b, uint64_t* out);
 /* ConsensusNode::save_node (librabft-v2/src/node.rs:233-238): bincode::serialize(&NodeState) of one node -- record store with every Block /
  * QuorumCertificate / Vote / Timeout it holds (rebuilt with the reference's BCS + SipHash-1-3 hashes and signatures), pacemaker, tracker --

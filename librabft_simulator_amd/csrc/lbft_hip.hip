@@ -79,19 +79,12 @@ __attribute__((amdgpu_waves_per_eu(LBFT_BIG_WAVES_PER_SIMD, LBFT_BIG_WAVES_PER_S
 #endif
 void lbft_k_run(Params p, u32* __restrict__ state, u32* __restrict__ unfinished) { LBFT_DEV_ONLY(CLS) run_body<CLS>(p, state, unfinished); }
 
-__device__ __forceinline__ u64 wave_sum(u64 v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ u64 wave_max(u64 v) {
-  for (int off = 32; off > 0; off >>= 1) { u64 o = __shfl_down(v, off, 64); v = o > v ? o : v; }
-  return v;
-}
-
-enum CounterSlot { C_EV0 = 0, C_EV1, C_EV2, C_EV3, C_DRAWS, C_ROUNDS, C_COMMITS, C_SCHED, C_FAULTED, C_NFOLD, C_NUPD, C_MAXQ, C_MAXSNAP, C_MAXBLK, C_WORDS };
+// CounterSlot, the wavefront reductions and the counters of a wavefront's instances (shared with lbft_k_ps_counters of liblbft_paramsets.so)
+#include "lbft_batch_counters.h"
 
 // Per-node State hash (simulated_context.rs:51-55) and the batch counters (wavefront shuffle
-// reductions, one atomic per wavefront and counter).
+// reductions, one atomic per wavefront and counter).  A finished run launches it only when the hashes are asked for (hashes_on_demand);
+// the run's own counters come from lbft_k_ps_counters, and this kernel's are compared with them there.
 #define LBFT_FINAL_WAVES 4  // wavefronts per workgroup of lbft_k_finalize = the nodes of the SAME 64 instances that are hashed side by side
 __global__ __launch_bounds__(LBFT_BLOCK * LBFT_FINAL_WAVES) void lbft_k_finalize(Params p, const u32* __restrict__ state, u64* __restrict__ states_out,
                                                                                  unsigned long long* __restrict__ counters) {
@@ -123,6 +116,9 @@ __global__ __launch_bounds__(LBFT_BLOCK * LBFT_FINAL_WAVES) void lbft_k_finalize
     states_out[(size_t)i * p.n + n] = h.finish();
   }
   if (n != 0) return;
+  // (instance_counter_words of lbft_batch_counters.h reads these words the same way.  The tail stays written out here: with its body in a
+  // shared function the kernel compiled to 16 bytes less -- another schedule --, and its machine code is pinned by
+  // tests/golden/kernel_manifest.json)
   u64 c[C_WORDS];
   for (int k = 0; k < C_WORDS; k++) c[k] = 0;
   if (i < p.m) {
@@ -249,6 +245,9 @@ static const u64 H_ZF[257] = LBFT_ZIG_NORM_F_BITS_INIT;
 static const u64 H_ET[256] = LBFT_EXP_TAB_INIT;
 static_assert(sizeof(H_ZX) + sizeof(H_ZF) + sizeof(H_ET) == LBFT_SAMPLER_TABLE_BYTES, "lbft_plan.h table_bytes");
 
+enum TailWord { TAIL_UNFINISHED = C_WORDS, TAIL_CHECK = C_WORDS + 2, TAIL_WORDS = TAIL_CHECK + C_WORDS };  // (lbft_batch::d_counters)
+static_assert(C_WORDS <= 16, "lbft_batch::run_words");
+
 struct lbft_batch {
   lbft_config cfg;
   std::vector<u64> rights;
@@ -264,9 +263,18 @@ struct lbft_batch {
   u8* d_leaders = nullptr;
   u32* d_weights = nullptr;
   std::vector<u32> weights;
-  u32* d_unfinished = nullptr;
   u64* d_states_out = nullptr;
+  // ONE allocation of TAIL_WORDS words: the batch counters, the run kernels' unfinished count right behind them (a single-launch run
+  // zeroes both with one fill), and the counters that lbft_k_finalize adds to when it runs for the State hashes alone
   unsigned long long* d_counters = nullptr;
+  u32* d_unfinished = nullptr;              // = d_counters + TAIL_UNFINISHED
+  unsigned long long* d_check = nullptr;    // = d_counters + TAIL_CHECK
+  // State hashes on demand: a finished run reduces its counters with lbft_k_ps_counters and leaves d_states_out as it was; the first
+  // request for the hashes (or the first accepted call that changes the state they are defined on) launches lbft_k_finalize once
+  mutable std::mutex hash_mutex;
+  mutable bool hashes_pending = false;
+  u64 hash_generation = 0;                  // `generation` when the run finished: pending hashes are those of exactly that state
+  unsigned long long run_words[16] = {0};   // the C_WORDS counter words of that run, as lbft_k_ps_counters reduced them
   mutable std::mutex sn_mutex;  // guards the save_node image cache (sn_*): lbft_batch_save_node takes a const batch but fills the cache
   u32* d_scratch = nullptr;  // m * n words for gathers
   lbft_node_call* d_calls = nullptr;  // lbft_node_calls: the calls of one batch and their result words
@@ -316,8 +324,9 @@ struct lbft_batch {
 static RunKernel plain_kernel(const lbft_batch* b) { return pick_run_kernel(b->p, false, false, b->knobs); }
 
 static int prepare_run(lbft_batch* b, int64_t max_clock);
-static int finalize_run(lbft_batch* b, u32 grid_full, u64 launches);
-static int launch_run(lbft_batch* b);
+static int finalize_run(lbft_batch* b, u64 launches, bool tail_zeroed = false);
+static int launch_run(lbft_batch* b, bool tail_zeroed = false);
+static int materialise_hashes(const lbft_batch* b);
 static int zero_calendar(lbft_batch* b);
 static int launch_init(lbft_batch* b, u32 grid_init);
 static int fill_commit_times(lbft_batch* b);
@@ -326,7 +335,7 @@ static void free_batch(lbft_batch* b) {
   if (!b) return;
   (void)hipSetDevice(b->device);
   hipFree(b->d_seeds); hipFree(b->d_state); hipFree(b->d_zx); hipFree(b->d_zf); hipFree(b->d_et); hipFree(b->d_dur);
-  hipFree(b->d_leaders); hipFree(b->d_weights); hipFree(b->d_prof); hipFree(b->d_unfinished); hipFree(b->d_states_out); hipFree(b->d_counters); hipFree(b->d_scratch); hipFree(b->d_calls); hipFree(b->d_call_out);
+  hipFree(b->d_leaders); hipFree(b->d_weights); hipFree(b->d_prof); hipFree(b->d_states_out); hipFree(b->d_counters); hipFree(b->d_scratch); hipFree(b->d_calls); hipFree(b->d_call_out);
   hipFree(b->d_psets); hipFree(b->d_set_of); hipFree(b->d_ps_dur); hipFree(b->d_ctimes);
   if (b->h_counters) hipHostFree(b->h_counters);
   if (b->ev0) hipEventDestroy(b->ev0);
@@ -400,11 +409,12 @@ int lbft_batch_create(const lbft_config* cfg, const uint64_t* seeds, size_t n_in
   CREATE_TRY(hipEventCreate(&b->ev2));
   CREATE_TRY(hipMalloc(&b->d_seeds, n_instances * sizeof(u64)));
   CREATE_TRY(hipMemcpy(b->d_seeds, seeds, n_instances * sizeof(u64), hipMemcpyHostToDevice));
-  CREATE_TRY(hipMalloc(&b->d_unfinished, sizeof(u32)));
   CREATE_TRY(hipMalloc(&b->d_prof, LBFT_NPHASES * sizeof(unsigned long long)));
   CREATE_TRY(hipMemset(b->d_prof, 0, LBFT_NPHASES * sizeof(unsigned long long)));  // (zeroed per run only in phase-timer builds)
   CREATE_TRY(hipMalloc(&b->d_states_out, n_instances * cfg->num_nodes * sizeof(u64)));
-  CREATE_TRY(hipMalloc(&b->d_counters, C_WORDS * sizeof(unsigned long long)));
+  CREATE_TRY(hipMalloc(&b->d_counters, TAIL_WORDS * sizeof(unsigned long long)));
+  b->d_unfinished = reinterpret_cast<u32*>(b->d_counters + TAIL_UNFINISHED);
+  b->d_check = b->d_counters + TAIL_CHECK;
   CREATE_TRY(hipMalloc(&b->d_scratch, n_instances * cfg->num_nodes * sizeof(u64) + 256));  // + the node-level calls' result words
   rc = upload_tables(b);
   if (rc != LBFT_OK) { free_batch(b); return rc; }
@@ -417,6 +427,7 @@ int lbft_batch_create(const lbft_config* cfg, const uint64_t* seeds, size_t n_in
 // so that adding them leaves this library's machine code as it is.
 static lbft_ps_init_fn g_ps_init = nullptr;
 static lbft_ps_run_fn g_ps_run = nullptr;
+static lbft_ps_counters_fn g_ps_counters = nullptr;
 static std::string side_lib_path(const char* name) {  // a library beside this one
   Dl_info self;
   std::string path = name;
@@ -448,7 +459,16 @@ static int load_side_lib(const char* lib, const char* what, std::initializer_lis
   return LBFT_ERR_UNSUPPORTED;
 }
 static int load_paramsets_lib() {
-  return load_side_lib(LBFT_PARAMSETS_LIB, "parameter sets", {{"lbft_ps_launch_init", (void**)&g_ps_init}, {"lbft_ps_launch_run", (void**)&g_ps_run}});
+  return load_side_lib(LBFT_PARAMSETS_LIB, "parameter sets", {{"lbft_ps_launch_init", (void**)&g_ps_init}, {"lbft_ps_launch_run", (void**)&g_ps_run},
+                                                              {"lbft_ps_launch_counters", (void**)&g_ps_counters}});
+}
+// lbft_k_ps_counters serves batches of every kind.  A parameter-set batch has the library open since its creation; any other batch tries
+// once per process and, where the library is missing or lacks a launcher, keeps the path it always had (lbft_k_finalize per run): a
+// plain batch depends on no second file.
+static bool lean_counters() {
+  static std::once_flag tried;
+  std::call_once(tried, [] { const std::string keep = g_err; (void)load_paramsets_lib(); g_err = keep; });
+  return g_ps_counters != nullptr;
 }
 static int launch_init(lbft_batch* b, u32 grid_init) {
   if (b->psets.empty()) {
@@ -569,13 +589,14 @@ int lbft_batch_manual_finalize(lbft_batch* b) {
   HIP_TRY(hipEventRecord(b->ev0, b->stream));
   HIP_TRY(hipEventRecord(b->ev1, b->stream));
   HIP_TRY(hipEventRecord(b->ev2, b->stream));
-  return finalize_run(b, (u32)((b->m + LBFT_BLOCK - 1) / LBFT_BLOCK), 0);
+  return finalize_run(b, 0);
 }
 
 static int node_op(lbft_batch* b, u32 op, size_t inst, u32 node, u32 arg0, u32 arg1, i64 node_time, unsigned long long* host_out, int n_out) {
   if (!b || inst >= b->m || node >= b->p.n) return LBFT_ERR_INVALID;
   if (!b->manual) { g_err = "lbft_batch_manual_begin first"; return LBFT_ERR_STATE; }
   HIP_TRY(hipSetDevice(b->device));
+  { int mrc = materialise_hashes(b); if (mrc != LBFT_OK) return mrc; }  // (after lbft_batch_manual_finalize: its hashes are those of the state before this call)
   unsigned long long* d_out = reinterpret_cast<unsigned long long*>(b->d_scratch);  // 16 result words
   b->generation++;
   lbft_k_node_op<<<1, 64, 0, b->stream>>>(b->p, b->d_state, op, (u32)inst, node, arg0, arg1, node_time, d_out);
@@ -628,6 +649,7 @@ int lbft_node_calls(lbft_batch* b, const lbft_node_call* calls, size_t n, lbft_n
     dev[k].op = op;
   }
   HIP_TRY(hipSetDevice(b->device));
+  { int mrc = materialise_hashes(b); if (mrc != LBFT_OK) return mrc; }
   const size_t call_bytes = n * sizeof(lbft_node_call), out_bytes = n * 16 * sizeof(unsigned long long);
   if (b->calls_cap < n) {
     if (b->d_calls) { hipFree(b->d_calls); b->d_calls = nullptr; }
@@ -849,6 +871,7 @@ int lbft_batch_reset(lbft_batch* b) {
   b->manual = false;
   b->started = false;
   b->step_launches = 0;
+  b->hashes_pending = false;  // (the hashes of a run are served while `ran` holds: nobody can ask for these any more)
   return LBFT_OK;
 }
 
@@ -915,11 +938,15 @@ int lbft_batch_run_until(lbft_batch* b, int64_t max_clock) {
 #if defined(LBFT_PHASE_TIMERS)
   HIP_TRY(hipMemsetAsync(b->d_prof, 0, LBFT_NPHASES * sizeof(unsigned long long), b->stream));  // (product builds never write the phase accumulators)
 #endif
-  u32 grid_full = (u32)((b->m + LBFT_BLOCK - 1) / LBFT_BLOCK);
+  // a whole simulation in one launch: the unfinished count and the batch counters, neighbours in memory, are zeroed by ONE fill ahead of
+  // the whole sequence instead of one in front of the run kernel and one in front of the counters kernel
+  const bool tail_zeroed = p.max_steps == 0;
+  // (everything in front of the check words, 128 bytes: a fill of 120 bytes ran as two fill kernels, the multiple of 16 and the rest)
+  if (tail_zeroed) HIP_TRY(hipMemsetAsync(b->d_counters, 0, TAIL_CHECK * sizeof(unsigned long long), b->stream));
   { int src = start_run(b); if (src != LBFT_OK) return src; }
   u64 launches = 0;
   for (;;) {
-    int rc = launch_run(b);
+    int rc = launch_run(b, tail_zeroed);
     if (rc != LBFT_OK) return rc;
     launches++;
     if (p.max_steps == 0) break;  // whole simulation in one launch
@@ -929,18 +956,18 @@ int lbft_batch_run_until(lbft_batch* b, int64_t max_clock) {
     if (unfinished == 0) break;
   }
   HIP_TRY(hipEventRecord(b->ev2, b->stream));
-  return finalize_run(b, grid_full, launches);
+  return finalize_run(b, launches, tail_zeroed);
 }
 
 // One launch of the batch's run kernel (LaunchPlan::kernel), as its row of lbft_plan.h's table says: a kernel of this library, or a
 // lane-private twin through its library's launcher, which is told the class (K_SMALL or K_MID) and given the batch's parameter sets
 // (none: a null pointer) and commit-time buffer.
-static int launch_run(lbft_batch* b) {
+static int launch_run(lbft_batch* b, bool tail_zeroed) {
   Params& p = b->p;
   const size_t lds = b->launch.lds_bytes;
   const u32 nwaves = b->launch.run_waves, block = 64u * nwaves;
   u32 grid_run = (u32)((b->m + (size_t)nwaves * p.lpw - 1) / ((size_t)nwaves * p.lpw));
-  HIP_TRY(hipMemsetAsync(b->d_unfinished, 0, sizeof(u32), b->stream));
+  if (!tail_zeroed) HIP_TRY(hipMemsetAsync(b->d_unfinished, 0, sizeof(u32), b->stream));
   b->generation++;
   const int cls = sim_class(p);
 #define LBFT_LAUNCH_LIB_HIP(KERNEL) launch_run_kernel(KERNEL, grid_run, block, lds, b->stream, p, b->d_state, b->d_unfinished)
@@ -979,7 +1006,7 @@ int lbft_batch_run_steps(lbft_batch* b, int64_t max_clock, uint32_t steps, uint6
   if (left == 0) {
     HIP_TRY(hipEventRecord(b->ev2, b->stream));
     b->started = false;
-    return finalize_run(b, (u32)((b->m + LBFT_BLOCK - 1) / LBFT_BLOCK), b->step_launches);
+    return finalize_run(b, b->step_launches);
   }
   return LBFT_OK;
 }
@@ -1069,17 +1096,54 @@ int lbft_batch_checkpoint_load(lbft_batch* b, const void* buf, size_t len) {
   return LBFT_OK;
 }
 
-static int finalize_run(lbft_batch* b, u32 grid_full, u64 launches) {
-  Params& p = b->p;
-  HIP_TRY(hipMemsetAsync(b->d_counters, 0, C_WORDS * sizeof(unsigned long long), b->stream));
-  lbft_k_finalize<<<dim3(grid_full, (p.n + LBFT_FINAL_WAVES - 1) / LBFT_FINAL_WAVES), LBFT_BLOCK * LBFT_FINAL_WAVES, 0, b->stream>>>(p, b->d_state, b->d_states_out, b->d_counters);
-  HIP_TRY(hipGetLastError());
-  // reset + init + run + finalize + this copy are ONE stream sequence with a single synchronisation at its end (no host round trip in between); the
-  // destination is pinned, so the copy is a DMA behind the finalize kernel instead of a staged copy with a synchronisation of its own
+static const char* const COUNTER_NAMES[C_WORDS] = {"events[0]", "events[1]", "events[2]", "events[3]", "rng_draws", "rounds", "commits", "events_scheduled",
+                                                   "faulted_instances", "timers_folded", "node_updates", "max_queue", "max_snapshots", "max_blocks"};
+static hipError_t launch_finalize(const lbft_batch* b, unsigned long long* d_counters) {
+  const Params& p = b->p;
+  const u32 grid_full = (u32)((b->m + LBFT_BLOCK - 1) / LBFT_BLOCK);
+  lbft_k_finalize<<<dim3(grid_full, (p.n + LBFT_FINAL_WAVES - 1) / LBFT_FINAL_WAVES), LBFT_BLOCK * LBFT_FINAL_WAVES, 0, b->stream>>>(p, b->d_state, b->d_states_out, d_counters);
+  return hipGetLastError();
+}
+// The State hashes of the last finished run into d_states_out, if they are not there yet: lbft_k_finalize, at most once per finished run.
+// Its counters go to words of their own (the batch's are never added to twice) and are the old reduction of the same state: all
+// fourteen are compared with what lbft_k_ps_counters gave the run.  Called by every reader of d_states_out, and by every call that is
+// accepted after a finished run and changes the state rows -- before it does, so that the hashes stay those of the run.
+static int materialise_hashes(const lbft_batch* b) {
+  std::lock_guard<std::mutex> lock(b->hash_mutex);
+  if (!b->hashes_pending) return LBFT_OK;
+  if (b->hash_generation != b->generation) { g_err = "the state changed after the run whose State hashes were still to be computed"; return LBFT_ERR_STATE; }
+  unsigned long long old_words[C_WORDS];
+  HIP_TRY(hipMemsetAsync(b->d_check, 0, sizeof(old_words), b->stream));
+  HIP_TRY(launch_finalize(b, b->d_check));
+  HIP_TRY(hipMemcpyAsync(old_words, b->d_check, sizeof(old_words), hipMemcpyDeviceToHost, b->stream));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  for (int k = 0; k < C_WORDS; k++)
+    if (old_words[k] != b->run_words[k]) {
+      g_err = std::string("batch counter ") + COUNTER_NAMES[k] + ": lbft_k_ps_counters gave the run " + std::to_string(b->run_words[k]) + ", lbft_k_finalize gives " +
+              std::to_string(old_words[k]) + " for the same state";
+      return LBFT_ERR_STATE;
+    }
+  b->hashes_pending = false;
+  return LBFT_OK;
+}
+
+static int finalize_run(lbft_batch* b, u64 launches, bool tail_zeroed) {
+  const bool lean = lean_counters();
+  if (!tail_zeroed) HIP_TRY(hipMemsetAsync(b->d_counters, 0, C_WORDS * sizeof(unsigned long long), b->stream));
+  if (lean) HIP_TRY(g_ps_counters(&b->p, b->d_state, b->d_counters, b->stream));
+  else HIP_TRY(launch_finalize(b, b->d_counters));
+  // reset + init + run + counters + this copy are ONE stream sequence with a single synchronisation at its end (no host round trip in between); the
+  // destination is pinned, so the copy is a DMA behind the counters kernel instead of a staged copy with a synchronisation of its own
   if (!b->h_counters) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&b->h_counters), C_WORDS * sizeof(unsigned long long), hipHostMallocDefault));
   unsigned long long* hc = b->h_counters;
   HIP_TRY(hipMemcpyAsync(hc, b->d_counters, C_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, b->stream));
   HIP_TRY(hipStreamSynchronize(b->stream));
+  {
+    std::lock_guard<std::mutex> lock(b->hash_mutex);
+    b->hashes_pending = lean;
+    b->hash_generation = b->generation;
+    memcpy(b->run_words, hc, C_WORDS * sizeof(unsigned long long));
+  }
   HIP_TRY(hipEventElapsedTime(&b->init_ms, b->ev0, b->ev1));
   HIP_TRY(hipEventElapsedTime(&b->run_ms, b->ev1, b->ev2));
   lbft_counters& k = b->counters;
@@ -1124,6 +1188,7 @@ int lbft_batch_last_committed_states(const lbft_batch* b, uint64_t* out) {
   if (!b || !out) return LBFT_ERR_INVALID;
   if (!b->ran) { g_err = "run the batch first"; return LBFT_ERR_STATE; }
   HIP_TRY(hipSetDevice(b->device));
+  { int mrc = materialise_hashes(b); if (mrc != LBFT_OK) return mrc; }
   HIP_TRY(hipMemcpy(out, b->d_states_out, b->m * b->p.n * sizeof(u64), hipMemcpyDeviceToHost));
   return LBFT_OK;
 }
@@ -1133,6 +1198,7 @@ int lbft_batch_last_committed_state(const lbft_batch* b, size_t inst, uint32_t n
   if (!b || !out || inst >= b->m || node >= b->p.n) return LBFT_ERR_INVALID;
   if (!b->ran) { g_err = "run the batch first"; return LBFT_ERR_STATE; }
   HIP_TRY(hipSetDevice(b->device));
+  { int mrc = materialise_hashes(b); if (mrc != LBFT_OK) return mrc; }
   HIP_TRY(hipMemcpy(out, b->d_states_out + inst * b->p.n + node, sizeof(u64), hipMemcpyDeviceToHost));
   return LBFT_OK;
 }
@@ -1623,6 +1689,7 @@ int lbft_batch_load_node(lbft_batch* b, size_t inst, uint32_t node, const void* 
   if (!b->ran && !b->manual && !b->started) { g_err = "run the batch (or start a node-level session) first"; return LBFT_ERR_STATE; }
   if (b->ctimes) { g_err = "load_node is not available on a batch that records commit times: a loaded history has none"; return LBFT_ERR_UNSUPPORTED; }
   HIP_TRY(hipSetDevice(b->device));
+  { int mrc = materialise_hashes(b); if (mrc != LBFT_OK) return mrc; }  // (after a finished run: its hashes are those of the state before the load)
   const Params& dp = b->p;
   std::lock_guard<std::mutex> sn_lock(b->sn_mutex);
   std::vector<u32> hw(dp.total_words);

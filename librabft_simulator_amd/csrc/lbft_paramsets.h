@@ -18,6 +18,9 @@ typedef hipError_t (*lbft_ps_init_fn)(const lbft::Params* p, lbft::u32* state, c
 // One launch of the run kernel of class `cls` (K_SMALL or K_MID) with the geometry prepare_run chose.
 typedef hipError_t (*lbft_ps_run_fn)(int cls, const lbft::Params* p, lbft::u32* state, lbft::u32* unfinished, const lbft::ParamSetDev* sets,
                                      const lbft::u8* set_of, lbft::u32 grid, lbft::u32 block, size_t lds_bytes, hipStream_t stream);
+// The fourteen batch counters of a finished run (lbft_batch_counters.h) added to counters[], which the caller zeroed: for batches of
+// every kind, plain ones included -- those fall back to lbft_k_finalize when this library is missing.
+typedef hipError_t (*lbft_ps_counters_fn)(const lbft::Params* p, const lbft::u32* state, unsigned long long* counters, hipStream_t stream);
 }
 
 #endif  // LBFT_PARAMSETS_H

@@ -38,7 +38,37 @@ void lbft_k_ps_run1(Params p, u32* __restrict__ state, u32* __restrict__ unfinis
   run_body<K_MID_SETS>(p, state, unfinished, sets, set_of);
 }
 
+// The batch counters of a finished run without the State hashes: the tail of lbft_k_finalize (liblbft_hip.so) as a kernel of its own, for
+// batches of every kind -- it reads the instance's scalar rows and two words per node through the generic accessors, whatever kernel ran.
+// One lane per instance; a workgroup of LBFT_COUNTER_WAVES wavefronts reduces its instances' words (shuffles within a wavefront, then
+// LDS across the wavefronts) and adds them to the batch's with ONE atomic per counter: the atomics of a run all go to one 128-byte line.
+#include "lbft_batch_counters.h"
+#define LBFT_COUNTER_WAVES 16
+__global__ __launch_bounds__(64 * LBFT_COUNTER_WAVES) void lbft_k_ps_counters(Params p, const u32* __restrict__ state, unsigned long long* __restrict__ counters) {
+  __shared__ u64 part[LBFT_COUNTER_WAVES][C_WORDS];
+  u64 c[C_WORDS];
+  instance_counter_words(p, state, blockIdx.x * (64 * LBFT_COUNTER_WAVES) + threadIdx.x, c);
+  for (int k = 0; k < C_WORDS; k++) {
+    u64 r = k >= C_MAXQ ? wave_max(c[k]) : wave_sum(c[k]);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][k] = r;
+  }
+  __syncthreads();
+  if (threadIdx.x >= C_WORDS) return;
+  const u32 k = threadIdx.x;
+  const bool is_max = k >= C_MAXQ;
+  u64 r = part[0][k];
+  for (int w = 1; w < LBFT_COUNTER_WAVES; w++) r = is_max ? (part[w][k] > r ? part[w][k] : r) : r + part[w][k];
+  if (is_max) atomicMax(&counters[k], (unsigned long long)r);
+  else atomicAdd(&counters[k], (unsigned long long)r);
+}
+
 extern "C" {
+
+__attribute__((visibility("default"))) hipError_t lbft_ps_launch_counters(const Params* p, const u32* state, unsigned long long* counters, hipStream_t stream) {
+  const u32 per_group = 64 * LBFT_COUNTER_WAVES;
+  lbft_k_ps_counters<<<(p->m + per_group - 1) / per_group, per_group, 0, stream>>>(*p, state, counters);
+  return hipGetLastError();
+}
 
 __attribute__((visibility("default"))) hipError_t lbft_ps_launch_init(const Params* p, u32* state, const u64* seeds, const ParamSetDev* sets, const u8* set_of,
                                                                      u32 grid, hipStream_t stream) {
