@@ -14,6 +14,8 @@
 
 using namespace lbft;
 
+#include "lbft_chain_walk.h"  // the node pass, the proposal time
+
 // One wavefront per instance.  The kernel reads, through the generic Sim accessors (every layout: tile widths 1, lanes per wavefront,
 // 64), the instance's fault word, NF_NCOMMITS and NF_STARTUP of its nodes, the log rows log[n][lcap] and of the block records B_LINK
 // and B_TIME.
@@ -66,15 +68,10 @@ __global__ __launch_bounds__(LBFT_CS_BLOCK) void lbft_k_cs_chain(Params p, const
       if (s.ld(I_FAULT) != 0) continue;
       // node pass
       u32 nc[LBFT_CS_NODE_ROUNDS];
-      u64 best = 0;
 #pragma unroll
-      for (u32 r = 0; r < LBFT_CS_NODE_ROUNDS; r++) {
-        const u32 j = r * 64 + lane;
-        nc[r] = j < n ? chn_commits(s.nfm(j, NF_NCOMMITS), lcap) : 0;
-        if (j < n) best = chn_ref_max(best, chn_ref_key(nc[r], j));
-      }
-      for (int d = 32; d; d >>= 1) best = chn_ref_max(best, (u64)__shfl_xor((unsigned long long)best, d, 64));
-      const u32 L = chn_ref_len(best), ref = chn_ref_node(best);
+      for (u32 r = 0; r < LBFT_CS_NODE_ROUNDS; r++) nc[r] = cw_commits(s, r * 64 + lane, n, lcap);
+      const CwChain ch = cw_node_pass<LBFT_CS_NODE_ROUNDS>(nc, lane, n, 64u);
+      const u32 L = ch.L, ref = ch.ref;
       if (stat_pass) {
 #pragma unroll
         for (u32 r = 0; r < LBFT_CS_NODE_ROUNDS; r++)
@@ -92,7 +89,7 @@ __global__ __launch_bounds__(LBFT_CS_BLOCK) void lbft_k_cs_chain(Params p, const
         if (have) {
           b = s.ld(lg + ref * lcap + k);
           a = s.blk_author(b);
-          gt = (i32)(s.nfm(a, NF_STARTUP) + s.bf(b, B_TIME));
+          gt = cw_proposal(s, b, a);
         }
         i32 pg = __shfl_up(gt, 1, 64);
         u32 pa = (u32)__shfl_up((int)a, 1, 64);

@@ -66,5 +66,15 @@ LBFT_HD bool fin_open(const FinEntry& e) { return e.committers != 0 && e.quorum 
 // A sample: a time of the entry after its proposal time g_k, or after its first commit.  Nothing is clamped: a time before its origin
 // would show as a sample above max_clock (the tests' reference asserts that there is none).
 LBFT_HD uint32_t fin_after(int32_t t, int32_t origin) { return (uint32_t)t - (uint32_t)origin; }
+// The samples an entry gives the families first .. spread, each with its guard: f(family, sample), in the families' order.  g = the
+// entry's proposal time.  (The sixth family, FIN_OPEN, is one sample per instance: the count of its fin_open entries.)
+template <class F>
+LBFT_HD void fin_samples(const FinEntry& e, uint32_t n, int32_t g, F&& f) {
+  const int32_t all = fin_all(e, n);
+  if (e.committers) f(FIN_FIRST, fin_after(e.first, g));
+  if (e.valid >= 0) f(FIN_VALID, fin_after(e.valid, g));
+  if (e.quorum >= 0) f(FIN_QUORUM, fin_after(e.quorum, g));
+  if (all >= 0) { f(FIN_ALL, fin_after(all, g)); f(FIN_SPREAD, fin_after(all, e.first)); }
+}
 
 #endif  // LBFT_COMMIT_FINALITY_H

@@ -26,6 +26,7 @@ using namespace lbft;
 
 #include "lbft_launch.h"
 #include "lbft_run_body.h"  // run_body
+#include "lbft_chain_walk.h"
 
 // Small class (lbft_k_run0's geometry: two wavefronts per SIMD) and mid class (lbft_k_run<1>'s: one wavefront per SIMD, the whole register
 // file), each plain and with parameter sets.
@@ -84,9 +85,7 @@ __global__ __launch_bounds__(LBFT_HIST_BLOCK) void lbft_k_ct_latency_hist(Params
       const i32 c = ct[k];
       if (c < 0) continue;  // (not recorded)
       const u32 b = s.ld(p.off_log + node * p.lcap + k);
-      const u32 a = s.blk_author(b);
-      const i64 lat = (i64)c - ((i64)(i32)s.nfm(a, NF_STARTUP) + (i64)(i32)s.bf(b, B_TIME));  // in [0, max_clock]
-      const u32 l = (u32)lat;  // (max_clock < 2^31: nothing is cut off)
+      const u32 l = fin_after(c, cw_proposal(s, b));  // in [0, max_clock]
       gs_lds_count(h, l, bin_width, bins, base, span);
       if (base == 0) gs_stat_add(st, l);
     }
@@ -174,13 +173,7 @@ __global__ __launch_bounds__(LBFT_TL_BLOCK) void lbft_k_ct_timeline(Params p, co
         }
       }
       if (stalls && base == 0) {
-        for (u32 d = LBFT_TL_SEG / 2; d; d >>= 1) {
-          CtlRow o;
-          o.longest = (u32)__shfl_xor((int)row.longest, (int)d, LBFT_TL_SEG);
-          o.last = __shfl_xor(row.last, (int)d, LBFT_TL_SEG);
-          o.first = (u32)__shfl_xor((int)row.first, (int)d, LBFT_TL_SEG);
-          row = ctl_merge(row, o);
-        }
+        for (int d = LBFT_TL_SEG / 2; d; d >>= 1) row = ctl_merge_step<LBFT_TL_SEG>(row, d);
         if (k0 == 0) {  // one sample per node
           if (row.first != LBFT_CTL_NONE) gs_stat_add(st[CTL_FIRST], row.first);
           gs_stat_add(st[CTL_TAIL], ctl_tail(row, p.max_clock));
@@ -197,16 +190,9 @@ __global__ __launch_bounds__(LBFT_TL_BLOCK) void lbft_k_ct_timeline(Params p, co
 }
 
 // Commit finality (lbft_batch_commit_finality): per entry of an instance's chain, the commit times of all its nodes -- an order
-// statistic under the voting rights (lbft_commit_finality.h).  One wavefront per instance, through the generic Sim accessors (timed
-// batches: instance-major rows or 64-wide tiles).
-//   node pass (lane = node, n <= LBFT_FN_MAX_NODES): nc_j = min(NF_NCOMMITS, lcap); a butterfly over the keys (nc_j, ~j) gives the
-//     chain's length L and the reference node, as in lbft_k_cs_chain.
-//   chain pass (lane = entry, 64 at a time): the n rows ctimes[i][j][c0 .. c0 + 63] -- a row load of the wavefront is 256 contiguous
-//     bytes -- go into the wavefront's [n][64] LDS tile, FIN_NONE where the node is no committer of the entry; b = log[ref][k] and the
-//     dependent gathers B_LINK, B_TIME and startup[author] give the proposal time g_k.  Each lane then walks its own column of the tile
-//     (fin_entry: n^2 LDS reads at consecutive addresses across the lanes, no bank conflict, no sort, no per-lane array).  A lane reads
-//     only what it wrote itself: the tile needs no barrier.
-// The rights table (at most LBFT_FN_MAX_NODES words) is copied into LDS once per workgroup; with unit rights it is not read.
+// statistic under the voting rights (lbft_commit_finality.h).  The walk -- node pass, chunks of 64 entries, the [n][64] tile, the rights
+// table in LDS -- is lbft_chain_walk.h's; the kernel adds what becomes of a column (fin_samples, the two histograms, the first committer,
+// the open entries).
 // grid = (workgroups per group, groups); a workgroup's LBFT_FN_WAVES wavefronts stride over the instances of its group and accumulate by
 // the scheme of lbft_group_stats.h: two LDS histograms (quorum finality and spread) in passes of LBFT_FN_LDS_BINS bins, the first
 // committers (n bins) in the first pass, the statistics in registers in the first pass.  Instances with a non-zero fault word are
@@ -214,7 +200,7 @@ __global__ __launch_bounds__(LBFT_TL_BLOCK) void lbft_k_ct_timeline(Params p, co
 // 65 984 B, two workgroups per CU.
 #define LBFT_FN_BLOCK 256
 #define LBFT_FN_WAVES (LBFT_FN_BLOCK / 64)
-#define LBFT_FN_MAX_NODES 32  // (timed batches have at most 32 nodes: lbft_batch_record_commit_times)
+#define LBFT_FN_MAX_NODES CW_MAX_NODES
 #define LBFT_FN_LDS_BINS 4096  // each of the two histograms: 16 KiB of u32 counts
 #define LBFT_FN_WORKGROUPS 1024u
 static_assert(LBFT_FINALITY_STATS == FIN_FAMILIES * 4, "six families of (samples, sum, min, max)");
@@ -228,17 +214,9 @@ __global__ __launch_bounds__(LBFT_FN_BLOCK) void lbft_k_ct_finality(Params p, co
   __shared__ i32 tile[LBFT_FN_WAVES][LBFT_FN_MAX_NODES][64];
   __shared__ u32 h_fin[LBFT_FN_LDS_BINS], h_spr[LBFT_FN_LDS_BINS], h_fc[LBFT_FN_MAX_NODES], s_rights[LBFT_FN_MAX_NODES];
   __shared__ unsigned long long s_stat[LBFT_FINALITY_STATS];
-  const u32 g = blockIdx.y;
-  const uint2 grp = gs_group(grp_inst, grp_off, g, p.m);
-  const u32 first = grp.x, cnt = grp.y;
-  if (blockIdx.x * LBFT_FN_WAVES >= cnt) return;  // (the whole workgroup: its group has fewer instances)
-  const u32 wave = threadIdx.x / 64, lane = threadIdx.x % 64;
-  const u32 n = p.n, lcap = p.lcap, lg = p.off_log;
-  const u32 cpe = fin_cpe32(p.cpe), rot = p.rot;
-  const u32 t_quorum = p.quorum, t_valid = fin_valid_threshold(p.total_votes, p.quorum);
-  const u32* rights = p.unit_weights ? nullptr : s_rights;
-  i32* col = &tile[wave][0][lane];  // this lane's column: node j at col[j * 64]
-  if (threadIdx.x < n) s_rights[threadIdx.x] = p.weights[threadIdx.x];  // (read after the pass loop's first barrier)
+  CwWalk w;
+  if (!cw_begin(w, p, grp_inst, grp_off, tile, s_rights)) return;  // (the rights: read after the pass loop's first barrier)
+  const u32 n = w.n, lane = w.lane;
   gs_stats_clear<LBFT_FINALITY_STATS>(s_stat);
   GsStat st[FIN_FAMILIES] = {};
   for (u32 base = 0; base < bins; base += LBFT_FN_LDS_BINS) {
@@ -248,38 +226,25 @@ __global__ __launch_bounds__(LBFT_FN_BLOCK) void lbft_k_ct_finality(Params p, co
     gs_lds_clear<LBFT_FN_BLOCK>(h_spr, span);
     if (stat_pass) gs_lds_clear<LBFT_FN_BLOCK>(h_fc, n);
     __syncthreads();
-    for (u32 q = blockIdx.x * LBFT_FN_WAVES + wave; q < cnt; q += gridDim.x * LBFT_FN_WAVES) {  // (one instance per wavefront: uniform in it)
-      const u32 i = gs_instance(grp_inst, first, q);
+    for (u32 q = blockIdx.x * LBFT_FN_WAVES + w.wave; q < w.cnt; q += gridDim.x * LBFT_FN_WAVES) {  // (one instance per wavefront: uniform in it)
+      const u32 i = gs_instance(grp_inst, w.first, q);
       Sim s(p, const_cast<u32*>(state), i);
       if (s.ld(I_FAULT) != 0) continue;
-      // node pass
-      const u32 nc = lane < n ? chn_commits(s.nfm(lane, NF_NCOMMITS), lcap) : 0;
-      u64 best = lane < n ? chn_ref_key(nc, lane) : 0;
-      for (int d = 32; d; d >>= 1) best = chn_ref_max(best, (u64)__shfl_xor((unsigned long long)best, d, 64));
-      const u32 L = chn_ref_len(best), ref = chn_ref_node(best);
-      // chain pass
+      const u32 nc = cw_commits(s, lane, n, w.lcap);
+      const CwChain ch = cw_node_pass<1>(&nc, lane, n, 64u);
       u32 open = 0;
-      for (u32 c0 = 0; c0 < L; c0 += 64) {
+      for (u32 c0 = 0; c0 < ch.L; c0 += 64) {
         const u32 k = c0 + lane;
-        const bool have = k < L;
-        for (u32 j = 0; j < n; j++) {
-          const u32 ncj = (u32)__shfl((int)nc, (int)j, 64);
-          const i32 c = k < ncj ? ctimes[((size_t)i * n + j) * lcap + k] : FIN_NONE;  // (k < nc_j <= lcap: inside the row)
-          col[j * 64] = fin_committer(k, ncj, c) ? c : FIN_NONE;
-        }
-        if (!have) continue;
-        const u32 b = s.ld(lg + ref * lcap + k);
-        const u32 a = s.blk_author(b);
-        const i32 gt = (i32)(s.nfm(a, NF_STARTUP) + s.bf(b, B_TIME));
-        const FinEntry e = fin_entry(col, 64u, n, rights, fin_rights_shift(k, cpe, rot, n), t_valid, t_quorum);
+        for (u32 j = 0; j < n; j++) cw_stage(w, ctimes, i, nc, j, k);
+        if (k >= ch.L) continue;
+        const i32 gt = cw_proposal(s, s.ld(w.lg + ch.ref * w.lcap + k));
+        const FinEntry e = cw_column(w, k);
         const i32 all = fin_all(e, n);
         if (e.quorum >= 0) gs_lds_count(h_fin, fin_after(e.quorum, gt), bin_width, bins, base, span);
         if (all >= 0) gs_lds_count(h_spr, fin_after(all, e.first), bin_width, bins, base, span);
         if (!stat_pass) continue;
-        if (e.committers) { gs_stat_add(st[FIN_FIRST], fin_after(e.first, gt)); gs_lds_count(h_fc, e.first_node, 1u, n, 0u, n); }
-        if (e.valid >= 0) gs_stat_add(st[FIN_VALID], fin_after(e.valid, gt));
-        if (e.quorum >= 0) gs_stat_add(st[FIN_QUORUM], fin_after(e.quorum, gt));
-        if (all >= 0) { gs_stat_add(st[FIN_ALL], fin_after(all, gt)); gs_stat_add(st[FIN_SPREAD], fin_after(all, e.first)); }
+        fin_samples(e, n, gt, [&](u32 family, u32 v) { gs_stat_add(st[family], v); });
+        if (e.committers) gs_lds_count(h_fc, e.first_node, 1u, n, 0u, n);
         open += fin_open(e) ? 1u : 0u;
       }
       if (stat_pass) {
@@ -289,11 +254,11 @@ __global__ __launch_bounds__(LBFT_FN_BLOCK) void lbft_k_ct_finality(Params p, co
     }
     if (stat_pass) gs_reduce_to_lds<FIN_FAMILIES>(st, s_stat, lane == 0);
     __syncthreads();
-    gs_lds_flush<LBFT_FN_BLOCK>(h_fin, finality_hist, g, bins, base, span);
-    gs_lds_flush<LBFT_FN_BLOCK>(h_spr, spread_hist, g, bins, base, span);
+    gs_lds_flush<LBFT_FN_BLOCK>(h_fin, finality_hist, w.g, bins, base, span);
+    gs_lds_flush<LBFT_FN_BLOCK>(h_spr, spread_hist, w.g, bins, base, span);
     if (stat_pass) {
-      gs_lds_flush<LBFT_FN_BLOCK>(h_fc, first_committer, g, n, 0u, n);
-      gs_stats_out<LBFT_FINALITY_STATS>(s_stat, stats, g);
+      gs_lds_flush<LBFT_FN_BLOCK>(h_fc, first_committer, w.g, n, 0u, n);
+      gs_stats_out<LBFT_FINALITY_STATS>(s_stat, stats, w.g);
     }
     __syncthreads();  // (before the next pass clears the histograms)
   }
@@ -302,13 +267,10 @@ __global__ __launch_bounds__(LBFT_FN_BLOCK) void lbft_k_ct_finality(Params p, co
 // Per-instance statistics (lbft_batch_instance_stats): the samples of the three kernels above, with the instance as the unit -- no
 // histogram, no atomic, one writer per row (lbft_instance_stats.h).  One wavefront per instance, IST_WAVES per workgroup, striding over
 // the instances of the workgroup's group (a group matters for `since` alone), through the generic Sim accessors.
-//   node pass and chain pass: lbft_k_ct_finality's -- the reference node, L, nc_j; 64 entries at a time, the n commit-time rows staged
-//     in the wavefront's [n][64] LDS tile, g_k from the reference node's log.  While row j of a chunk is staged, its entries also give
-//     the timeline samples -- the predecessor c_j(k - 1) is the lower lane's entry (__shfl_up; lane 0 reads the row's word before the
-//     chunk, so no carry is kept), ctl_entry makes the gap sample, and the chunk's CtlRow is reduced by a butterfly and merged into lane
-//     j's (lane = node) -- and the latency sample c_j(k) - g_k where log[j][k] == log[ref][k], else after the proposal time of the node's
-//     own block.  Lane k then walks its column of the tile (fin_entry) for the six finality quantities.  A lane reads only LDS words it
-//     wrote itself: no barrier.
+//   node pass and chain pass: lbft_chain_walk.h's.  While row j of a chunk is staged, its entries also give the timeline samples -- the
+//     predecessor c_j(k - 1) is the lower lane's entry (__shfl_up; lane 0 reads the row's word before the chunk, so no carry is kept),
+//     ctl_entry makes the gap sample, and the chunk's CtlRow is reduced by a butterfly and merged into lane j's (lane = node) -- and the
+//     latency sample c_j(k) - its origin (cw_own_proposal).  Lane k then takes the six finality quantities from its column (ist_column).
 //   closing pass (lane = node): the row's first / tail / longest samples.
 // Every family is accumulated per lane (IstStat), reduced by butterflies once per instance, and the row's IST_WORDS words are stored by
 // as many lanes: 352 contiguous bytes.  The row of an instance with a non-zero fault word is left as the caller zeroed it.
@@ -334,71 +296,48 @@ __global__ __launch_bounds__(LBFT_IS_BLOCK) void lbft_k_ct_instances(Params p, c
                                                                      const i32* __restrict__ since_of, unsigned long long* __restrict__ rows) {
   __shared__ i32 tile[IST_WAVES][LBFT_FN_MAX_NODES][64];
   __shared__ u32 s_rights[LBFT_FN_MAX_NODES];
-  const u32 g = blockIdx.y;
-  const uint2 grp = gs_group(grp_inst, grp_off, g, p.m);
-  const u32 first = grp.x, cnt = grp.y;
-  if (blockIdx.x * IST_WAVES >= cnt) return;  // (the whole workgroup: its group has fewer instances)
-  const u32 wave = threadIdx.x / 64, lane = threadIdx.x % 64;
-  const u32 n = p.n, lcap = p.lcap, lg = p.off_log;
-  const u32 cpe = fin_cpe32(p.cpe), rot = p.rot;
-  const u32 t_quorum = p.quorum, t_valid = fin_valid_threshold(p.total_votes, p.quorum);
-  const u32* rights = p.unit_weights ? nullptr : s_rights;
-  const i32 since = since_of ? since_of[g] : 0;
-  i32* col = &tile[wave][0][lane];  // this lane's column: node j at col[j * 64]
-  if (threadIdx.x < n) s_rights[threadIdx.x] = p.weights[threadIdx.x];
+  CwWalk w;
+  if (!cw_begin(w, p, grp_inst, grp_off, tile, s_rights)) return;
+  const u32 n = w.n, lane = w.lane;
+  const i32 since = since_of ? since_of[w.g] : 0;
   __syncthreads();
-  for (u32 q = blockIdx.x * IST_WAVES + wave; q < cnt; q += gridDim.x * IST_WAVES) {  // (one instance per wavefront: uniform in it)
-    const u32 i = gs_instance(grp_inst, first, q);
+  for (u32 q = blockIdx.x * IST_WAVES + w.wave; q < w.cnt; q += gridDim.x * IST_WAVES) {  // (one instance per wavefront: uniform in it)
+    const u32 i = gs_instance(grp_inst, w.first, q);
     Sim s(p, const_cast<u32*>(state), i);
     if (s.ld(I_FAULT) != 0) continue;
-    // node pass
-    const u32 nc = lane < n ? chn_commits(s.nfm(lane, NF_NCOMMITS), lcap) : 0;
-    u64 best = lane < n ? chn_ref_key(nc, lane) : 0;
-    for (int d = 32; d; d >>= 1) best = chn_ref_max(best, (u64)__shfl_xor((unsigned long long)best, d, 64));
-    const u32 L = chn_ref_len(best), ref = chn_ref_node(best);
-    // chain pass
+    const u32 nc = cw_commits(s, lane, n, w.lcap);
+    const CwChain ch = cw_node_pass<1>(&nc, lane, n, 64u);
     IstStat st[IST_FAMILIES];
     for (u32 f = 0; f < IST_FAMILIES; f++) st[f] = ist_empty();
     CtlRow row = ctl_empty();  // of node `lane`
     u32 open = 0;
-    for (u32 c0 = 0; c0 < L; c0 += 64) {
+    for (u32 c0 = 0; c0 < ch.L; c0 += 64) {
       const u32 k = c0 + lane;
-      const bool have = k < L;
+      const bool have = k < ch.L;
       u32 b = 0;
       i32 gt = 0;
       if (have) {
-        b = s.ld(lg + ref * lcap + k);
-        gt = (i32)(s.nfm(s.blk_author(b), NF_STARTUP) + s.bf(b, B_TIME));
+        b = s.ld(w.lg + ch.ref * w.lcap + k);
+        gt = cw_proposal(s, b);
       }
       for (u32 j = 0; j < n; j++) {
-        const u32 ncj = (u32)__shfl((int)nc, (int)j, 64);
-        const i32* ct = ctimes + ((size_t)i * n + j) * lcap;
-        i32 c = k < ncj ? ct[k] : FIN_NONE;  // (k < nc_j <= lcap: inside the row)
-        c = fin_committer(k, ncj, c) ? c : FIN_NONE;
-        col[j * 64] = c;
+        const CwStaged e = cw_stage(w, ctimes, i, nc, j, k);
+        const i32 c = e.c;
+        // Lane 0: the last entry of the row's previous chunk.  The load stays in front of the shuffle: folded into the `if` below it the
+        // kernel was 6 % slower on 32-node batches (where its code falls, EXPERIMENTS.md "One chain walk"), so time the call after moving it.
+        const i32 before = lane == 0 && c0 && k < e.commits ? e.ct[k - 1] : -1;
         i32 prev = __shfl_up(c, 1, 64);
-        if (lane == 0) prev = c0 && k < ncj ? ct[k - 1] : -1;  // the last entry of the row's previous chunk
+        if (lane == 0) prev = before;
         CtlRow r = ctl_empty();
         const u32 gap = ctl_entry(r, c, prev, since);
         if (gap) ist_add(st[IST_STALLS + CTL_GAPS], gap);
-        for (int d = 32; d; d >>= 1) {
-          CtlRow o;
-          o.longest = (u32)__shfl_xor((int)r.longest, d, 64);
-          o.last = __shfl_xor(r.last, d, 64);
-          o.first = (u32)__shfl_xor((int)r.first, d, 64);
-          r = ctl_merge(r, o);
-        }
+        for (int d = 32; d; d >>= 1) r = ctl_merge_step<64>(r, d);
         if (lane == j) row = ctl_merge(row, r);
-        if (c >= 0) {  // (then k < nc_j <= L: b and gt are the chain's)
-          const u32 bj = s.ld(lg + j * lcap + k);
-          i32 gj = gt;
-          if (bj != b) gj = (i32)(s.nfm(s.blk_author(bj), NF_STARTUP) + s.bf(bj, B_TIME));  // (the node's own block)
-          ist_add(st[IST_LATENCY], ist_latency(c, gj));
-        }
+        if (c >= 0) ist_add(st[IST_LATENCY], ist_latency(c, cw_own_proposal(s, w, j, k, b, gt)));
       }
-      if (have) open += ist_column(st, fin_entry(col, 64u, n, rights, fin_rights_shift(k, cpe, rot, n), t_valid, t_quorum), n, gt);
+      if (have) open += ist_column(st, cw_column(w, k), n, gt);
     }
-    // closing pass
+    // closing pass (lane = node)
     if (lane < n) ist_node(st, row, p.max_clock);
     for (int d = 32; d; d >>= 1) open += (u32)__shfl_xor((int)open, d, 64);
     if (lane == 0) ist_add(st[IST_FINALITY + FIN_OPEN], open);  // one sample per instance
@@ -414,20 +353,19 @@ __global__ __launch_bounds__(LBFT_IS_BLOCK) void lbft_k_ct_instances(Params p, c
 }
 
 // Commit phases (lbft_batch_commit_phases): the latency histogram's samples and the finality's families first .. spread, split by the
-// phase of the entry's proposal time (lbft_commit_phases.h) -- the second grouping axis.  The mapping is lbft_k_ct_finality's: one
-// wavefront per instance, LBFT_PH_WAVES per workgroup striding over the instances of the workgroup's group, the node pass, the chain 64
-// entries at a time through the wavefront's [n][64] LDS tile.  While row j of a chunk is staged, lane k also takes the latency sample
-// c_j(k) - proposal time of the block in node j's own log, as lbft_k_ct_instances does (on the device that block is the chain's b_k and
-// the sample's phase the lane's; a node whose log differs has its own); lane k then walks its column (fin_entry).  The group's edges are
-// copied into LDS once per workgroup.
+// phase of the entry's proposal time (lbft_commit_phases.h) -- the second grouping axis.  The walk is lbft_chain_walk.h's, LBFT_PH_WAVES
+// wavefronts per workgroup striding over the instances of the workgroup's group.  While row j of a chunk is staged, lane k also takes
+// the latency sample c_j(k) - its origin (cw_own_proposal), in the origin's phase (on the device the origin is g_k and the phase the
+// lane's; a node whose log differs has its own); lane k then takes its column's samples (fin_samples) in the phase of g_k.  The group's
+// edges are copied into LDS once per workgroup.
 // Histograms: latency and quorum finality, each one virtual histogram of phases x bins bins (phase p's slice at p * bins), in passes of
 // LBFT_PH_LDS_BINS LDS bins by the scheme of lbft_group_stats.h; a group's slice of the global array is the virtual histogram itself.
 // Statistics, first pass: GsStat accumulators per phase in registers would be an array indexed by a run-time phase, which lands in
 // scratch; every sample goes, with four LDS integer atomics, into the workgroup's [phases][24] block of {samples, sum, max(~sample),
 // max} words, which is flushed once per workgroup by gs_stats_out's rule with the phase offset.  (The other form -- the lanes of a
 // chunk share one or two phases, so one butterfly per distinct phase and one lane's atomics -- is
-// profiles/commit_phases/ballot_prereduction.patch: faster with one phase, slower with three and eight, EXPERIMENTS.md "Commit
-// phases".)  Instances with a non-zero fault word are skipped.
+// profiles/commit_phases/ballot_prereduction.patch, against the kernel's body as it was before lbft_chain_walk.h: faster with one
+// phase, slower with three and eight, EXPERIMENTS.md "Commit phases".)  Instances with a non-zero fault word are skipped.
 // LDS: tile 32 KiB, histograms 2 x 16 KiB, 128 B rights, 32 B edges, 1536 B statistics: 67 232 B, two workgroups per CU.
 #define LBFT_PH_BLOCK 256
 #define LBFT_PH_WAVES (LBFT_PH_BLOCK / 64)
@@ -451,18 +389,10 @@ __global__ __launch_bounds__(LBFT_PH_BLOCK) void lbft_k_ct_phases(Params p, cons
   __shared__ u32 h_lat[LBFT_PH_LDS_BINS], h_fin[LBFT_PH_LDS_BINS], s_rights[LBFT_FN_MAX_NODES];
   __shared__ i32 s_edges[CPH_MAX_PHASES];
   __shared__ unsigned long long s_stat[CPH_MAX_PHASES * CPH_STATS];
-  const u32 g = blockIdx.y;
-  const uint2 grp = gs_group(grp_inst, grp_off, g, p.m);
-  const u32 first = grp.x, cnt = grp.y;
-  if (blockIdx.x * LBFT_PH_WAVES >= cnt) return;  // (the whole workgroup: its group has fewer instances)
-  const u32 wave = threadIdx.x / 64, lane = threadIdx.x % 64;
-  const u32 n = p.n, lcap = p.lcap, lg = p.off_log;
-  const u32 cpe = fin_cpe32(p.cpe), rot = p.rot;
-  const u32 t_quorum = p.quorum, t_valid = fin_valid_threshold(p.total_votes, p.quorum);
-  const u32* rights = p.unit_weights ? nullptr : s_rights;
+  CwWalk w;
+  if (!cw_begin(w, p, grp_inst, grp_off, tile, s_rights)) return;  // (the rights and the edges: read after the pass loop's first barrier)
+  const u32 n = w.n, lane = w.lane, g = w.g;
   const u32 n_edges = phases - 1u, vbins = phases * bins, words = phases * CPH_STATS;  // (phases x bins < 2^32: the launcher)
-  i32* col = &tile[wave][0][lane];  // this lane's column: node j at col[j * 64]
-  if (threadIdx.x < n) s_rights[threadIdx.x] = p.weights[threadIdx.x];  // (both read after the pass loop's first barrier)
   if (threadIdx.x < CPH_MAX_PHASES) s_edges[threadIdx.x] = threadIdx.x < n_edges ? edges[g * n_edges + threadIdx.x] : CPH_NO_EDGE;
   gs_stats_clear<CPH_MAX_PHASES * CPH_STATS>(s_stat);
   for (u32 base = 0; base < vbins; base += LBFT_PH_LDS_BINS) {
@@ -471,39 +401,27 @@ __global__ __launch_bounds__(LBFT_PH_BLOCK) void lbft_k_ct_phases(Params p, cons
     gs_lds_clear<LBFT_PH_BLOCK>(h_lat, span);
     gs_lds_clear<LBFT_PH_BLOCK>(h_fin, span);
     __syncthreads();
-    for (u32 q = blockIdx.x * LBFT_PH_WAVES + wave; q < cnt; q += gridDim.x * LBFT_PH_WAVES) {  // (one instance per wavefront: uniform in it)
-      const u32 i = gs_instance(grp_inst, first, q);
+    for (u32 q = blockIdx.x * LBFT_PH_WAVES + w.wave; q < w.cnt; q += gridDim.x * LBFT_PH_WAVES) {  // (one instance per wavefront: uniform in it)
+      const u32 i = gs_instance(grp_inst, w.first, q);
       Sim s(p, const_cast<u32*>(state), i);
       if (s.ld(I_FAULT) != 0) continue;
-      // node pass
-      const u32 nc = lane < n ? chn_commits(s.nfm(lane, NF_NCOMMITS), lcap) : 0;
-      u64 best = lane < n ? chn_ref_key(nc, lane) : 0;
-      for (int d = 32; d; d >>= 1) best = chn_ref_max(best, (u64)__shfl_xor((unsigned long long)best, d, 64));
-      const u32 L = chn_ref_len(best), ref = chn_ref_node(best);
-      // chain pass
-      for (u32 c0 = 0; c0 < L; c0 += 64) {
+      const u32 nc = cw_commits(s, lane, n, w.lcap);
+      const CwChain ch = cw_node_pass<1>(&nc, lane, n, 64u);
+      for (u32 c0 = 0; c0 < ch.L; c0 += 64) {
         const u32 k = c0 + lane;
-        const bool have = k < L;
+        const bool have = k < ch.L;
         u32 b = 0;
         i32 gt = 0;
         if (have) {
-          b = s.ld(lg + ref * lcap + k);
-          gt = (i32)(s.nfm(s.blk_author(b), NF_STARTUP) + s.bf(b, B_TIME));
+          b = s.ld(w.lg + ch.ref * w.lcap + k);
+          gt = cw_proposal(s, b);
         }
         const u32 ph = cph_phase(s_edges, gt);
         for (u32 j = 0; j < n; j++) {
-          const u32 ncj = (u32)__shfl((int)nc, (int)j, 64);
-          i32 c = k < ncj ? ctimes[((size_t)i * n + j) * lcap + k] : FIN_NONE;  // (k < nc_j <= lcap: inside the row)
-          c = fin_committer(k, ncj, c) ? c : FIN_NONE;
-          col[j * 64] = c;
-          if (c >= 0) {  // (then k < nc_j <= L: b, gt and ph are the chain's)
-            const u32 bj = s.ld(lg + j * lcap + k);
-            i32 gj = gt;
-            u32 pj = ph;
-            if (bj != b) {  // (the node's own block)
-              gj = (i32)(s.nfm(s.blk_author(bj), NF_STARTUP) + s.bf(bj, B_TIME));
-              pj = cph_phase(s_edges, gj);
-            }
+          const i32 c = cw_stage(w, ctimes, i, nc, j, k).c;
+          if (c >= 0) {
+            const i32 gj = cw_own_proposal(s, w, j, k, b, gt);
+            const u32 pj = gj == gt ? ph : cph_phase(s_edges, gj);  // (another block, another time: it has its own phase)
             const u32 l = fin_after(c, gj);
             const u32 vb = cph_bin(pj, l, bin_width, bins);
             if (cph_in_pass(vb, base, span)) atomicAdd(&h_lat[vb - base], 1u);
@@ -511,21 +429,12 @@ __global__ __launch_bounds__(LBFT_PH_BLOCK) void lbft_k_ct_phases(Params p, cons
           }
         }
         if (have) {
-          const FinEntry e = fin_entry(col, 64u, n, rights, fin_rights_shift(k, cpe, rot, n), t_valid, t_quorum);
-          const i32 all = fin_all(e, n);
+          const FinEntry e = cw_column(w, k);
           if (e.quorum >= 0) {
             const u32 vb = cph_bin(ph, fin_after(e.quorum, gt), bin_width, bins);
             if (cph_in_pass(vb, base, span)) atomicAdd(&h_fin[vb - base], 1u);
           }
-          if (stat_pass) {
-            if (e.committers) cph_sample_to_lds(s_stat, ph, CPH_FINALITY + FIN_FIRST, fin_after(e.first, gt));
-            if (e.valid >= 0) cph_sample_to_lds(s_stat, ph, CPH_FINALITY + FIN_VALID, fin_after(e.valid, gt));
-            if (e.quorum >= 0) cph_sample_to_lds(s_stat, ph, CPH_FINALITY + FIN_QUORUM, fin_after(e.quorum, gt));
-            if (all >= 0) {
-              cph_sample_to_lds(s_stat, ph, CPH_FINALITY + FIN_ALL, fin_after(all, gt));
-              cph_sample_to_lds(s_stat, ph, CPH_FINALITY + FIN_SPREAD, fin_after(all, e.first));
-            }
-          }
+          if (stat_pass) fin_samples(e, n, gt, [&](u32 family, u32 v) { cph_sample_to_lds(s_stat, ph, CPH_FINALITY + family, v); });
         }
       }
     }

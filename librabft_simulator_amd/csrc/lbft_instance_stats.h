@@ -52,11 +52,7 @@ LBFT_HD uint32_t ist_latency(int32_t c, int32_t g) { return (uint32_t)c - (uint3
 // What the column of entry k gives the finality families (st = the row's IST_FAMILIES accumulators, g = the entry's proposal time);
 // returns 1 if the entry is open.
 LBFT_HD uint32_t ist_column(IstStat* st, const FinEntry& e, uint32_t n, int32_t g) {
-  const int32_t all = fin_all(e, n);
-  if (e.committers) ist_add(st[IST_FINALITY + FIN_FIRST], fin_after(e.first, g));
-  if (e.valid >= 0) ist_add(st[IST_FINALITY + FIN_VALID], fin_after(e.valid, g));
-  if (e.quorum >= 0) ist_add(st[IST_FINALITY + FIN_QUORUM], fin_after(e.quorum, g));
-  if (all >= 0) { ist_add(st[IST_FINALITY + FIN_ALL], fin_after(all, g)); ist_add(st[IST_FINALITY + FIN_SPREAD], fin_after(all, e.first)); }
+  fin_samples(e, n, g, [&](uint32_t family, uint32_t v) { ist_add(st[IST_FINALITY + family], v); });
   return fin_open(e) ? 1u : 0u;
 }
 // What a node's whole row gives the stall families: first (if any), tail, longest -- one sample each.

@@ -13,6 +13,8 @@
 
 using namespace lbft;
 
+#include "lbft_chain_walk.h"  // the node pass
+
 // One segment of W = rh_width(n) lanes per instance, 64 / W instances per wavefront, LBFT_RH_BLOCK / 64 wavefronts per workgroup; no
 // LDS, no atomics.  State is read through the generic Sim accessors (every layout).  The lanes of a segment run the same control flow;
 // every shuffle and ballot is read inside the segment only.
@@ -46,15 +48,10 @@ __global__ __launch_bounds__(LBFT_RH_BLOCK) void lbft_k_rh_chain(Params p, const
   if (s.ld(I_FAULT) != 0) return;
   // node pass
   u32 nc[LBFT_RH_NODE_ROUNDS];
-  u64 best = 0;
 #pragma unroll
-  for (u32 r = 0; r < LBFT_RH_NODE_ROUNDS; r++) {
-    const u32 j = r * 64 + sl;
-    nc[r] = j < n ? chn_commits(s.nfm(j, NF_NCOMMITS), lcap) : 0;
-    if (j < n) best = chn_ref_max(best, chn_ref_key(nc[r], j));
-  }
-  for (u32 d = W >> 1; d; d >>= 1) best = chn_ref_max(best, (u64)__shfl_xor((unsigned long long)best, (int)d, (int)W));
-  const u32 L = chn_ref_len(best), ref = chn_ref_node(best);  // (L <= lcap, ref < n: both from keys built above)
+  for (u32 r = 0; r < LBFT_RH_NODE_ROUNDS; r++) nc[r] = cw_commits(s, r * 64 + sl, n, lcap);
+  const CwChain ch = cw_node_pass<LBFT_RH_NODE_ROUNDS>(nc, sl, n, W);
+  const u32 L = ch.L, ref = ch.ref;  // (L <= lcap, ref < n: both from keys built from the counts)
   const u32 nb = s.ld(I_NBLOCKS) < p.bcap ? s.ld(I_NBLOCKS) : p.bcap;
   const u32 row = lg + ref * lcap;
 

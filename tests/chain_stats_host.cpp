@@ -1,16 +1,9 @@
 // TEST INFRASTRUCTURE: host shim over lbft_chain_rules.h, the arithmetic lbft_k_cs_chain turns an instance's commit logs into samples
-// with.  It takes the state as the device holds it -- logs[instance][node][lcap] of block ids (1-based), commits[instance][node] (not
-// yet clamped), the block pool as blk_author / blk_time[instance][blocks + 1] (index = block id), startup[instance][node] and the fault
-// words -- and walks it the way the kernel does: the reference node by the key order, the chain `chunk` entries side by side, each
-// lane taking its predecessor from the lane below or from what the previous chunk carried, the run starts as a ballot over the chunk,
-// and inside every chunk the other nodes' rows against the chunk's block ids.  Plain loops in place of the wavefront; chunk = 1 is a
-// plain walk.  chunk <= 64: the ballot is one 64-bit word.
-#include <stddef.h>
-#include <stdint.h>
-
-#include <vector>
-
-#include "../librabft_simulator_amd/csrc/lbft_chain_rules.h"
+// with.  The state as the device holds it (without commit times) and the first half of the walk -- the reference node, the chunks, the
+// proposal time -- are tests/chain_walk_host.h's; the shim adds the fault words and what the kernel does with a chunk: each lane takes
+// its predecessor from the lane below or from what the previous chunk carried, the run starts are a ballot over the chunk, and inside
+// every chunk the other nodes' rows are compared against the chunk's block ids.  chunk <= 64: the ballot is one 64-bit word.
+#include "chain_walk_host.h"
 
 extern "C" int chn_host(const uint32_t* logs, const uint32_t* commits, const uint32_t* blk_author, const int32_t* blk_time, const int32_t* startup,
                         const uint32_t* faults, const uint32_t* group_of, uint32_t m, uint32_t n, uint32_t lcap, uint32_t blocks, uint32_t groups,
@@ -24,23 +17,19 @@ extern "C" int chn_host(const uint32_t* logs, const uint32_t* commits, const uin
     const uint32_t g = group_of ? group_of[i] : 0;
     if (g >= groups) return -1;
     GsStat* s = &st[(size_t)g * CHN_FAMILIES];
-    const uint32_t* log = logs + (size_t)i * n * lcap;
-    const uint32_t* author = blk_author + (size_t)i * (blocks + 1);
-    const int32_t* time = blk_time + (size_t)i * (blocks + 1);
-    uint64_t best = 0;
-    for (uint32_t j = 0; j < n; j++) best = chn_ref_max(best, chn_ref_key(chn_commits(commits[(size_t)i * n + j], lcap), j));
-    const uint32_t L = chn_ref_len(best), ref = chn_ref_node(best);
-    for (uint32_t j = 0; j < n; j++) gs_stat_add(s[CHN_LAG], L - chn_commits(commits[(size_t)i * n + j], lcap));
+    const CwInstance v = cw_instance(nullptr, logs, commits, blk_author, blk_time, startup, i, n, lcap, blocks);
+    const uint32_t* log = v.logs;
+    const CwChain ch = cw_node_pass(v);
+    const uint32_t L = ch.L, ref = ch.ref;
+    for (uint32_t j = 0; j < n; j++) gs_stat_add(s[CHN_LAG], L - cw_commits(v, j));
     int32_t carry_g = 0;
     uint32_t carry_a = 0, carry_start = 0, differing = 0, inversions = 0;
     for (uint32_t c0 = 0; c0 < L; c0 += chunk) {
-      const uint32_t have = L - c0 < chunk ? L - c0 : chunk;  // lanes with an entry
+      const uint32_t have = cw_have(ch, c0, chunk);
       for (uint32_t l = 0; l < have; l++) {
         b[l] = log[(size_t)ref * lcap + c0 + l];
-        if (b[l] == 0 || b[l] > blocks) return -2;
-        a[l] = author[b[l]];
-        if (a[l] >= n) return -2;
-        gt[l] = startup[(size_t)i * n + a[l]] + time[b[l]];
+        if (!cw_proposal(v, b[l], gt[l])) return -2;
+        a[l] = v.author[b[l]];
       }
       uint64_t starts = 0;
       for (uint32_t l = 0; l < have; l++) {
@@ -48,9 +37,9 @@ extern "C" int chn_host(const uint32_t* logs, const uint32_t* commits, const uin
         const int32_t pg = l ? gt[l - 1] : carry_g;
         const uint32_t pa = l ? a[l - 1] : carry_a;
         if (k > 0) {
-          const uint32_t v = chn_interval(pg, gt[l]);
-          interval_hist[(size_t)g * bins + gs_bin(v, width, bins)]++;
-          gs_stat_add(s[CHN_INTERVAL], v);
+          const uint32_t d = chn_interval(pg, gt[l]);
+          interval_hist[(size_t)g * bins + gs_bin(d, width, bins)]++;
+          gs_stat_add(s[CHN_INTERVAL], d);
           inversions += chn_inverted(pg, gt[l]) ? 1u : 0u;
         }
         if (chn_run_start(k, a[l], pa)) starts |= 1ull << l;
@@ -64,7 +53,7 @@ extern "C" int chn_host(const uint32_t* logs, const uint32_t* commits, const uin
       carry_a = a[have - 1];
       for (uint32_t j = 0; j < n; j++) {
         if (j == ref) continue;
-        const uint32_t ncj = chn_commits(commits[(size_t)i * n + j], lcap);
+        const uint32_t ncj = cw_commits(v, j);
         for (uint32_t l = 0; l < have; l++)
           differing += (c0 + l < ncj && log[(size_t)j * lcap + c0 + l] != b[l]) ? 1u : 0u;
       }

@@ -1,17 +1,8 @@
 // TEST INFRASTRUCTURE: host shim over lbft_commit_finality.h, the arithmetic lbft_k_ct_finality turns the commit times of an instance's
-// nodes into finality samples with.  It takes the state as the device holds it -- ctimes[instance][node][lcap] (-1 = not recorded),
-// logs[instance][node][lcap] of block ids (1-based), commits[instance][node] (not yet clamped), the block pool as blk_author /
-// blk_time[instance][blocks + 1] (index = block id), startup[instance][node], the fault words, the rights table (NULL = unit rights) with
-// its rotation and commands_per_epoch -- and walks it the way the kernel does: the reference node by the key order, the chain `chunk`
-// entries side by side, the n rows of a chunk staged as an [n][chunk] tile with FIN_NONE where the node is no committer, each lane
-// then taking its column (stride = chunk).  Plain loops in place of the wavefront; chunk = 1 is a plain walk.
-#include <stddef.h>
-#include <stdint.h>
-
-#include <vector>
-
-#include "../librabft_simulator_amd/csrc/lbft_chain_rules.h"
-#include "../librabft_simulator_amd/csrc/lbft_commit_finality.h"
+// nodes into finality samples with.  The state as the device holds it and the walk are tests/chain_walk_host.h's; the shim adds the
+// fault words, the groups, the rights table (NULL = unit rights) with its rotation and commands_per_epoch, and what the kernel does
+// with a column: the families' statistics, the two histograms, the first committers, the count of open entries.
+#include "chain_walk_host.h"
 
 extern "C" int fin_host(const int32_t* ctimes, const uint32_t* logs, const uint32_t* commits, const uint32_t* blk_author, const int32_t* blk_time,
                         const int32_t* startup, const uint32_t* faults, const uint32_t* group_of, const uint32_t* rights, uint32_t rot,
@@ -27,46 +18,24 @@ extern "C" int fin_host(const int32_t* ctimes, const uint32_t* logs, const uint3
     const uint32_t g = group_of ? group_of[i] : 0;
     if (g >= groups) return -1;
     GsStat* s = &st[(size_t)g * FIN_FAMILIES];
-    const uint32_t* author = blk_author + (size_t)i * (blocks + 1);
-    const int32_t* time = blk_time + (size_t)i * (blocks + 1);
-    uint64_t best = 0;
-    for (uint32_t j = 0; j < n; j++) best = chn_ref_max(best, chn_ref_key(chn_commits(commits[(size_t)i * n + j], lcap), j));
-    const uint32_t L = chn_ref_len(best), ref = chn_ref_node(best);
+    const CwInstance v = cw_instance(ctimes, logs, commits, blk_author, blk_time, startup, i, n, lcap, blocks);
+    const CwChain ch = cw_node_pass(v);
     uint32_t open = 0;
-    for (uint32_t c0 = 0; c0 < L; c0 += chunk) {
-      const uint32_t have = L - c0 < chunk ? L - c0 : chunk;  // lanes with an entry
-      for (uint32_t j = 0; j < n; j++) {
-        const uint32_t ncj = chn_commits(commits[(size_t)i * n + j], lcap);
-        for (uint32_t l = 0; l < chunk; l++) {
-          const uint32_t k = c0 + l;
-          const int32_t c = k < ncj ? ctimes[((size_t)i * n + j) * lcap + k] : FIN_NONE;
-          tile[(size_t)j * chunk + l] = fin_committer(k, ncj, c) ? c : FIN_NONE;
-        }
-      }
+    for (uint32_t c0 = 0; c0 < ch.L; c0 += chunk) {
+      const uint32_t have = cw_have(ch, c0, chunk);
+      for (uint32_t j = 0; j < n; j++) cw_stage(v, j, c0, chunk, have, tile.data());
       for (uint32_t l = 0; l < have; l++) {
         const uint32_t k = c0 + l;
-        const uint32_t b = logs[((size_t)i * n + ref) * lcap + k];
-        if (b == 0 || b > blocks) return -2;
-        const uint32_t a = author[b];
-        if (a >= n) return -2;
-        const int32_t gt = startup[(size_t)i * n + a] + time[b];
+        int32_t gt;
+        if (!cw_proposal(v, v.logs[(size_t)ch.ref * lcap + k], gt)) return -2;
         const FinEntry e = fin_entry(&tile[l], chunk, n, rights, fin_rights_shift(k, cpe, rot, n), t_valid, quorum);
-        const int32_t all = fin_all(e, n);
-        if (e.committers) {
-          if (e.first < gt) return -3;  // a commit before the proposal: a finding, not a sample
-          gs_stat_add(s[FIN_FIRST], fin_after(e.first, gt));
-          first_committer[(size_t)g * n + e.first_node]++;
-        }
-        if (e.valid >= 0) gs_stat_add(s[FIN_VALID], fin_after(e.valid, gt));
-        if (e.quorum >= 0) {
-          gs_stat_add(s[FIN_QUORUM], fin_after(e.quorum, gt));
-          finality_hist[(size_t)g * bins + gs_bin(fin_after(e.quorum, gt), width, bins)]++;
-        }
-        if (all >= 0) {
-          gs_stat_add(s[FIN_ALL], fin_after(all, gt));
-          gs_stat_add(s[FIN_SPREAD], fin_after(all, e.first));
-          spread_hist[(size_t)g * bins + gs_bin(fin_after(all, e.first), width, bins)]++;
-        }
+        if (e.committers && e.first < gt) return -3;  // a commit before the proposal: a finding, not a sample
+        fin_samples(e, n, gt, [&](uint32_t family, uint32_t sample) {
+          gs_stat_add(s[family], sample);
+          if (family == FIN_QUORUM) finality_hist[(size_t)g * bins + gs_bin(sample, width, bins)]++;
+          if (family == FIN_SPREAD) spread_hist[(size_t)g * bins + gs_bin(sample, width, bins)]++;
+        });
+        if (e.committers) first_committer[(size_t)g * n + e.first_node]++;
         open += fin_open(e) ? 1u : 0u;
       }
     }

@@ -1,21 +1,13 @@
 // TEST INFRASTRUCTURE: host shim over lbft_commit_phases.h and the rule headers of the two calls it splits (lbft_commit_finality.h,
-// lbft_chain_rules.h), the arithmetic lbft_k_ct_phases turns a finished run into per-phase statistics with.  It takes the state as the
-// device holds it -- ctimes[instance][node][lcap] (-1 = not recorded), logs[instance][node][lcap] of block ids (1-based),
-// commits[instance][node] (not yet clamped), the block pool as blk_author / blk_time[instance][blocks + 1] (index = block id),
-// startup[instance][node], the fault words, the rights table (NULL = unit rights) with its rotation and commands_per_epoch, the edges
-// [group][phases - 1] as the launcher takes them -- and walks it the way the kernel does: per pass of `lds_bins` bins of the virtual
-// histograms, per instance the reference node by the key order, the chain `chunk` entries side by side, row j of a chunk staged into
-// the [n][chunk] tile while its entries give the latency samples (after the proposal time of the node's own block, in that block's
-// phase), each lane then taking its column; every sample is added to the four words of its (phase, family).  Plain loops in place of
-// the wavefront.  The words are kept as the kernel keeps them (samples, sum, max(~sample), max: GsStat's) and turned into the minimum at
-// the end, as the library's caller does.
-#include <stddef.h>
-#include <stdint.h>
+// lbft_chain_rules.h), the arithmetic lbft_k_ct_phases turns a finished run into per-phase statistics with.  The state as the device
+// holds it and the walk are tests/chain_walk_host.h's; the shim adds the fault words, the rights table (NULL = unit rights) with its
+// rotation and commands_per_epoch, the edges [group][phases - 1] as the launcher takes them, and what the kernel does with a sample:
+// per pass of `lds_bins` bins of the virtual histograms, the latency samples while row j of a chunk is staged (in the phase of the
+// block that gives the sample its origin), each lane then its column; every sample is added to the four words of its (phase, family).
+// The words are kept as the kernel keeps them (samples, sum, max(~sample), max: GsStat's) and turned into the minimum at the end, as the
+// library's caller does.
+#include "chain_walk_host.h"
 
-#include <vector>
-
-#include "../librabft_simulator_amd/csrc/lbft_chain_rules.h"
-#include "../librabft_simulator_amd/csrc/lbft_commit_finality.h"
 #include "../librabft_simulator_amd/csrc/lbft_commit_phases.h"
 
 // (the kernel: four LDS atomics, add, add, max, max)
@@ -50,65 +42,43 @@ extern "C" int cph_host(const int32_t* ctimes, const uint32_t* logs, const uint3
       uint64_t* lat = latency_hist + (size_t)g * vbins;
       uint64_t* fin = finality_hist + (size_t)g * vbins;
       uint64_t* w_of = stats + (size_t)g * words;
-      const uint32_t* author = blk_author + (size_t)i * (blocks + 1);
-      const int32_t* time = blk_time + (size_t)i * (blocks + 1);
-      auto proposal = [&](uint32_t b, int32_t& out) {
-        if (b == 0 || b > blocks || author[b] >= n) return false;
-        out = startup[(size_t)i * n + author[b]] + time[b];
-        return true;
-      };
-      uint64_t best = 0;
-      for (uint32_t j = 0; j < n; j++) best = chn_ref_max(best, chn_ref_key(chn_commits(commits[(size_t)i * n + j], lcap), j));
-      const uint32_t L = chn_ref_len(best), ref = chn_ref_node(best);
-      for (uint32_t c0 = 0; c0 < L; c0 += chunk) {
-        const uint32_t have = L - c0 < chunk ? L - c0 : chunk;  // lanes with an entry
+      const CwInstance v = cw_instance(ctimes, logs, commits, blk_author, blk_time, startup, i, n, lcap, blocks);
+      const CwChain ch = cw_node_pass(v);
+      for (uint32_t c0 = 0; c0 < ch.L; c0 += chunk) {
+        const uint32_t have = cw_have(ch, c0, chunk);
         for (uint32_t l = 0; l < have; l++) {
-          b_of[l] = logs[((size_t)i * n + ref) * lcap + c0 + l];
-          if (!proposal(b_of[l], gt[l])) return -2;
+          b_of[l] = v.logs[(size_t)ch.ref * lcap + c0 + l];
+          if (!cw_proposal(v, b_of[l], gt[l])) return -2;
           ph[l] = cph_phase(s_edges, gt[l]);
           if (ph[l] >= phases) return -5;
         }
         for (uint32_t j = 0; j < n; j++) {
-          const uint32_t ncj = chn_commits(commits[(size_t)i * n + j], lcap);
-          const int32_t* ct = ctimes + ((size_t)i * n + j) * lcap;
-          for (uint32_t l = 0; l < chunk; l++) {
-            const uint32_t k = c0 + l;
-            int32_t c = k < ncj ? ct[k] : FIN_NONE;
-            c = fin_committer(k, ncj, c) ? c : FIN_NONE;
-            tile[(size_t)j * chunk + l] = c;
+          if (!cw_stage(v, j, c0, chunk, have, tile.data())) return -4;
+          for (uint32_t l = 0; l < have; l++) {
+            const int32_t c = tile[(size_t)j * chunk + l];
             if (c < 0) continue;
-            if (l >= have) return -4;  // (a committer's entry lies below L)
-            const uint32_t bj = logs[((size_t)i * n + j) * lcap + k];
-            int32_t gj = gt[l];
+            int32_t gj;
+            if (!cw_own_proposal(v, j, c0 + l, b_of[l], gt[l], gj)) return -2;
             uint32_t pj = ph[l];
-            if (bj != b_of[l]) {  // the node's own block
-              if (!proposal(bj, gj)) return -2;
+            if (gj != gt[l]) {  // (another block, another time: it has its own phase)
               pj = cph_phase(s_edges, gj);
               if (pj >= phases) return -5;
             }
             if (c < gj) return -3;  // a commit before the proposal: a finding, not a sample
-            const uint32_t v = fin_after(c, gj), vb = cph_bin(pj, v, bin_width, bins);
+            const uint32_t d = fin_after(c, gj), vb = cph_bin(pj, d, bin_width, bins);
             if (cph_in_pass(vb, base, span)) lat[vb]++;
-            if (stat_pass) sample(w_of, pj, CPH_LATENCY, v);
+            if (stat_pass) sample(w_of, pj, CPH_LATENCY, d);
           }
         }
         for (uint32_t l = 0; l < have; l++) {
           const uint32_t k = c0 + l;
           const FinEntry e = fin_entry(&tile[l], chunk, n, rights, fin_rights_shift(k, cpe, rot, n), t_valid, quorum);
           if (e.committers && e.first < gt[l]) return -3;
-          const int32_t all = fin_all(e, n);
           if (e.quorum >= 0) {
             const uint32_t vb = cph_bin(ph[l], fin_after(e.quorum, gt[l]), bin_width, bins);
             if (cph_in_pass(vb, base, span)) fin[vb]++;
           }
-          if (!stat_pass) continue;
-          if (e.committers) sample(w_of, ph[l], CPH_FINALITY + FIN_FIRST, fin_after(e.first, gt[l]));
-          if (e.valid >= 0) sample(w_of, ph[l], CPH_FINALITY + FIN_VALID, fin_after(e.valid, gt[l]));
-          if (e.quorum >= 0) sample(w_of, ph[l], CPH_FINALITY + FIN_QUORUM, fin_after(e.quorum, gt[l]));
-          if (all >= 0) {
-            sample(w_of, ph[l], CPH_FINALITY + FIN_ALL, fin_after(all, gt[l]));
-            sample(w_of, ph[l], CPH_FINALITY + FIN_SPREAD, fin_after(all, e.first));
-          }
+          if (stat_pass) fin_samples(e, n, gt[l], [&](uint32_t family, uint32_t s) { sample(w_of, ph[l], CPH_FINALITY + family, s); });
         }
       }
     }
@@ -132,19 +102,6 @@ extern "C" uint32_t cph_stats_host() { return CPH_STATS; }
 // A stand-alone caller for a sanitizer build: the cases are read from stdin as plain numbers (tests/test_commit_phases_host.py writes
 // them), the outputs are printed.  Format: m n lcap blocks groups rot cpe total quorum phases width bins lds_bins chunk has_rights, then
 // the arrays in cph_host's order.
-#include <stdio.h>
-
-template <class T>
-static bool read_into(std::vector<T>& v, size_t count) {
-  v.resize(count);
-  for (T& x : v) {
-    long long t;
-    if (scanf("%lld", &t) != 1) return false;
-    x = (T)t;
-  }
-  return true;
-}
-
 int main() {
   unsigned cases = 0;
   if (scanf("%u", &cases) != 1) return 2;
@@ -155,17 +112,13 @@ int main() {
               &chunk, &has_rights) != 15)
       return 2;
     if (!phases || !bins || (unsigned long long)groups * phases * bins > (1u << 20)) return 2;
-    std::vector<int32_t> ctimes, blk_time, startup, edges;
-    std::vector<uint32_t> logs, commits, blk_author, faults, group_of, rights;
-    const size_t cells = (size_t)m * n * lcap, pool = (size_t)m * (blocks + 1);
-    if (!read_into(ctimes, cells) || !read_into(logs, cells) || !read_into(commits, (size_t)m * n) || !read_into(blk_author, pool) ||
-        !read_into(blk_time, pool) || !read_into(startup, (size_t)m * n) || !read_into(faults, m) || !read_into(group_of, m) ||
-        !read_into(rights, has_rights ? n : 0) || !read_into(edges, (size_t)groups * (phases - 1)))
-      return 2;
+    CwArrays a;
+    std::vector<int32_t> edges;
+    if (!cw_read_arrays(a, m, n, lcap, blocks, has_rights) || !cw_read_into(edges, (size_t)groups * (phases - 1))) return 2;
     std::vector<uint64_t> lat((size_t)groups * phases * bins, 0), fin(lat.size(), 0), stats((size_t)groups * phases * CPH_STATS, 0);
-    const int rc = cph_host(ctimes.data(), logs.data(), commits.data(), blk_author.data(), blk_time.data(), startup.data(), faults.data(), group_of.data(),
-                            has_rights ? rights.data() : nullptr, rot, cpe, total, quorum, m, n, lcap, blocks, groups, phases > 1 ? edges.data() : nullptr,
-                            phases, width, bins, lds_bins, chunk, lat.data(), fin.data(), stats.data());
+    const int rc = cph_host(a.ctimes.data(), a.logs.data(), a.commits.data(), a.blk_author.data(), a.blk_time.data(), a.startup.data(), a.faults.data(),
+                            a.group_of.data(), has_rights ? a.rights.data() : nullptr, rot, cpe, total, quorum, m, n, lcap, blocks, groups,
+                            phases > 1 ? edges.data() : nullptr, phases, width, bins, lds_bins, chunk, lat.data(), fin.data(), stats.data());
     printf("%d", rc);
     for (const std::vector<uint64_t>* v : {&lat, &fin, &stats})
       for (uint64_t x : *v) printf(" %llu", (unsigned long long)x);
