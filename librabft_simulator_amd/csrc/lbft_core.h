@@ -227,6 +227,15 @@ void lbft_host_push(long long t, unsigned kind, unsigned node);
 #define LBFT_HOOK_POP(t, k, n, s) do { } while (0)
 #define LBFT_HOOK_PUSH(t, k, n) do { } while (0)
 #endif
+// (tests/queue_exhaustion_host.cpp: which of the calendar queue's exhausted-pool branches a run reached -- 0 / 1: push_event on an empty bucket / on a
+// full tail chunk, 2..4: bulk_append dropping a group that needed 1 / 2 / 3 new chunks, 5: bulk_append with a stack of freed chunks that is not
+// empty but too short; nothing in device builds)
+#if defined(LBFT_HOST_POOL_STATS) && !defined(__HIPCC__)
+extern unsigned long long lbft_host_pool_stats[6];
+#define LBFT_POOL_STAT(k) (lbft_host_pool_stats[k]++)
+#else
+#define LBFT_POOL_STAT(k) do { } while (0)
+#endif
 // (tests/tools/mem_lines.cpp, round 6: every access of the event loop to the instance's rows -- instance-relative byte offset, store or load -- for the
 // per-structure count of 128-byte lines an event touches; nothing in device builds)
 #if defined(LBFT_HOST_MEMHOOK) && !defined(__HIPCC__)
@@ -1298,13 +1307,10 @@ struct SimT {
   LBFT_HD u32 calh(u32 idx) const { return P.off_cal_head + 2u * idx; }       // (chunk + 1) << 6 | position of the next entry to pop
   LBFT_HD u32 calt(u32 idx) const { return P.off_cal_head + 2u * idx + 1u; }  // (chunk + 1) << 6 | position of the last entry written; 0 = empty bucket
   LBFT_HD u32 chw(u32 c, u32 pos) const { return P.off_qmeta + c * LBFT_CAL_CH + pos; }
-  LBFT_HD u32 cal_alloc_chunk() {
-    u32 c;
-    if (cal_free) c = ld(P.off_qlo + --cal_free);
-    else c = cal_bump++;
-    if (LBFT_UNLIKELY(c >= P.cal_chunks)) { fault |= F_QUEUE_OVERFLOW; c = P.cal_chunks - 1u; }  // (in bounds; the instance's results are void from here on)
-    return c;
-  }
+  // The pool has no chunk left: the caller raises F_QUEUE_OVERFLOW and drops the event, as on a full queue, BEFORE it stores anything -- a chunk
+  // that is handed out is never a live one, every chunk is freed once, so cal_free <= cal_chunks and cal_bump <= cal_chunks throughout.
+  LBFT_HD bool cal_pool_empty() const { return cal_free == 0 && cal_bump >= P.cal_chunks; }
+  LBFT_HD u32 cal_alloc_chunk() { return cal_free ? ld(P.off_qlo + --cal_free) : cal_bump++; }  // (only after !cal_pool_empty())
   // opens the first non-empty bucket at or after the cursor, unless that is the one already open (the queue is not empty)
   LBFT_HD void cal_open() {
     if (cur_h != 0 && cal_cursor == sp_idx) return;
@@ -1361,6 +1367,11 @@ struct SimT {
       u32 idx = (u32)time * 4u + (3u - kind);
       u32 tl = ld(calt(idx));
       u32 c, pos;
+      if ((tl == 0 || (tl & 63u) == LBFT_CAL_CE) && LBFT_UNLIKELY(cal_pool_empty())) {  // a new chunk is needed and there is none: nothing is stored
+        if (tl == 0) LBFT_POOL_STAT(0); else LBFT_POOL_STAT(1);
+        fault |= F_QUEUE_OVERFLOW;
+        return false;
+      }
       if (tl == 0) {  // empty bucket
         c = cal_alloc_chunk(); pos = 1;
         st(calh(idx), ((c + 1u) << 6) | 1u);
@@ -3041,7 +3052,8 @@ LBFT_UNROLL
     return j;
   }
   // ---- lanes = messages of ONE kind for the network in lane k, in lane (= creation stamp) order: `live` lanes are appended to the calendar buckets
-  // (t[l], kc) with the event word meta[l].  Returns the ballot of the lanes that were scheduled (a full queue drops the surplus and raises the fault).
+  // (t[l], kc) with the event word meta[l].  Returns the ballot of the lanes that were scheduled (a full queue drops the surplus, an exhausted
+  // chunk pool the groups it cannot serve; both raise the fault).
   LBFT_HD u64 bulk_append(u32 k, u32 l4, i32 clk, u32 kc, PL<u32>& live, const PL<u32>& t, const PL<u32>& meta) {
     const bool is_k = LBFT_IS_LANE(k);
       u64 L = pl_ballot(live);
@@ -3085,9 +3097,27 @@ LBFT_UNROLL
           if (live[l] && rk[l] == 0) { u32 base = tg[l] ? (tg[l] & 63u) : 0u; qn[l] = (base + gs[l] + LBFT_CAL_CE - 1u) / LBFT_CAL_CE - (tg[l] ? 1u : 0u); }
           q0[l] = qn[l] & 1u; q1b[l] = (qn[l] >> 1) & 1u;
         }
-        const u64 Q0 = pl_ballot(q0), Q1 = pl_ballot(q1b);
-        const u32 total_new = popc64(Q0) + 2u * popc64(Q1);
-        const u32 pool = P.cal_chunks;
+        u64 Q0 = pl_ballot(q0), Q1 = pl_ballot(q1b);
+        u32 total_new = popc64(Q0) + 2u * popc64(Q1);
+        const u32 avail = fc + (P.cal_chunks - bump);  // what the pool can give: the stack of freed chunks, then the bump allocator
+        if (LBFT_UNLIKELY(total_new > avail)) {
+          // Pool exhausted: a group whose chunks (by allocation rank) the pool cannot give is not scheduled -- its lanes leave `live` before any entry,
+          // link, head, tail or bitmap word is stored, like the surplus of a full queue.  The groups that stay are the first by rank: their ranks hold.
+          if (fc != 0 && fc < total_new) LBFT_POOL_STAT(5);
+          PL<u32> drop, gdrop;
+          LBFT_FOR_LANES(l) {
+            const u64 lower = (1ULL << l) - 1ULL;
+            drop[l] = (qn[l] != 0 && popc64(Q0 & lower) + 2u * popc64(Q1 & lower) + qn[l] > avail) ? 1u : 0u;
+            if (drop[l]) LBFT_POOL_STAT(1u + qn[l]);
+          }
+          pl_shfl(gdrop, drop, lead);
+          LBFT_FOR_LANES(l) if (live[l] && gdrop[l]) { live[l] = 0; qn[l] = 0; q0[l] = 0; q1b[l] = 0; }
+          if (is_k) fault |= F_QUEUE_OVERFLOW;
+          L = pl_ballot(live);
+          nl = popc64(L);
+          Q0 = pl_ballot(q0); Q1 = pl_ballot(q1b);
+          total_new = popc64(Q0) + 2u * popc64(Q1);
+        }
         PL<u32> id0, id1, id2;
         LBFT_FOR_LANES(l) {
           const u64 lower = (1ULL << l) - 1ULL;
@@ -3097,8 +3127,7 @@ LBFT_UNROLL
           for (u32 j = 0; j < 3; j++)
             if (j < qn[l]) {
               u32 ar = a0 + j;  // allocation rank of this chunk
-              u32 c = ar < fc ? ldc(l4, P.off_qlo + fc - 1u - ar) : bump + (ar - fc);
-              ids[j] = c < pool ? c : pool - 1u;  // (pool exhausted: the leader lane raises the fault below; stay in bounds)
+              ids[j] = ar < fc ? ldc(l4, P.off_qlo + fc - 1u - ar) : bump + (ar - fc);  // (ar < avail: a free chunk of the pool)
             }
           id0[l] = ids[0]; id1[l] = ids[1]; id2[l] = ids[2];
         }
@@ -3148,8 +3177,7 @@ LBFT_UNROLL
           qlen += nl;
           if (qlen > maxq) maxq = qlen;
           cal_free = fc - (total_new < fc ? total_new : fc);
-          cal_bump = bump + (total_new > fc ? total_new - fc : 0u);
-          if (cal_bump > pool) { fault |= F_QUEUE_OVERFLOW; cal_bump = pool; }
+          cal_bump = bump + (total_new > fc ? total_new - fc : 0u);  // (total_new <= avail: at most cal_chunks)
           u32 lo = (u32)clk * 4u + kc;  // every message lies at or after the current time: a lower bound for the cursor
           if (lo < cal_cursor) cal_cursor = lo;
         }
@@ -4425,8 +4453,10 @@ inline u64 compute_layout(Params& p) {
   if (hot_first) snaps_blocks();
   // Calendar queue (round 6): a pool of 32-word chunks (31 event metas + a link word each) in the rows off_qmeta, the stack of freed chunks in the rows
   // off_qlo, no key / link rows.  An entry costs 4.13 bytes; the pool holds qcap entries plus one partly filled tail chunk per bucket that can be
-  // non-empty at a time (events only ever sit in the ~delay-spread many time slots ahead of the clock; a margin of qcap / 32 chunks, at least 256) -- running out raises
-  // F_QUEUE_OVERFLOW like a full queue.
+  // non-empty at a time (events only ever sit in the ~delay-spread many time slots ahead of the clock; a margin of qcap / 32 chunks, at least 256).  A bucket of k
+  // entries pins up to min(k, 2 + (k - 2) / 31) chunks, so many sparse buckets (a delay spread of hundreds of ticks) can use the pool up while
+  // qlen < qcap: push_event / bulk_append then raise F_QUEUE_OVERFLOW and drop the event before they store anything, exactly as on a full queue
+  // ("What queue_capacity bounds on the calendar").
   p.cal_chunks = 0;
   if (p.qcal) {
     u32 spare = p.qcap / 32u;

@@ -29,9 +29,22 @@ static int* g_roundtrip = nullptr;
 // What the last lbft_hostmodel_run_batch ran as (test hook): the KernelClass of the step | cooperative event loop << 8 | heap << 9 | calendar << 10
 static std::atomic<uint32_t> g_last_class{0};
 
+// The calendar's allocator words of every instance after the next lbft_hostmodel_run_batch (test hook, not thread-safe): cal_free, cal_bump and the
+// pool's size cal_chunks, three words per instance
+static uint32_t* g_cal_words = nullptr;
+
+#ifdef LBFT_HOST_FENCE
+// tests/queue_exhaustion_host.cpp: the instance whose rows the accesses reported through LBFT_HOOK_MEM belong to, from here on (threads = 1)
+void lbft_host_fence_instance(const lbft::Params& p, uint32_t i);
+#define LBFT_FENCE_INSTANCE(p, i) lbft_host_fence_instance(p, i)
+#else
+#define LBFT_FENCE_INSTANCE(p, i) do { } while (0)
+#endif
+
 extern "C" {
 
 uint32_t lbft_hostmodel_last_class(void) { return g_last_class.load(); }
+void lbft_hostmodel_capture_calendar(uint32_t* words) { g_cal_words = words; }
 void lbft_hostmodel_capture_node_images(uint8_t* buf, size_t stride, size_t* lens) { g_image_buf = buf; g_image_stride = stride; g_image_lens = lens; }
 void lbft_hostmodel_roundtrip_node_images(int* results) { g_roundtrip = results; }
 
@@ -148,6 +161,7 @@ int lbft_hostmodel_run_batch(const lbft_oracle_config* cfg, const lbft_hostmodel
   dirty_state(p, state, fill);
   auto worker = [&](u32 tid) {
     for (size_t i = tid; i < n_instances; i += threads) {
+      LBFT_FENCE_INSTANCE(p, (u32)i);
       init_instance(p, state.data(), (u32)i, seeds[i]);
       const bool coop = generic ? [&] { Sim s(p, state.data(), (u32)i); return run_one(s, p, fill); }() : run_instance<LIB_HIP>(kernel, p, state.data(), (u32)i, fill);
       g_last_class.store((uint32_t)(generic ? K_GENERIC : run_kernel_info(kernel).cls) | (coop ? 256u : 0u) | (p.qheap ? 512u : 0u) | (p.qcal ? 1024u : 0u));
@@ -228,8 +242,10 @@ int lbft_hostmodel_run_batch(const lbft_oracle_config* cfg, const lbft_hostmodel
   if (counters) memset(counters, 0, sizeof(*counters));
   int rc = 0;
   for (size_t i = 0; i < n_instances; i++) {
+    LBFT_FENCE_INSTANCE(p, (u32)i);
     Sim s(p, state.data(), (u32)i);
     s.load_scalars();
+    if (g_cal_words) { g_cal_words[3 * i] = s.cal_free; g_cal_words[3 * i + 1] = s.cal_bump; g_cal_words[3 * i + 2] = p.cal_chunks; }
     if (faults) faults[i] = s.fault;
     if (s.fault) rc = 1;
     if (maxq_out) maxq_out[i] = s.maxq;
@@ -266,6 +282,7 @@ int lbft_hostmodel_run_batch(const lbft_oracle_config* cfg, const lbft_hostmodel
       if (s.maxq > counters->max_queue) counters->max_queue = s.maxq;
     }
   }
+  g_cal_words = nullptr;
   return rc;
 }
 

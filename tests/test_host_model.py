@@ -109,6 +109,13 @@ def test_cooperative_event_loop_small_capacities_fault_cleanly(oracle):
     assert (b["faults"] & 1).all()   # F_QUEUE_OVERFLOW
     b = oracle.hostmodel_run_batch(cfg, seeds, 200, threads=2, history_cap=8, qcap=16 * 1600, scap=3, bcap=128, lcap=128, ql=0, qheap=1, qcal=1, ring=128)
     assert (b["faults"] & 2).all()   # F_SNAP_OVERFLOW
+    # ... and the calendar's chunk pool, which a wide delay spread uses up long before the queue is full (one chunk per non-empty bucket): the
+    # bulk send drops the groups the pool cannot serve and raises the same bit, nothing else (tests/test_queue_exhaustion_host.py fences it)
+    cfg = oracle.make_config(math_mode=1, num_nodes=40, delay_model=1, uniform_lo=0, uniform_hi=300)
+    seeds = np.arange(1, 4, dtype=np.uint64)
+    b = oracle.hostmodel_run_batch(cfg, seeds, 1000, threads=3, history_cap=8, qcap=12800, scap=640, bcap=512, lcap=512, ql=0, qheap=1, qcal=1, ring=512)
+    assert (b["faults"] == 1).all() and (b["maxq"] < 12800).all()   # F_QUEUE_OVERFLOW alone, below queue_capacity entries
+    assert (b["commit_counts"] <= 512).all()
 
 
 # qcal = 1: calendar event queue (one FIFO per (time, kind) bucket) instead of the binary heap
