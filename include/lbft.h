@@ -393,6 +393,41 @@ int lbft_batch_round_switches_all(const lbft_batch* b, int64_t* out, size_t cap_
 #define LBFT_CHAIN_STATS 24
 int lbft_batch_chain_stats(const lbft_batch* b, uint32_t bin_width, uint32_t bins, uint64_t* interval_hist, uint64_t* author_blocks, uint64_t* stats);
 
+/* Run load: how much work the networks did and how close they came to their capacities, per group and per instance, computed on the
+ * device from the words every finished run leaves behind.  The call needs no commit times and no round trace.  Every instance gives one
+ * u32 sample to each of sixteen families:
+ *   family 0 notifications, 1 requests, 2 responses, 3 timers: the events of each kind (lbft_counters.events[0..3] sums them);
+ *   family 4 messages:   families 0 + 1 + 2 (a u32 add);
+ *   family 5 scheduled:  creation stamps (events_scheduled);   family 6 draws:   RNG draws (rng_draws);
+ *   family 7 folded:     duplicate timers folded (timers_folded);   family 8 updates: update_node calls (node_updates);
+ *   family 9 queue:      high-water mark of the event queue (max_queue is the largest of them);
+ *   family 10 chunks:    high-water mark of the calendar queue's chunk pool -- its bump pointer, which advances only while every chunk
+ *                        handed out is live --, 0 on a batch that does not run the calendar queue;
+ *   family 11 snapshots: high-water mark of the snapshot pool (max_snapshots);   family 12 blocks: blocks created (max_blocks);
+ *   family 13 log:       the largest commit count of the instance's nodes, unclamped (past the log capacity after LBFT_FAULT_LOG_OVERFLOW);
+ *   family 14 commits, 15 rounds: the smallest commit count and the smallest active round of its nodes (what lbft_counters.commits and
+ *                        .rounds sum).
+ * lbft_batch_load_stats, per group (the parameter sets, or one group for a plain batch), over the instances with a zero fault word:
+ *   stats[g * LBFT_LOAD_STATS + 4 * family + {0, 1, 2, 3}] = samples, sum, min, max (min = max = 0 without samples);
+ *   hist[g * bins + min(sample / bin_width, bins - 1)] counts family hist_family of the same instances;
+ *   faults[g * 32 + k] counts EVERY instance of the group whose fault word has bit k: which capacity ran out in which set;
+ *   caps (may be NULL) = what the batch runs with: queue_capacity, the chunks of the calendar's pool (0 without the calendar), and the
+ *   snapshot, block and log capacities -- the denominators of families 9 to 13.
+ * lbft_batch_instance_load: rows[inst * LBFT_LOAD_FAMILIES + family], for every instance, faulted ones included (their fault words come
+ * from lbft_batch_faults): the rows to size a capacity by.
+ * Refused in this order, before any HIP call and with nothing written: NULL b, hist, faults or stats (respectively rows)
+ * (LBFT_ERR_INVALID); before a finished run (LBFT_ERR_STATE; legal wherever lbft_batch_commit_counts is, see lbft_batch_chain_stats);
+ * hist_family >= LBFT_LOAD_FAMILIES, bin_width or bins of 0, groups * bins > 2^31 (LBFT_ERR_INVALID).  The batch may be plain or
+ * parameter-set, timed or not, traced or not, of any kernel class (2 to 128 nodes).  The calls change no state.  Computed on the device
+ * (lbft_k_ps_load, liblbft_paramsets.so beside this library; LBFT_ERR_UNSUPPORTED naming it when it is missing or lacks the launcher);
+ * every accumulation is an integer add or max: bit-reproducible. */
+#define LBFT_LOAD_FAMILIES 16
+#define LBFT_LOAD_STATS 64 /* 16 families x {samples, sum, min, max} */
+#define LBFT_LOAD_CAPS 5
+int lbft_batch_load_stats(const lbft_batch* b, uint32_t hist_family, uint32_t bin_width, uint32_t bins, uint64_t* hist, uint64_t* faults, uint64_t* stats,
+                          uint32_t* caps);
+int lbft_batch_instance_load(const lbft_batch* b, uint32_t* rows);
+
 /* Commit finality: when is an entry final in the network -- committed by the first node, by nodes holding a quorum of the voting rights,
  * by every node -- per group, computed on the device from the recorded commit times, the commit logs, the block pool, the startup times,
  * the voting rights and the fault words.  The per-node statistics (latency histogram, timelines) never look across the nodes of one

@@ -428,6 +428,7 @@ int lbft_batch_create(const lbft_config* cfg, const uint64_t* seeds, size_t n_in
 static lbft_ps_init_fn g_ps_init = nullptr;
 static lbft_ps_run_fn g_ps_run = nullptr;
 static lbft_ps_counters_fn g_ps_counters = nullptr;
+static lbft_ps_load_fn g_ps_load = nullptr;
 static std::string side_lib_path(const char* name) {  // a library beside this one
   Dl_info self;
   std::string path = name;
@@ -460,7 +461,7 @@ static int load_side_lib(const char* lib, const char* what, std::initializer_lis
 }
 static int load_paramsets_lib() {
   return load_side_lib(LBFT_PARAMSETS_LIB, "parameter sets", {{"lbft_ps_launch_init", (void**)&g_ps_init}, {"lbft_ps_launch_run", (void**)&g_ps_run},
-                                                              {"lbft_ps_launch_counters", (void**)&g_ps_counters}});
+                                                              {"lbft_ps_launch_counters", (void**)&g_ps_counters}, {"lbft_ps_launch_load", (void**)&g_ps_load}});
 }
 // lbft_k_ps_counters serves batches of every kind.  A parameter-set batch has the library open since its creation; any other batch tries
 // once per process and, where the library is missing or lacks a launcher, keeps the path it always had (lbft_k_finalize per run): a
@@ -1490,6 +1491,46 @@ int lbft_batch_chain_stats(const lbft_batch* b, uint32_t bin_width, uint32_t bin
   unsigned long long* d_stats = gc.out(stats, groups * LBFT_CHAIN_STATS, true);
   if (gc.e == hipSuccess) gc.e = g_cs_chain(&b->p, b->d_state, gc.d_inst, gc.d_off, (u32)groups, gc.gi.max_group, bin_width, bins, d_hist, d_auth, d_stats, b->stream);
   return gc.finish("chain statistics");
+}
+
+// ---- run load (lbft_batch_load_stats, lbft_batch_instance_load) ----
+// Message counts and capacity high-water marks per group and per instance, from the words every finished run leaves on the device
+// (lbft_k_ps_load, liblbft_paramsets.so: the library behind every finished run).  Refused in this order before any HIP call, with
+// nothing written: a NULL argument, a batch that has not run, a bad hist_family / bin_width / bins.  The calls change no state.
+static int refuse_load(const lbft_batch* b, bool args_ok, uint32_t hist_family, uint32_t bin_width, uint32_t bins) {
+  int rc = refuse_grouped(b, args_ok, 1, 1, false);  // (NULL arguments, then the state)
+  if (rc != LBFT_OK) return rc;
+  if (hist_family >= LBFT_LOAD_FAMILIES) { g_err = "hist_family must be below LBFT_LOAD_FAMILIES"; return LBFT_ERR_INVALID; }
+  rc = refuse_grouped(b, true, bin_width, bins, false);
+  return rc != LBFT_OK ? rc : load_paramsets_lib();
+}
+int lbft_batch_load_stats(const lbft_batch* b, uint32_t hist_family, uint32_t bin_width, uint32_t bins, uint64_t* hist, uint64_t* faults, uint64_t* stats,
+                          uint32_t* caps) {
+  int rc = refuse_load(b, hist && faults && stats, hist_family, bin_width, bins);
+  if (rc != LBFT_OK) return rc;
+  const size_t groups = group_count(b);
+  HIP_TRY(hipSetDevice(b->device));
+  GroupedCall gc(b);
+  unsigned long long *d_hist = gc.out(hist, groups * bins), *d_faults = gc.out(faults, groups * 32), *d_stats = gc.out(stats, groups * LBFT_LOAD_STATS, true);
+  if (gc.e == hipSuccess) gc.e = g_ps_load(&b->p, b->d_state, gc.d_inst, gc.d_off, (u32)groups, gc.gi.max_group, hist_family, bin_width, bins, d_hist, d_faults, d_stats,
+                                           nullptr, b->stream);
+  rc = gc.finish("load statistics");
+  if (rc == LBFT_OK && caps) {
+    const Params& p = b->p;
+    caps[0] = p.qcap; caps[1] = p.qcal ? p.cal_chunks : 0u; caps[2] = p.scap; caps[3] = p.bcap; caps[4] = p.lcap;
+  }
+  return rc;
+}
+int lbft_batch_instance_load(const lbft_batch* b, uint32_t* rows) {
+  int rc = refuse_load(b, rows != nullptr, 0, 1, 1);
+  if (rc != LBFT_OK) return rc;
+  HIP_TRY(hipSetDevice(b->device));
+  GroupedCall gc(b);
+  // (an instance's sixteen u32 words are eight of GroupedCall's 64-bit output words: zeroed, and copied back by finish())
+  u32* d_rows = reinterpret_cast<u32*>(gc.out(reinterpret_cast<uint64_t*>(rows), b->m * (LBFT_LOAD_FAMILIES / 2)));
+  if (gc.e == hipSuccess) gc.e = g_ps_load(&b->p, b->d_state, gc.d_inst, gc.d_off, (u32)group_count(b), gc.gi.max_group, 0, 1, 1, nullptr, nullptr, nullptr, d_rows,
+                                           b->stream);
+  return gc.finish("instance load");
 }
 
 // Every instance's round-switch table in one call: out[(inst * cap_rounds + round) * num_nodes + node], what lbft_batch_round_switches

@@ -21,6 +21,16 @@ typedef hipError_t (*lbft_ps_run_fn)(int cls, const lbft::Params* p, lbft::u32* 
 // The fourteen batch counters of a finished run (lbft_batch_counters.h) added to counters[], which the caller zeroed: for batches of
 // every kind, plain ones included -- those fall back to lbft_k_finalize when this library is missing.
 typedef hipError_t (*lbft_ps_counters_fn)(const lbft::Params* p, const lbft::u32* state, unsigned long long* counters, hipStream_t stream);
+// The run load of a finished run (lbft_load_stats.h; lbft_k_ps_load), for batches of every kind.  grp_inst / grp_off: the group index
+// (NULL: one group of every instance).  stats != NULL: hist[groups * bins], faults[groups * 32] and stats[groups * 64], which the caller
+// zeroed, and rows[m * 16] when that is not NULL; stats == NULL: the rows alone (hist and faults NULL, bins 1).
+// A liblbft_paramsets.so built before this launcher existed lacks it and is refused as a whole (load_side_lib fills every slot or
+// none): parameter-set batches and the run load then report LBFT_ERR_UNSUPPORTED, and plain batches reduce their counters with
+// lbft_k_finalize, as they do when the library is missing.
+typedef hipError_t (*lbft_ps_load_fn)(const lbft::Params* p, const lbft::u32* state, const lbft::u32* grp_inst, const lbft::u32* grp_off,
+                                      lbft::u32 n_groups, lbft::u32 max_group, lbft::u32 hist_family, lbft::u32 bin_width, lbft::u32 bins,
+                                      unsigned long long* hist, unsigned long long* faults, unsigned long long* stats, lbft::u32* rows,
+                                      hipStream_t stream);
 }
 
 #endif  // LBFT_PARAMSETS_H

@@ -7,6 +7,10 @@
 // layout, LDS layout (lbft_launch.h) -- is the batch's, so the host side of liblbft_hip.so sizes and reads back these batches as any other.
 // Built as a library of its own (build.py): the code object of liblbft_hip.so, whose kernels are pinned byte for byte by the codegen
 // manifest, does not change.
+// The library also holds the two kernels behind every finished run of every kind of batch: lbft_k_ps_counters (the batch counters) and
+// lbft_k_ps_load (the run load per group and per instance).  liblbft_hip.so looks up all four launchers or refuses the file: one built
+// before lbft_ps_launch_load existed is refused as a whole, and plain batches then reduce their counters with lbft_k_finalize, as they
+// do when the file is missing.
 #include <hip/hip_runtime.h>
 
 #include "../../include/lbft.h"
@@ -62,7 +66,97 @@ __global__ __launch_bounds__(64 * LBFT_COUNTER_WAVES) void lbft_k_ps_counters(Pa
   else atomicAdd(&counters[k], (unsigned long long)r);
 }
 
+// The run load (lbft_batch_load_stats, lbft_batch_instance_load): sixteen u32 samples per instance -- the rule header's families -- from
+// the words a finished run of any kind leaves on the device, read through the generic accessors (instance-major rows or 64-instance
+// tiles alike).  One 16-lane segment per instance, four instances per wavefront, lane f of a segment = family f:
+//   lanes 0-3 and 5-12 load their family's word; `messages` is a segment add of lanes 0-2; for the three families over the nodes the
+//   segment's lanes stride over the nodes two words each (128 nodes: eight trips) and merge by a 16-lane butterfly;
+//   rows != NULL: lane f stores rows[i * 16 + f] (consecutive instances: 256 contiguous bytes per wavefront);
+//   stats != NULL: lane k (and k + 16) counts fault bit k into the census; of an instance without a fault every lane adds its sample to
+//   its ONE GsStat, lane hist_family bins it.  The workgroup's stride over, the segments are combined (ld_reduce_to_lds).
+// The stride is uniform in the wavefront (its four instances are predicated), so every shuffle has all 64 lanes.
+// grid = (ld_workgroups per group, groups); the LDS histogram goes in passes of LD_LDS_BINS bins (lbft_group_stats.h), the rows, the
+// census and the statistics in the first.
+#include "lbft_load_stats.h"
+__device__ __forceinline__ u32 ld_row_of(u32 w) {  // LoadWord -> the instance's row
+  return w < LDW_STAMP ? I_EV0 + w : w == LDW_STAMP ? (u32)I_STAMP : w == LDW_DRAWS ? (u32)I_DRAWS : w == LDW_NFOLD ? (u32)I_NFOLD : w == LDW_NUPD ? (u32)I_NUPD
+       : w == LDW_MAXQ ? (u32)I_MAXQ : w == LDW_CAL_BUMP ? (u32)I_CAL_BUMP : w == LDW_MAXSNAP ? (u32)I_MAXSNAP : (u32)I_NBLOCKS;
+}
+static_assert(I_EV1 == I_EV0 + 1 && I_EV2 == I_EV0 + 2 && I_EV3 == I_EV0 + 3 && LDW_STAMP == 4, "ld_row_of");
+__global__ __launch_bounds__(LD_BLOCK) void lbft_k_ps_load(Params p, const u32* __restrict__ state, const u32* __restrict__ grp_inst,
+                                                           const u32* __restrict__ grp_off, u32 hist_family, u32 bin_width, u32 bins,
+                                                           unsigned long long* __restrict__ hist, unsigned long long* __restrict__ faults,
+                                                           unsigned long long* __restrict__ stats, u32* __restrict__ rows) {
+  __shared__ u32 h[LD_LDS_BINS];
+  __shared__ unsigned long long s_stat[LD_WORDS];
+  __shared__ u32 s_fault[LD_FAULT_BITS];
+  const u32 per = LD_BLOCK / LD_SEGMENT;  // instances per workgroup and step
+  const u32 g = blockIdx.y;
+  const uint2 grp = gs_group(grp_inst, grp_off, g, p.m);
+  const u32 first = grp.x, cnt = grp.y;
+  if (blockIdx.x * per >= cnt) return;  // (the whole workgroup: its group has fewer instances)
+  const u32 lane = threadIdx.x % 64, f = threadIdx.x % LD_SEGMENT, seg = threadIdx.x / LD_SEGMENT;
+  const u32 n = p.n, word = ld_word_of(f);
+  const bool calendar = p.qcal != 0, grouped = stats != nullptr;
+  if (grouped) {
+    gs_stats_clear<LD_WORDS>(s_stat);
+    if (threadIdx.x < LD_FAULT_BITS) s_fault[threadIdx.x] = 0;
+  }
+  GsStat st = {};
+  for (u32 base = 0; base < bins; base += LD_LDS_BINS) {
+    const u32 span = bins - base < LD_LDS_BINS ? bins - base : LD_LDS_BINS;
+    const bool first_pass = base == 0;
+    if (grouped) gs_lds_clear<LD_BLOCK>(h, span);
+    __syncthreads();
+    for (u32 k0 = blockIdx.x * per; k0 < cnt; k0 += gridDim.x * per) {  // (uniform in the workgroup)
+      const u32 k = k0 + seg;
+      const bool valid = k < cnt;
+      u32 i = 0, fault = 0, v = 0;
+      LdNodes nodes = ld_nodes_empty();
+      if (valid) {
+        i = gs_instance(grp_inst, first, k);
+        Sim s(p, const_cast<u32*>(state), i);
+        fault = s.ld(I_FAULT);
+        if (word != LDW_NONE) v = ld_word_sample(f, s.ld(ld_row_of(word)), calendar);
+        for (u32 q = f; q < n; q += LD_SEGMENT) ld_nodes_add(nodes, s.nfm(q, NF_NCOMMITS), s.nfm(q, NF_PM_ROUND));
+      }
+      nodes = ld_segment_merge(nodes);
+      v = ld_sample(f, v, ld_segment_sum(ld_message_share(f, v)), nodes);
+      if (!valid) continue;
+      if (first_pass && rows) rows[(size_t)i * LD_FAMILIES + f] = v;
+      if (!grouped) continue;
+      if (first_pass) {
+        if (ld_fault_bit(fault, f)) atomicAdd(&s_fault[f], 1u);
+        if (ld_fault_bit(fault, f + LD_SEGMENT)) atomicAdd(&s_fault[f + LD_SEGMENT], 1u);
+      }
+      if (!ld_clean(fault)) continue;
+      if (first_pass) gs_stat_add(st, v);
+      if (f == hist_family) gs_lds_count(h, v, bin_width, bins, base, span);
+    }
+    if (!grouped) return;  // (the rows alone: one pass, nothing in LDS)
+    if (first_pass) ld_reduce_to_lds(st, s_stat, lane);
+    __syncthreads();
+    gs_lds_flush<LD_BLOCK>(h, hist, g, bins, base, span);
+    if (first_pass) {
+      gs_stats_out<LD_WORDS>(s_stat, stats, g);
+      if (threadIdx.x < LD_FAULT_BITS && s_fault[threadIdx.x]) atomicAdd(&faults[(size_t)g * LD_FAULT_BITS + threadIdx.x], (unsigned long long)s_fault[threadIdx.x]);
+    }
+    __syncthreads();  // (before the next pass clears the histogram)
+  }
+}
+
 extern "C" {
+
+// stats == NULL: the rows alone (lbft_batch_instance_load); else the grouped outputs, all three (rows may be NULL).
+__attribute__((visibility("default"))) hipError_t lbft_ps_launch_load(const Params* p, const u32* state, const u32* grp_inst, const u32* grp_off, u32 n_groups,
+                                                                     u32 max_group, u32 hist_family, u32 bin_width, u32 bins, unsigned long long* hist,
+                                                                     unsigned long long* faults, unsigned long long* stats, u32* rows, hipStream_t stream) {
+  if (n_groups == 0 || max_group == 0 || hist_family >= LD_FAMILIES || bin_width == 0 || bins == 0) return hipErrorInvalidValue;
+  if (stats ? !hist || !faults : !rows || hist || faults || bins != 1) return hipErrorInvalidValue;
+  lbft_k_ps_load<<<dim3((u32)ld_workgroups(n_groups, max_group), n_groups), LD_BLOCK, 0, stream>>>(*p, state, grp_inst, grp_off, hist_family, bin_width, bins, hist,
+                                                                                                    faults, stats, rows);
+  return hipGetLastError();
+}
 
 __attribute__((visibility("default"))) hipError_t lbft_ps_launch_counters(const Params* p, const u32* state, unsigned long long* counters, hipStream_t stream) {
   const u32 per_group = 64 * LBFT_COUNTER_WAVES;

@@ -29,6 +29,9 @@ deviation and standard error, and the extremes with the seeds that attain them: 
 and the finality of the entries PROPOSED in each window of the clock -- up to 7 edges in [0, max_clock + 1], not decreasing, or
 ``partition`` for before / during / after each point's own partition; per phase ``from``, ``to``, the six families and the quantiles
 of the latency and of the quorum finality).  ``--phases WARM,END`` sets a warm-up and a cool-down apart.
+``--load`` adds a ``"load"`` object (BatchResult.load_by_param_set: events by kind, messages per commit, the high-water marks of the
+event queue, the calendar's chunk pool and the snapshot pool against their capacities, the fault census and the seeds that came closest
+to a capacity); like ``--chain`` it needs neither commit times nor the trace and leaves the batch on the kernel it would run anyway.
 """
 import argparse
 import itertools
@@ -132,6 +135,7 @@ def main(argv=None):
                     help="record commit times and add each point's latency and finality per proposal-time window")
     ap.add_argument("--rounds", action="store_true", help="record the round-switch trace and add each point's round statistics")
     ap.add_argument("--chain", action="store_true", help="add each point's chain statistics (agreement, chain quality, block cadence)")
+    ap.add_argument("--load", action="store_true", help="add each point's run load (message counts per commit, capacity headroom, worst seeds)")
     ap.add_argument("--round-trace", type=int, default=None, metavar="N", help="with --rounds: rounds per node the trace keeps")
     args = ap.parse_args(argv)
     if args.round_trace is not None and (args.round_trace < 1 or not args.rounds):
@@ -162,6 +166,7 @@ def main(argv=None):
         phases = res.phases_by_param_set(args.phases) if args.phases is not None else None
         round_stats = res.rounds_by_param_set() if args.rounds else None
         chain = res.chain_by_param_set() if args.chain else None
+        load = res.load_by_param_set() if args.load else None
         for k, (pt, row) in enumerate(zip(points, res.by_param_set())):
             line = dict(pt, nodes=args.nodes, max_clock=args.max_clock, seeds=args.seeds_per_point, assign=args.assign)
             line.update(instances=row["instances"], faulted=row["faulted"], commits=row["commits"], rounds=row["rounds"])
@@ -181,6 +186,8 @@ def main(argv=None):
                 line["round_stats"] = round_stats[k]
             if chain is not None:
                 line["chain"] = chain[k]
+            if load is not None:
+                line["load"] = load[k]
             print(json.dumps(line), flush=True)
     finally:
         sim.close()

@@ -410,6 +410,79 @@ class BatchResult:
             out.append(row)
         return out
 
+    def _load_call(self, family, bin_width, bins):
+        groups = self._groups()
+        hist = np.zeros((groups, bins), dtype=np.uint64)
+        faults = np.zeros((groups, 32), dtype=np.uint64)
+        stats = np.zeros((groups, _lib.LOAD_STATS), dtype=np.uint64)
+        caps = np.zeros(len(_lib.LOAD_CAPS), dtype=np.uint32)
+        check(_lib.lib().lbft_batch_load_stats(self._sim._h, family, bin_width, bins, hist.ctypes.data, faults.ctypes.data, stats.ctypes.data,
+                                               caps.ctypes.data))
+        return hist, faults, stats, caps
+
+    def load_stats(self, family="queue", bin_width=None, bins=None):
+        """The run load computed on the device (lbft_batch_load_stats), per group (the parameter sets of a ``with_param_sets`` batch, else
+        one group): ``(hist, faults, stats, caps)``.  Every instance gives one sample to each of the sixteen families of
+        ``LOAD_FAMILIES``: the events by kind (``notifications``, ``requests``, ``responses``, ``timers``), ``messages`` (the first three
+        added), ``scheduled``, ``draws``, ``folded``, ``updates``, the high-water marks ``queue``, ``chunks`` (the calendar queue's pool; 0
+        without it), ``snapshots``, the number of ``blocks``, ``log`` (the largest commit count of its nodes), ``commits`` and ``rounds``
+        (the smallest).  ``stats[group]`` (64 uint64) holds ``(samples, sum, min, max)`` per family over the instances without a fault;
+        ``hist[group, min(sample // bin_width, bins - 1)]`` bins ``family`` (a name or an index) of the same instances;
+        ``faults[group, k]`` counts every instance of the group with fault bit ``k``; ``caps`` (5 uint32) are the capacities the batch
+        runs with, in the order of ``LOAD_CAPS``: the denominators of ``queue``, ``chunks``, ``snapshots``, ``blocks`` and ``log``.  The
+        defaults are exact: width 1, and as many bins as the family's largest sample needs (found by a first call with one bin).  Needs
+        nothing of the run: no commit times, no round trace; serves every kind of batch."""
+        names = _lib.LOAD_FAMILIES
+        f = names.index(family) if family in names else family
+        if isinstance(f, bool) or not isinstance(f, (int, np.integer)) or not 0 <= int(f) < len(names):
+            raise ValueError("family: one of %s, or its index" % ", ".join(names))
+        if (bin_width is not None and int(bin_width) < 1) or (bins is not None and int(bins) < 1):
+            raise ValueError("bin_width and bins must be at least 1")
+        f, bin_width = int(f), 1 if bin_width is None else int(bin_width)
+        if bins is None:
+            bins = int(self._load_call(f, bin_width, 1)[2][:, 4 * f + 3].max()) // bin_width + 1
+        return self._load_call(f, bin_width, int(bins))
+
+    def instance_load(self):
+        """``[instances, 16]`` uint32: the sixteen samples of ``load_stats`` (columns in the order of ``LOAD_FAMILIES``) of every instance,
+        faulted ones included -- with ``faults``, the rows to size a capacity by (lbft_batch_instance_load)."""
+        rows = np.zeros((self._sim.num_instances, len(_lib.LOAD_FAMILIES)), dtype=np.uint32)
+        check(_lib.lib().lbft_batch_instance_load(self._sim._h, rows.ctypes.data))
+        return rows
+
+    def load_by_param_set(self, quantiles=(0.5, 0.9, 0.99)):
+        """Per group of ``load_stats`` (parameter set, or the one group of a plain batch), in set order: ``instances`` and ``clean``
+        (those without a fault); per family ``{mean, min, max}`` over the clean instances (``None`` without any);
+        ``messages_per_commit`` = sum(messages) / sum(commits), and the same for ``notifications``, ``requests`` and ``responses``
+        (``None`` without commits); ``headroom`` = {capacity name: largest high-water mark / capacity} for ``LOAD_CAPS`` over the clean
+        instances (``None`` for a capacity of 0 -- ``chunks`` without the calendar queue -- and for a group without a clean instance); ``queue_quantiles`` ({str(q): slots}, exact, the inverted-CDF rule of
+        ``histogram_quantile``); ``faults`` = {fault name: instances}, over every instance of the group; ``worst_seed`` = for ``queue``
+        and ``chunks`` the seed of the group's instance with the largest value, faulted instances included (``None`` for an empty
+        group): the seed to replay in ``Simulator.new``."""
+        names = _lib.LOAD_FAMILIES
+        hist, faults, stats, caps = self.load_stats("queue")
+        rows = self.instance_load()
+        set_of = getattr(self._sim, "set_of_instance", None) if self._sim.param_sets is not None else None
+        seeds = np.asarray(self._sim.seeds, dtype=np.uint64)
+        out = []
+        for g in range(hist.shape[0]):
+            members = np.arange(len(rows)) if set_of is None else np.flatnonzero(set_of == g)
+            fam = _families(stats[g], tuple((name, "instances") for name in names))
+            row = {"set": g, "instances": int(len(members)), "clean": int(stats[g, 0])}
+            for name in names:
+                row[name] = {k: fam[name][k] for k in ("mean", "min", "max")}
+            commits = int(stats[g, 4 * names.index("commits") + 1])
+            for name in ("messages", "notifications", "requests", "responses"):
+                row[name + "_per_commit"] = int(stats[g, 4 * names.index(name) + 1]) / commits if commits else None
+            row["headroom"] = {name: (int(stats[g, 4 * names.index(name) + 3]) / int(cap) if cap and row["clean"] else None)
+                               for name, cap in zip(_lib.LOAD_CAPS, caps)}
+            row["queue_quantiles"] = {str(q): histogram_quantile(hist[g], 1, q) for q in quantiles}
+            row["faults"] = {_lib.FAULT_NAMES.get(1 << k, "bit_%d" % k): int(c) for k, c in enumerate(faults[g]) if c}
+            row["worst_seed"] = {name: (int(seeds[members[np.argmax(rows[members, names.index(name)])]]) if len(members) else None)
+                                 for name in ("queue", "chunks")}
+            out.append(row)
+        return out
+
     def by_param_set(self):
         """Per parameter set of a ``BatchSimulator.with_param_sets`` batch, in set order: the number of instances, of faulted instances,
         and mean / min / max over its instances of the commits and of the active round (each instance's minimum over its nodes)."""
