@@ -71,8 +71,10 @@ typedef struct lbft_config {
                                      blocks A, B on the same previous QC (two fetches, same NodeTime; B ends up as its current
                                      proposed block, record_store.rs:466-476); (E2) receivers with an even author index get
                                      its notifications with A instead of B as proposed_block; (E3) otherwise it follows the
-                                     protocol.  The reference has no Byzantine behaviour; oracle/lbft_oracle.cpp is the spec. */
-  const uint64_t* voting_rights;  /* NULL: every node has weight 1 (simulated_context.rs:209-216); else num_nodes weights */
+                                     protocol.  1 makes every node an equivocator; a k above every index leaves node 0 alone.
+                                     The reference has no Byzantine behaviour; oracle/lbft_oracle.cpp is the spec. */
+  const uint64_t* voting_rights;  /* NULL: every node has weight 1 (simulated_context.rs:209-216); else num_nodes weights, each in
+                                     [0, 0xffffff] and not all of them 0 (LBFT_ERR_INVALID otherwise, before any HIP call) */
   /* Capacities of the per-instance device structures; 0 = choose from num_nodes / max_clock. */
   uint32_t queue_capacity;    /* pending events with time <= max_clock */
   uint32_t snapshot_capacity; /* notifications in flight */
@@ -82,13 +84,18 @@ typedef struct lbft_config {
    * the specification).  Every message Simulator::schedule_network_event would schedule draws its delay as usual, then
    * (L1) if drop_per_million > 0 one more next_u64() draw d decides: lost iff mulhi64(d, 1000000) < drop_per_million;
    * (L2) if partition_size > 0 and partition_start <= clock < partition_end, messages between a node < partition_size
-   * and a node >= partition_size are lost.  A lost message consumes its creation stamp and is never queued. */
+   * and a node >= partition_size are lost.  A lost message consumes its creation stamp and is never queued.
+   * drop_per_million >= 1000000 loses every message (the draw is still made).  partition_size >= num_nodes, an empty window
+   * (partition_start == partition_end) or a reversed one (partition_start > partition_end) cuts nothing.  The window is compared
+   * with the clock as given: values outside the 32-bit clock range behave as unbounded (a negative start is "from the beginning", an
+   * end above LBFT_MAX_CLOCK is "for ever", a start above it never begins).  No value of these fields is refused. */
   uint32_t drop_per_million;
   uint32_t partition_size;
   int64_t partition_start, partition_end;
   /* Epoch reconfiguration (extension; "We do not simulate changes in the voting rights yet", simulated_context.rs:209-216;
    * the oracle is the specification).  EpochReader::configuration(state) gives author i the voting right
    * voting_rights[(i + e * rights_rotation) % num_nodes] with e = read_epoch_id(state); 0 = the same rights in every epoch.
+   * rights_rotation is taken modulo num_nodes (13 on 5 nodes is 3), and rotating unit rights changes nothing.
    * The record store of epoch e counts votes / timeouts with these weights and elects its leaders over them
    * (node.rs:331-348, configuration.rs:65-75).  Meaningful with commands_per_epoch small enough to change epochs and
    * quirks = 3 (with the reference's quirks a network stalls at its first epoch change). */

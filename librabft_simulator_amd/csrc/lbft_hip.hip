@@ -386,6 +386,12 @@ int lbft_batch_create(const lbft_config* cfg, const uint64_t* seeds, size_t n_in
   int rc = validate(cfg);
   if (rc != LBFT_OK) { g_err = "invalid or unsupported configuration"; return rc; }
   if (!seeds || n_instances == 0 || n_instances > 0x7fffffffu / cfg->num_nodes) { g_err = "bad seeds / n_instances"; return LBFT_ERR_INVALID; }
+  {  // the voting rights are refused like the rest of the configuration: before the first HIP call
+    Params probe;
+    std::vector<u32> probe_weights;
+    rc = fill_params(cfg, n_instances, probe, probe_weights);
+    if (rc != LBFT_OK) { g_err = "bad voting rights"; return rc; }
+  }
   int ndev = 0;
   HIP_TRY(hipGetDeviceCount(&ndev));
   if (device < 0 || device >= ndev) { g_err = "no such HIP device"; return LBFT_ERR_HIP; }

@@ -17,10 +17,8 @@ int ps_hostmodel_run(const lbft_config* base, const lbft_param_set* sets, uint32
                      lbft_commit* histories, size_t history_cap, uint32_t* faults, uint32_t state_fill) {
   const u32 n = base->num_nodes;
   if (n_sets == 0) return -1;
-  lbft_config unit = *base;  // (this model runs unit voting rights, whatever the base says)
-  unit.voting_rights = nullptr; unit.rights_rotation = 0;
-  TwinBatch tb;
-  const int cls = setup_twin_batch(&unit, sets, n_sets, 16 * n < 64 ? 64 : 16 * n, m, max_clock, tb);
+  TwinBatch tb;  // (the base's voting rights and their rotation are the batch's, as on the device)
+  const int cls = setup_twin_batch(base, sets, n_sets, 16 * n < 64 ? 64 : 16 * n, m, max_clock, tb);
   if (cls < 0) return cls;
   const Params& p = tb.p;
   const std::vector<ParamSetDev>& dev = tb.dev;

@@ -47,11 +47,20 @@ REGRESSION_SEEDS = (1, 2, 3)
 
 
 def case_line(kw, max_clock, caps, seeds, history_cap):
+    """One case as the program reads it.  `kw` may also hold voting_rights (one per node) and rights_rotation: they follow the seeds as the
+    line's optional tail; a line without it means unit rights and no rotation, as before."""
+    kw = dict(kw)
+    rights, rotation = kw.pop("voting_rights", None), kw.pop("rights_rotation", 0)
     cfg = dict(CONFIG_DEFAULTS, **kw)
     assert set(cfg) == set(CONFIG_FIELDS) and set(caps) <= set(CAPS_FIELDS), (kw, caps)
     words = [repr(float(cfg[k])) if k in ("mean", "variance") else str(int(cfg[k])) for k in CONFIG_FIELDS]
     words += [str(int(max_clock))] + [str(int(caps.get(k, 0))) for k in CAPS_FIELDS] + [str(int(history_cap)), str(len(seeds))]
-    return " ".join(words + [str(int(s)) for s in seeds])
+    words += [str(int(s)) for s in seeds]
+    if rights is not None or rotation:
+        rights = [1] * cfg["num_nodes"] if rights is None else list(rights)
+        assert len(rights) == cfg["num_nodes"], (kw, rights)
+        words += [str(int(rotation))] + [str(int(w)) for w in rights]
+    return " ".join(words)
 
 
 def compile_program(out, sanitize):

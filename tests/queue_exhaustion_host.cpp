@@ -6,6 +6,7 @@
 // are reported per case.  Cases come from stdin as plain numbers, one line each after the count:
 //   n delay_model mean variance lo hi commands_per_epoch quirks equivocate_every drop_per_million partition_size partition_start partition_end
 //   max_clock qcap scap bcap lcap ql qheap qcal ring ring_topup tw state_fill history_cap m seed[m]
+// and, optionally, after the seeds on the same line:  rights_rotation voting_right[n]  (without them: unit rights, no rotation).
 // Output, per case: "case <rc> <m> <n>", then per instance one line
 //   fault maxq maxsnap cal_free cal_bump cal_chunks violations first_offset first_is_store | counts[n] | rounds[n] | states[n] | per node min(count, cap) x (proposer index time)
 // (without the bars), then "stats" and the six counters: exhaustion on an empty bucket, on a full tail chunk, in bulk_append for a leader that
@@ -17,6 +18,9 @@
 #include <cinttypes>
 #include <cstdio>
 #include <cstdlib>
+#include <iostream>
+#include <sstream>
+#include <string>
 #include <vector>
 
 namespace lbft { unsigned long long lbft_host_pool_stats[6]; }
@@ -51,9 +55,12 @@ void lbft_host_mem(unsigned off, int store) {
 }  // namespace lbft
 
 int main() {
-  int n_cases = 0;
-  if (scanf("%d", &n_cases) != 1) return 2;
+  std::string text;
+  if (!std::getline(std::cin, text)) return 2;
+  const int n_cases = atoi(text.c_str());
   for (int c = 0; c < n_cases; c++) {
+    if (!std::getline(std::cin, text)) return 2;
+    std::istringstream line(text);
     lbft_oracle_config cfg;
     memset(&cfg, 0, sizeof(cfg));
     lbft_hostmodel_caps caps;
@@ -61,14 +68,24 @@ int main() {
     long long max_clock = 0;
     unsigned long long cpe = 0, history_cap = 0, m = 0;
     long long lo, hi, ps, pe;
-    if (scanf("%u %u %lf %lf %lld %lld %llu %u %u %u %u %lld %lld", &cfg.num_nodes, &cfg.delay_model, &cfg.mean, &cfg.variance, &lo, &hi, &cpe, &cfg.quirks,
-              &cfg.equivocate_every, &cfg.drop_per_million, &cfg.partition_size, &ps, &pe) != 13) return 2;
-    if (scanf("%lld %u %u %u %u %u %u %u %u %u %u %u %llu %llu", &max_clock, &caps.qcap, &caps.scap, &caps.bcap, &caps.lcap, &caps.ql, &caps.qheap, &caps.qcal,
-              &caps.ring, &caps.ring_topup, &caps.tw, &caps.state_fill, &history_cap, &m) != 14) return 2;
+    line >> cfg.num_nodes >> cfg.delay_model >> cfg.mean >> cfg.variance >> lo >> hi >> cpe >> cfg.quirks >> cfg.equivocate_every >> cfg.drop_per_million >>
+        cfg.partition_size >> ps >> pe;
+    line >> max_clock >> caps.qcap >> caps.scap >> caps.bcap >> caps.lcap >> caps.ql >> caps.qheap >> caps.qcal >> caps.ring >> caps.ring_topup >> caps.tw >>
+        caps.state_fill >> history_cap >> m;
+    if (!line) return 2;
     cfg.uniform_lo = lo; cfg.uniform_hi = hi; cfg.partition_start = ps; cfg.partition_end = pe; cfg.commands_per_epoch = cpe;
     cfg.target_commit_interval = 100000; cfg.delta = 20; cfg.gamma = 2.0; cfg.lambda = 0.5; cfg.math_mode = 1;  // (oracle_ctypes.make_config's defaults)
     std::vector<uint64_t> seeds(m);
-    for (auto& s : seeds) { unsigned long long v; if (scanf("%llu", &v) != 1) return 2; s = v; }
+    for (auto& s : seeds) { unsigned long long v; if (!(line >> v)) return 2; s = v; }
+    std::vector<uint64_t> rights;
+    unsigned rotation = 0;
+    if (line >> rotation) {  // the optional tail: rights_rotation and one voting right per node
+      rights.resize(cfg.num_nodes);
+      for (auto& w : rights) { unsigned long long v; if (!(line >> v)) return 2; w = v; }
+      cfg.voting_rights = rights.data();
+      cfg.rights_rotation = rotation;
+    }
+    if (!line.eof()) { line >> std::ws; if (!line.eof()) return 2; }
     const size_t n = cfg.num_nodes;
     std::vector<uint32_t> counts(m * n), faults(m), maxq(m), maxsnap(m), cal(3 * m);
     std::vector<uint64_t> rounds(m * n), states(m * n);
