@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+import third_party_reference
 from support import amd  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -391,26 +392,7 @@ def test_device_third_party_arithmetic(amd, oracle):
 
 def siphash13_words(words):
     """SipHash-1-3 (keys 0,0) over little-endian u64 words (numpy-free, small inputs only)."""
-    mask = (1 << 64) - 1
-    v = [0x736f6d6570736575, 0x646f72616e646f6d, 0x6c7967656e657261, 0x7465646279746573]
-
-    def rotl(x, b):
-        return ((x << b) | (x >> (64 - b))) & mask
-
-    def rnd():
-        v[0] = (v[0] + v[1]) & mask; v[1] = rotl(v[1], 13); v[1] ^= v[0]; v[0] = rotl(v[0], 32)
-        v[2] = (v[2] + v[3]) & mask; v[3] = rotl(v[3], 16); v[3] ^= v[2]
-        v[0] = (v[0] + v[3]) & mask; v[3] = rotl(v[3], 21); v[3] ^= v[0]
-        v[2] = (v[2] + v[1]) & mask; v[1] = rotl(v[1], 17); v[1] ^= v[2]; v[2] = rotl(v[2], 32)
-
-    for m in words:
-        m &= mask
-        v[3] ^= m; rnd(); v[0] ^= m
-    b = ((len(words) * 8) << 56) & mask
-    v[3] ^= b; rnd(); v[0] ^= b
-    v[2] ^= 0xff
-    rnd(); rnd(); rnd()
-    return v[0] ^ v[1] ^ v[2] ^ v[3]
+    return third_party_reference.siphash13(third_party_reference.le64(*words))
 
 
 def test_full_size_65536x4_properties(amd, oracle):
