@@ -435,6 +435,48 @@ int lbft_batch_load_stats(const lbft_batch* b, uint32_t hist_family, uint32_t bi
                           uint32_t* caps);
 int lbft_batch_instance_load(const lbft_batch* b, uint32_t* rows);
 
+/* Vote statistics: whose votes certify the chain, who is left out of the quorum certificates (QCs) and how much proposing is in vain, per
+ * group, computed on the device from what every run leaves behind -- the nodes' commit logs, the block pool with every block's round,
+ * epoch, author, ledger depth and the voter set of its QC, the voting rights and the fault words.  The call needs no commit times and no
+ * round trace.  For instance i without a fault (a non-zero fault word skips the instance):
+ *   nc_j, the reference node `ref` and L = nc_ref are those of the chain statistics (lbft_batch_chain_stats above); b_k = log[ref][k];
+ *   the pool is blocks 1 .. nb, nb = min(block count, block capacity);
+ *   a log entry that is no pool index ends the chain at that entry, as in lbft_batch_chain_record_hashes: L becomes its index, and no block
+ *   record is read whose id was not checked;
+ *   V(b) = the voter set of b's QC restricted to authors < num_nodes, empty when b has no QC;
+ *   e(b) = the epoch of b; the voting right of j in epoch e is w_j(e) = voting_rights[(j + e * rights_rotation) % num_nodes] (1 with unit
+ *   rights), quorum = 2 * total / 3 + 1;
+ *   the tip is (e, round) of b_{L-1}; with L == 0 there is no tip.
+ * Groups are those of the latency histogram (the parameter sets, or one group for a plain batch).  Eight sample families, each reported as
+ * stats[g * LBFT_VOTE_STATS + 4 * family + {0, 1, 2, 3}] = samples, sum, min, max (min = max = 0 without samples):
+ *   family 0, votes:     popcount(V(b_k)), one sample per chain entry with a non-empty V; also counted in
+ *                        votes_hist[g * (num_nodes + 1) + votes].  A committed block always has a QC: a sample count below the chain
+ *                        lengths' sum says otherwise
+ *   family 1, weight:    the sum of w_j(e(b_k)) over j in V(b_k), the same entries
+ *   family 2, margin:    weight - quorum (>= 0), the same entries; also binned, margin_hist[g * bins + min(margin / bin_width, bins - 1)]
+ *   family 3, skipped:   round(b_{k+1}) - round(b_k) - 1, one sample per consecutive chain pair of the same epoch
+ *   family 4, blocks:    nb, one sample per instance
+ *   family 5, orphaned:  one sample per instance, the pool blocks that are no chain entries and whose (e, round) is <= the tip's,
+ *                        lexicographically: they can never commit; 0 when L == 0
+ *   family 6, pending:   one sample per instance, the pool blocks that are no chain entries and not orphaned
+ *   family 7, certified_off_chain: one sample per instance, the pool blocks that are no chain entries and have a non-empty V
+ * Per instance blocks = L + orphaned + pending.
+ * node_table[(g * num_nodes + a) * LBFT_VOTE_NODE_COLUMNS + {0, 1, 2}] = the pool blocks authored by a, the orphaned ones among them, the
+ * chain entries whose V contains a: column 0 sums to family 4's sum, column 1 to family 5's, column 2 to family 0's sum (and to family
+ * 1's under unit rights).
+ * Refused in this order, before any HIP call and with nothing written: NULL arguments, bin_width or bins of 0, groups * bins > 2^31
+ * (LBFT_ERR_INVALID); before a finished run (LBFT_ERR_STATE; legal wherever lbft_batch_commit_counts is, see lbft_batch_chain_stats, also
+ * after lbft_batch_manual_finalize).  The batch may be plain or parameter-set, timed or not, traced or not, of any kernel class (2 to 128
+ * nodes).  The call changes no state.  Computed on the device (lbft_k_ps_votes, liblbft_paramsets.so beside this library;
+ * LBFT_ERR_UNSUPPORTED naming it when it is missing or lacks the launcher); every accumulation is an integer add, min or max:
+ * bit-reproducible. */
+#define LBFT_VOTE_FAMILIES 8
+#define LBFT_VOTE_STATS 32       /* 8 families x {samples, sum, min, max} */
+#define LBFT_VOTE_NODE_COLUMNS 3 /* proposed, orphaned, voted */
+int lbft_batch_vote_stats(const lbft_batch* b, uint32_t bin_width, uint32_t bins, uint64_t* margin_hist /* [groups * bins] */,
+                          uint64_t* votes_hist /* [groups * (num_nodes + 1)] */,
+                          uint64_t* node_table /* [groups * num_nodes * LBFT_VOTE_NODE_COLUMNS] */, uint64_t* stats /* [groups * LBFT_VOTE_STATS] */);
+
 /* Commit finality: when is an entry final in the network -- committed by the first node, by nodes holding a quorum of the voting rights,
  * by every node -- per group, computed on the device from the recorded commit times, the commit logs, the block pool, the startup times,
  * the voting rights and the fault words.  The per-node statistics (latency histogram, timelines) never look across the nodes of one

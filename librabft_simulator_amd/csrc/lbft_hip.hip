@@ -435,6 +435,7 @@ static lbft_ps_init_fn g_ps_init = nullptr;
 static lbft_ps_run_fn g_ps_run = nullptr;
 static lbft_ps_counters_fn g_ps_counters = nullptr;
 static lbft_ps_load_fn g_ps_load = nullptr;
+static lbft_ps_votes_fn g_ps_votes = nullptr;
 static std::string side_lib_path(const char* name) {  // a library beside this one
   Dl_info self;
   std::string path = name;
@@ -467,7 +468,8 @@ static int load_side_lib(const char* lib, const char* what, std::initializer_lis
 }
 static int load_paramsets_lib() {
   return load_side_lib(LBFT_PARAMSETS_LIB, "parameter sets", {{"lbft_ps_launch_init", (void**)&g_ps_init}, {"lbft_ps_launch_run", (void**)&g_ps_run},
-                                                              {"lbft_ps_launch_counters", (void**)&g_ps_counters}, {"lbft_ps_launch_load", (void**)&g_ps_load}});
+                                                              {"lbft_ps_launch_counters", (void**)&g_ps_counters}, {"lbft_ps_launch_load", (void**)&g_ps_load},
+                                                              {"lbft_ps_launch_votes", (void**)&g_ps_votes}});
 }
 // lbft_k_ps_counters serves batches of every kind.  A parameter-set batch has the library open since its creation; any other batch tries
 // once per process and, where the library is missing or lacks a launcher, keeps the path it always had (lbft_k_finalize per run): a
@@ -1537,6 +1539,26 @@ int lbft_batch_instance_load(const lbft_batch* b, uint32_t* rows) {
   if (gc.e == hipSuccess) gc.e = g_ps_load(&b->p, b->d_state, gc.d_inst, gc.d_off, (u32)group_count(b), gc.gi.max_group, 0, 1, 1, nullptr, nullptr, nullptr, d_rows,
                                            b->stream);
   return gc.finish("instance load");
+}
+
+// ---- vote statistics (lbft_batch_vote_stats) ----
+// Votes, weight and margin of the chain's quorum certificates, who voted, the rounds the chain skipped and the block pool sorted into
+// chain, orphaned and pending by author, per group (lbft_k_ps_votes, liblbft_paramsets.so: the library behind every finished run).
+// Legality and refusal order are lbft_batch_chain_stats'; arguments are checked before the first HIP call; the call changes no state.
+int lbft_batch_vote_stats(const lbft_batch* b, uint32_t bin_width, uint32_t bins, uint64_t* margin_hist, uint64_t* votes_hist, uint64_t* node_table,
+                          uint64_t* stats) {
+  int rc = refuse_grouped(b, margin_hist && votes_hist && node_table && stats, bin_width, bins, false);
+  if (rc != LBFT_OK) return rc;
+  rc = load_paramsets_lib();
+  if (rc != LBFT_OK) return rc;
+  const size_t groups = group_count(b), n = b->p.n;
+  HIP_TRY(hipSetDevice(b->device));
+  GroupedCall gc(b);
+  unsigned long long *d_margin = gc.out(margin_hist, groups * bins), *d_votes = gc.out(votes_hist, groups * (n + 1));
+  unsigned long long *d_nodes = gc.out(node_table, groups * n * LBFT_VOTE_NODE_COLUMNS), *d_stats = gc.out(stats, groups * LBFT_VOTE_STATS, true);
+  if (gc.e == hipSuccess) gc.e = g_ps_votes(&b->p, b->d_state, gc.d_inst, gc.d_off, (u32)groups, gc.gi.max_group, bin_width, bins, d_margin, d_votes, d_nodes, d_stats,
+                                            b->stream);
+  return gc.finish("vote statistics");
 }
 
 // Every instance's round-switch table in one call: out[(inst * cap_rounds + round) * num_nodes + node], what lbft_batch_round_switches

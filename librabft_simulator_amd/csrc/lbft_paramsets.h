@@ -31,6 +31,13 @@ typedef hipError_t (*lbft_ps_load_fn)(const lbft::Params* p, const lbft::u32* st
                                       lbft::u32 n_groups, lbft::u32 max_group, lbft::u32 hist_family, lbft::u32 bin_width, lbft::u32 bins,
                                       unsigned long long* hist, unsigned long long* faults, unsigned long long* stats, lbft::u32* rows,
                                       hipStream_t stream);
+// The vote statistics of a finished run (lbft_vote_rules.h; lbft_k_ps_votes), for batches of every kind.  grp_inst / grp_off: the group
+// index (NULL: one group of every instance).  margin_hist[groups * bins], votes_hist[groups * (n + 1)], node_table[groups * n * 3] and
+// stats[groups * 32], which the caller zeroed.  A library built before this launcher existed is refused as a whole, as above.
+typedef hipError_t (*lbft_ps_votes_fn)(const lbft::Params* p, const lbft::u32* state, const lbft::u32* grp_inst, const lbft::u32* grp_off,
+                                       lbft::u32 n_groups, lbft::u32 max_group, lbft::u32 bin_width, lbft::u32 bins,
+                                       unsigned long long* margin_hist, unsigned long long* votes_hist, unsigned long long* node_table,
+                                       unsigned long long* stats, hipStream_t stream);
 }
 
 #endif  // LBFT_PARAMSETS_H

@@ -7,10 +7,10 @@
 // layout, LDS layout (lbft_launch.h) -- is the batch's, so the host side of liblbft_hip.so sizes and reads back these batches as any other.
 // Built as a library of its own (build.py): the code object of liblbft_hip.so, whose kernels are pinned byte for byte by the codegen
 // manifest, does not change.
-// The library also holds the two kernels behind every finished run of every kind of batch: lbft_k_ps_counters (the batch counters) and
-// lbft_k_ps_load (the run load per group and per instance).  liblbft_hip.so looks up all four launchers or refuses the file: one built
-// before lbft_ps_launch_load existed is refused as a whole, and plain batches then reduce their counters with lbft_k_finalize, as they
-// do when the file is missing.
+// The library also holds the three kernels behind every finished run of every kind of batch: lbft_k_ps_counters (the batch counters),
+// lbft_k_ps_load (the run load per group and per instance) and lbft_k_ps_votes (the vote statistics per group).  liblbft_hip.so looks
+// up all five launchers or refuses the file: one built before lbft_ps_launch_load or lbft_ps_launch_votes existed is refused as a
+// whole, and plain batches then reduce their counters with lbft_k_finalize, as they do when the file is missing.
 #include <hip/hip_runtime.h>
 
 #include "../../include/lbft.h"
@@ -145,7 +145,172 @@ __global__ __launch_bounds__(LD_BLOCK) void lbft_k_ps_load(Params p, const u32* 
   }
 }
 
+// The vote statistics (lbft_batch_vote_stats): per group, the voter sets of the committed chain -- votes, weight and margin of every
+// quorum certificate, who voted, the rounds the chain skipped -- and the block pool sorted into chain, orphaned and pending, by author.
+// One wavefront per instance, lbft_k_cs_chain's shape: the kernel reads, through the generic Sim accessors (every layout), the fault
+// word, I_NBLOCKS, NF_NCOMMITS of the nodes, the reference node's log row and of the block records B_LINK, B_ROUND, B_EPOCH, B_DEPTH and
+// the mw voter words.
+//   node pass (lane = node, two rounds above 64 nodes): the chain walk's cw_commits / cw_node_pass give L and the reference node.
+//   chain pass (lane = entry, 64 at a time): the id is checked (rh_valid_id) before its record is read; the first id outside the pool
+//     ends the chain there (by ballot).  Popcounts of the voter words; the weight from the rights table in LDS at the epoch's rotation
+//     (unit rights: the popcount); every voter bit counts into the LDS node table.  The predecessor's round and epoch come by
+//     __shfl_up, lane 0 takes what the previous chunk carried.  The tip is broadcast from the last valid entry.
+//   pool pass (lane = block id, 64 at a time over 1 .. nb; first pass only): chain membership is one dependent gather,
+//     log[ref][B_DEPTH - 1] == id (vt_chain_slot / vt_member); proposed and orphaned count into the LDS node table by author, the
+//     per-instance counts are ballots.
+// grid = (workgroups per group, groups); a workgroup's VT_WAVES wavefronts stride over the instances of its group and accumulate by the
+// scheme of lbft_group_stats.h: the margin histogram in passes of VT_LDS_BINS bins; the vote-count histogram, the node table and the
+// statistics in the first pass.  Instances with a non-zero fault word are skipped.
+#include "lbft_chain_walk.h"  // the node pass
+#include "lbft_record_hash_rules.h"  // rh_valid_id, rh_voter_field, rh_author_bits
+#include "lbft_vote_rules.h"
+#define VT_BLOCK 256
+#define VT_WAVES (VT_BLOCK / 64)
+#define VT_LDS_BINS 4096  // the margin histogram: 16 KiB of u32 counts
+#define VT_WORKGROUPS 1024u
+#define VT_NODE_ROUNDS ((LBFT_MAX_NODES + 63) / 64)
+#define VT_MASK_WORDS ((LBFT_MAX_NODES + 31) / 32)
+static_assert(LBFT_VOTE_STATS == VT_FAMILIES * 4 && LBFT_VOTE_FAMILIES == VT_FAMILIES && LBFT_VOTE_NODE_COLUMNS == VT_NODE_COLUMNS, "lbft.h");
+static_assert(LBFT_MAX_NODES <= VT_BLOCK, "the rights table is copied by one lane per node");
+__device__ __forceinline__ u32 vt_ballot_count(bool v) { return (u32)__popcll(__ballot(v)); }
+__global__ __launch_bounds__(VT_BLOCK) void lbft_k_ps_votes(Params p, const u32* __restrict__ state, const u32* __restrict__ grp_inst,
+                                                            const u32* __restrict__ grp_off, u32 bin_width, u32 bins,
+                                                            unsigned long long* __restrict__ margin_hist, unsigned long long* __restrict__ votes_hist,
+                                                            unsigned long long* __restrict__ node_table, unsigned long long* __restrict__ stats) {
+  __shared__ u32 h_margin[VT_LDS_BINS], h_votes[LBFT_MAX_NODES + 1], h_node[LBFT_MAX_NODES * VT_NODE_COLUMNS], s_rights[LBFT_MAX_NODES];
+  __shared__ unsigned long long s_stat[LBFT_VOTE_STATS];
+  const u32 g = blockIdx.y;
+  const uint2 grp = gs_group(grp_inst, grp_off, g, p.m);
+  const u32 first = grp.x, cnt = grp.y;
+  if (blockIdx.x * VT_WAVES >= cnt) return;  // (the whole workgroup: its group has fewer instances)
+  const u32 wave = threadIdx.x / 64, lane = threadIdx.x % 64;
+  const u32 n = p.n, lcap = p.lcap, lg = p.off_log, mw = p.mw, quorum = p.quorum, rot = p.rot;
+  const bool unit = p.unit_weights != 0;
+  gs_stats_clear<LBFT_VOTE_STATS>(s_stat);
+  if (!unit && threadIdx.x < n) s_rights[threadIdx.x] = p.weights[threadIdx.x];  // (read after the pass loop's first barrier)
+  GsStat st[VT_FAMILIES] = {};
+  for (u32 base = 0; base < bins; base += VT_LDS_BINS) {
+    const u32 span = bins - base < VT_LDS_BINS ? bins - base : VT_LDS_BINS;
+    const bool stat_pass = base == 0;
+    gs_lds_clear<VT_BLOCK>(h_margin, span);
+    if (stat_pass) {
+      gs_lds_clear<VT_BLOCK>(h_votes, n + 1);
+      gs_lds_clear<VT_BLOCK>(h_node, n * VT_NODE_COLUMNS);
+    }
+    __syncthreads();
+    for (u32 q = blockIdx.x * VT_WAVES + wave; q < cnt; q += gridDim.x * VT_WAVES) {  // (one instance per wavefront: uniform in it)
+      const u32 i = gs_instance(grp_inst, first, q);
+      Sim s(p, const_cast<u32*>(state), i);
+      if (s.ld(I_FAULT) != 0) continue;
+      // node pass
+      u32 nc[VT_NODE_ROUNDS];
+#pragma unroll
+      for (u32 r = 0; r < VT_NODE_ROUNDS; r++) nc[r] = cw_commits(s, r * 64 + lane, n, lcap);
+      const CwChain ch = cw_node_pass<VT_NODE_ROUNDS>(nc, lane, n, 64u);
+      const u32 ref = ch.ref, row = lg + ref * lcap;  // (ch.L <= lcap, ref < n: both from keys built from the counts)
+      const u32 nb = s.ld(I_NBLOCKS) < p.bcap ? s.ld(I_NBLOCKS) : p.bcap;
+      // chain pass
+      u32 L = ch.L;  // the chain's entries: up to the first id outside the pool
+      u32 carry_r = 0, carry_e = 0, tip_r = 0, tip_e = 0;
+      for (u32 c0 = 0; c0 < L; c0 += 64) {
+        const u32 k = c0 + lane;
+        const bool have = k < L;
+        const u32 y = have ? s.ld(row + k) : 0;  // (k < L <= lcap: inside the row)
+        const unsigned long long bad = __ballot(have && !rh_valid_id(y, nb));
+        const u32 inblk = L - c0 < 64 ? L - c0 : 64;
+        const u32 jb = bad ? (u32)__builtin_ctzll(bad) : 64u;
+        const u32 nv = jb < inblk ? jb : inblk;  // the chunk's entries before the first bad id
+        const bool live = lane < nv;
+        u32 round = 0, epoch = 0, votes = 0, weight = 0;
+        if (live) {
+          round = s.bf(y, B_ROUND); epoch = s.bf(y, B_EPOCH);
+          const u32 shift = vt_rights_shift(epoch, rot, n);
+#pragma unroll
+          for (u32 w = 0; w < VT_MASK_WORDS; w++) {
+            if (w >= mw) continue;
+            const u32 v = s.bf(y, rh_voter_field(w, mw)) & rh_author_bits(w, n);
+            votes += (u32)__popc(v);
+            if (unit && !stat_pass) continue;
+            for (u32 m = v; m; m &= m - 1u) {
+              const u32 a = 32 * w + (u32)ctz32(m);  // (a < n: rh_author_bits)
+              if (!unit) weight += s_rights[vt_right_index(a, shift, n)];
+              if (stat_pass) atomicAdd(&h_node[vt_node_cell(a, VT_COL_VOTED)], 1u);
+            }
+          }
+          if (unit) weight = votes;
+        }
+        u32 pr = (u32)__shfl_up((int)round, 1, 64), pe = (u32)__shfl_up((int)epoch, 1, 64);
+        if (lane == 0) { pr = carry_r; pe = carry_e; }
+        carry_r = (u32)__shfl((int)round, 63, 64);  // (of a chunk that is not full: the last one, nothing reads it)
+        carry_e = (u32)__shfl((int)epoch, 63, 64);
+        if (nv) { tip_r = (u32)__shfl((int)round, (int)nv - 1, 64); tip_e = (u32)__shfl((int)epoch, (int)nv - 1, 64); }
+        if (live && votes) {
+          const u32 margin = vt_margin(weight, quorum);
+          gs_lds_count(h_margin, margin, bin_width, bins, base, span);
+          if (stat_pass) {
+            gs_stat_add(st[VT_VOTES], votes); gs_stat_add(st[VT_WEIGHT], weight); gs_stat_add(st[VT_MARGIN], margin);
+            atomicAdd(&h_votes[votes], 1u);  // (votes <= n: the bits of authors below n)
+          }
+        }
+        if (stat_pass && live && k > 0 && vt_same_epoch(pe, epoch)) gs_stat_add(st[VT_SKIPPED], vt_skipped(pr, round));
+        if (nv < inblk) L = c0 + nv;  // (ends the loop)
+      }
+      if (!stat_pass) continue;
+      // pool pass
+      u32 orphaned = 0, pending = 0, certified_off = 0;
+      for (u32 b0 = 1; b0 <= nb; b0 += 64) {
+        const u32 b = b0 + lane;
+        const bool have = b <= nb;
+        u32 cls = VT_ON_CHAIN, author = 0;
+        bool certified = false;
+        if (have) {
+          author = s.bf(b, B_LINK) >> 16;
+          const u32 round = s.bf(b, B_ROUND), epoch = s.bf(b, B_EPOCH), slot = vt_chain_slot(s.bf(b, B_DEPTH), L);
+#pragma unroll
+          for (u32 w = 0; w < VT_MASK_WORDS; w++)
+            if (w < mw) certified |= (s.bf(b, rh_voter_field(w, mw)) & rh_author_bits(w, n)) != 0;
+          const u32 at = slot < L ? s.ld(row + slot) : 0;  // (slot < L <= lcap: inside the row)
+          cls = vt_classify(vt_member(slot, L, at, b), L != 0, epoch, round, tip_e, tip_r);
+          if (author < n) {
+            atomicAdd(&h_node[vt_node_cell(author, VT_COL_PROPOSED)], 1u);
+            if (cls == VT_ORPHAN) atomicAdd(&h_node[vt_node_cell(author, VT_COL_ORPHANED)], 1u);
+          }
+        }
+        orphaned += vt_ballot_count(have && cls == VT_ORPHAN);
+        pending += vt_ballot_count(have && cls == VT_PENDING_BLOCK);
+        certified_off += vt_ballot_count(have && cls != VT_ON_CHAIN && certified);
+      }
+      if (lane == 0) {  // one sample per instance
+        gs_stat_add(st[VT_BLOCKS], nb); gs_stat_add(st[VT_ORPHANED], orphaned);
+        gs_stat_add(st[VT_PENDING], pending); gs_stat_add(st[VT_CERTIFIED_OFF], certified_off);
+      }
+    }
+    if (stat_pass) gs_reduce_to_lds<VT_FAMILIES>(st, s_stat, lane == 0);
+    __syncthreads();
+    gs_lds_flush<VT_BLOCK>(h_margin, margin_hist, g, bins, base, span);
+    if (stat_pass) {
+      gs_lds_flush<VT_BLOCK>(h_votes, votes_hist, g, n + 1, 0u, n + 1);
+      gs_lds_flush<VT_BLOCK>(h_node, node_table, g, n * VT_NODE_COLUMNS, 0u, n * VT_NODE_COLUMNS);
+      gs_stats_out<LBFT_VOTE_STATS>(s_stat, stats, g);
+    }
+    __syncthreads();  // (before the next pass clears the histogram)
+  }
+}
+
 extern "C" {
+
+// The caller zeroed all four outputs.
+__attribute__((visibility("default"))) hipError_t lbft_ps_launch_votes(const Params* p, const u32* state, const u32* grp_inst, const u32* grp_off, u32 n_groups,
+                                                                      u32 max_group, u32 bin_width, u32 bins, unsigned long long* margin_hist,
+                                                                      unsigned long long* votes_hist, unsigned long long* node_table,
+                                                                      unsigned long long* stats, hipStream_t stream) {
+  if (bin_width == 0 || bins == 0 || n_groups == 0 || max_group == 0 || p->n == 0 || p->n > LBFT_MAX_NODES || !margin_hist || !votes_hist || !node_table || !stats)
+    return hipErrorInvalidValue;
+  // (an instance of the largest group gives at most bcap >= lcap samples to a bin of a histogram or a cell of the node table)
+  const u64 gx = gs_workgroups(VT_WORKGROUPS, n_groups, ((u64)max_group + VT_WAVES - 1) / VT_WAVES, (u64)max_group * p->bcap);
+  lbft_k_ps_votes<<<dim3((u32)gx, n_groups), VT_BLOCK, 0, stream>>>(*p, state, grp_inst, grp_off, bin_width, bins, margin_hist, votes_hist, node_table, stats);
+  return hipGetLastError();
+}
 
 // stats == NULL: the rows alone (lbft_batch_instance_load); else the grouped outputs, all three (rows may be NULL).
 __attribute__((visibility("default"))) hipError_t lbft_ps_launch_load(const Params* p, const u32* state, const u32* grp_inst, const u32* grp_off, u32 n_groups,

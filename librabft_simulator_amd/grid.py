@@ -32,6 +32,9 @@ of the latency and of the quorum finality).  ``--phases WARM,END`` sets a warm-u
 ``--load`` adds a ``"load"`` object (BatchResult.load_by_param_set: events by kind, messages per commit, the high-water marks of the
 event queue, the calendar's chunk pool and the snapshot pool against their capacities, the fault census and the seeds that came closest
 to a capacity); like ``--chain`` it needs neither commit times nor the trace and leaves the batch on the kernel it would run anyway.
+``--votes`` adds a ``"votes"`` object (BatchResult.votes_by_param_set: the votes, weight and margin of the chain's quorum certificates,
+the rounds the chain skipped, the blocks proposed, orphaned and pending, each node's participation, the orphan rate and the round
+utilisation); it too needs neither commit times nor the trace.
 """
 import argparse
 import itertools
@@ -136,6 +139,7 @@ def main(argv=None):
     ap.add_argument("--rounds", action="store_true", help="record the round-switch trace and add each point's round statistics")
     ap.add_argument("--chain", action="store_true", help="add each point's chain statistics (agreement, chain quality, block cadence)")
     ap.add_argument("--load", action="store_true", help="add each point's run load (message counts per commit, capacity headroom, worst seeds)")
+    ap.add_argument("--votes", action="store_true", help="add each point's vote statistics (QC sizes and margins, participation, orphaned blocks)")
     ap.add_argument("--round-trace", type=int, default=None, metavar="N", help="with --rounds: rounds per node the trace keeps")
     args = ap.parse_args(argv)
     if args.round_trace is not None and (args.round_trace < 1 or not args.rounds):
@@ -167,6 +171,7 @@ def main(argv=None):
         round_stats = res.rounds_by_param_set() if args.rounds else None
         chain = res.chain_by_param_set() if args.chain else None
         load = res.load_by_param_set() if args.load else None
+        votes = res.votes_by_param_set() if args.votes else None
         for k, (pt, row) in enumerate(zip(points, res.by_param_set())):
             line = dict(pt, nodes=args.nodes, max_clock=args.max_clock, seeds=args.seeds_per_point, assign=args.assign)
             line.update(instances=row["instances"], faulted=row["faulted"], commits=row["commits"], rounds=row["rounds"])
@@ -188,6 +193,8 @@ def main(argv=None):
                 line["chain"] = chain[k]
             if load is not None:
                 line["load"] = load[k]
+            if votes is not None:
+                line["votes"] = votes[k]
             print(json.dumps(line), flush=True)
     finally:
         sim.close()

@@ -483,6 +483,66 @@ class BatchResult:
             out.append(row)
         return out
 
+    def vote_stats(self, bin_width=None, bins=None):
+        """Vote statistics computed on the device (lbft_batch_vote_stats), per group (the parameter sets of a ``with_param_sets`` batch,
+        else one group): ``(margin_hist, votes_hist, node_table, stats)``.  An instance's chain is that of ``chain_stats``; its pool is
+        every block proposed.  ``stats[group]`` (32 uint64) holds ``(samples, sum, min, max)`` of the eight families of
+        ``VOTE_FAMILIES``: per chain entry with a quorum certificate its ``votes``, their ``weight`` in the voting rights of the block's
+        epoch and the ``margin`` of that weight over the quorum; per consecutive chain pair of one epoch the rounds ``skipped``; per
+        instance the ``blocks`` of the pool, the ``orphaned`` ones (off the chain and not above its tip: they can never commit), the
+        ``pending`` ones (off the chain, above the tip) and the ``certified_off_chain`` ones (off the chain with a certificate).
+        ``margin_hist[group, min(margin // bin_width, bins - 1)]`` bins the margins, ``votes_hist[group, v]`` counts the certificates
+        with ``v`` votes (``num_nodes + 1`` columns), ``node_table[group, node]`` holds, in the order of ``VOTE_NODE_COLUMNS``, the
+        blocks the node ``proposed``, the ``orphaned`` ones among them and the chain's certificates it ``voted`` in.  Instances with a
+        fault are skipped.  The defaults are exact while the margins allow: width 1 and ``min(total - quorum + 1, 4096)`` bins.  Needs
+        nothing of the run: no commit times, no round trace; serves every kind of batch."""
+        if (bin_width is not None and int(bin_width) < 1) or (bins is not None and int(bins) < 1):
+            raise ValueError("bin_width and bins must be at least 1")
+        bin_width = 1 if bin_width is None else int(bin_width)
+        if bins is None:
+            total, quorum = self._voting_totals()
+            bins = min(total - quorum + 1, 4096)
+        bins = int(bins)
+        groups, n = self._groups(), self._sim.num_nodes
+        margin = np.zeros((groups, bins), dtype=np.uint64)
+        votes = np.zeros((groups, n + 1), dtype=np.uint64)
+        nodes = np.zeros((groups, n, len(_lib.VOTE_NODE_COLUMNS)), dtype=np.uint64)
+        stats = np.zeros((groups, _lib.VOTE_STATS), dtype=np.uint64)
+        check(_lib.lib().lbft_batch_vote_stats(self._sim._h, bin_width, bins, margin.ctypes.data, votes.ctypes.data, nodes.ctypes.data, stats.ctypes.data))
+        return margin, votes, nodes, stats
+
+    def _voting_totals(self):
+        """(total, quorum) of the batch's voting rights: quorum = 2 * total // 3 + 1 (every epoch's rotation has the same total)."""
+        cfg, n = self._sim._cfg, self._sim.num_nodes
+        total = sum(int(cfg.voting_rights[k]) for k in range(n)) if cfg.voting_rights else n
+        return total, 2 * total // 3 + 1
+
+    def votes_by_param_set(self, quantiles=(0.5, 0.9, 0.99)):
+        """Per group of ``vote_stats`` (default binning), in set order: the eight families of ``VOTE_FAMILIES`` = samples (``entries``,
+        ``pairs`` or ``instances``), mean, min, max; ``margin["quantiles"]`` ({str(q): weight}, exact, the inverted-CDF rule of
+        ``histogram_quantile``; ``None`` when the histogram clamps: more than 4 096 possible margins); ``votes_hist``, the certificates by
+        number of votes; ``nodes`` = per node ``proposed``, ``orphaned``, ``voted`` and ``participation`` = voted / certificates;
+        ``orphan_rate`` = orphaned / (blocks - pending), the share of the decided blocks that were proposed in vain;
+        ``round_utilisation`` = pairs / (pairs + skipped rounds).  ``None`` where a denominator is 0."""
+        total, quorum = self._voting_totals()
+        exact = total - quorum + 1 <= 4096
+        margin, votes, nodes, stats = self.vote_stats()
+        keys = ("entries", "entries", "entries", "pairs", "instances", "instances", "instances", "instances")
+        out = []
+        for g in range(margin.shape[0]):
+            row = {"set": g, **_families(stats[g], tuple(zip(_lib.VOTE_FAMILIES, keys)))}
+            row["margin"]["quantiles"] = {str(q): histogram_quantile(margin[g], 1, q) for q in quantiles} if exact else None
+            row["votes_hist"] = [int(v) for v in votes[g]]
+            qcs = int(stats[g, 0])
+            row["nodes"] = [{"proposed": int(p), "orphaned": int(o), "voted": int(v), "participation": int(v) / qcs if qcs else None}
+                            for p, o, v in nodes[g]]
+            blocks, orphaned, pending = (int(stats[g, 4 * f + 1]) for f in (4, 5, 6))
+            row["orphan_rate"] = orphaned / (blocks - pending) if blocks - pending else None
+            pairs, skipped = int(stats[g, 4 * 3]), int(stats[g, 4 * 3 + 1])
+            row["round_utilisation"] = pairs / (pairs + skipped) if pairs + skipped else None
+            out.append(row)
+        return out
+
     def by_param_set(self):
         """Per parameter set of a ``BatchSimulator.with_param_sets`` batch, in set order: the number of instances, of faulted instances,
         and mean / min / max over its instances of the commits and of the active round (each instance's minimum over its nodes)."""
