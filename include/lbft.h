@@ -477,6 +477,55 @@ int lbft_batch_vote_stats(const lbft_batch* b, uint32_t bin_width, uint32_t bins
                           uint64_t* votes_hist /* [groups * (num_nodes + 1)] */,
                           uint64_t* node_table /* [groups * num_nodes * LBFT_VOTE_NODE_COLUMNS] */, uint64_t* stats /* [groups * LBFT_VOTE_STATS] */);
 
+/* Epoch statistics: what an epoch change costs and whom it leaves behind, per group and per epoch, computed on the device from what
+ * every run leaves behind -- the nodes' commit logs, epochs and startup times, the block pool with every block's epoch, round, time,
+ * author and ledger depth, and the fault words.  The call needs no commit times and no round trace.  For instance i without a fault (a
+ * non-zero fault word skips the instance):
+ *   nc_j, the reference node `ref`, L and the chain b_k = log[ref][k] are those of lbft_batch_vote_stats above: a log entry that is no pool
+ *   index ends the chain at that entry, no block record is read whose id was not checked, and the pool is blocks 1 .. nb,
+ *   nb = min(block count, block capacity);
+ *   e_k = the epoch of b_k, r_k = its round, g_k = startup[author of b_k] + time of b_k, its global proposal time;
+ *   a segment is a maximal run of consecutive chain entries with equal e_k; the last segment of a chain is open, every other one is
+ *   complete; a boundary is a pair (k - 1, k) with e_{k-1} != e_k.  In a run e_k = k / commands_per_epoch and the epochs rise by one; the
+ *   definitions do not depend on that: on state edited by hand the epochs may decrease or be huge, and the call stays defined;
+ *   E_j = the epoch node j is in (what lbft_batch_epochs returns), E_max = max_j E_j;
+ *   the tip epoch is e_{L-1}; with L == 0 there is no tip.
+ * Groups are those of the latency histogram (the parameter sets, or one group for a plain batch).  Ten sample families, each reported as
+ * stats[g * LBFT_EPOCH_STATS + 4 * family + {0, 1, 2, 3}] = samples, sum, min, max (min = max = 0 without samples):
+ *   family 0, segments:    one sample per instance, the number of segments (0 when L == 0)
+ *   family 1, node_epoch:  E_j, one sample per node
+ *   family 2, behind:      E_max - E_j, one sample per node
+ *   family 3, length:      the entries of a complete segment, one sample per complete segment
+ *   family 4, duration:    max(g_last - g_first, 0) over the entries of a complete segment, the same segments
+ *   family 5, last_round:  r of the last entry of a complete segment, the same segments (rounds restart in every epoch: the rounds the
+ *                          epoch needed to fill)
+ *   family 6, first_round: r of the first entry of a segment, open ones too (the rounds an epoch spends before its first chain block)
+ *   family 7, handover:    max(g_k - g_{k-1}, 0), one sample per boundary; also binned,
+ *                          handover_hist[g * bins + min(handover / bin_width, bins - 1)]
+ *   family 8, stranded:    one sample per instance, the pool blocks that are no chain entries and whose epoch is below the tip epoch: the
+ *                          chain has left their epoch; 0 when L == 0
+ *   family 9, blocks:      nb, one sample per instance
+ * epoch_table[(g * epoch_bins + x) * LBFT_EPOCH_COLUMNS + c], x = min(epoch, epoch_bins - 1) (the last row also takes every epoch above it):
+ *   column 0, segments: the segments of that epoch;   column 1, complete: the complete ones;   column 2, entries: its chain entries;
+ *   column 3, duration: the sum of family 4's samples of that epoch;
+ *   column 4, handover: the sum of family 7's samples whose LATER entry has that epoch;
+ *   column 5, stranded: the stranded blocks of that epoch;   column 6, blocks: the pool blocks of that epoch.
+ * Summed over x, column 0 = family 6's samples = family 0's sum, column 1 = family 3's samples, column 2 = family 3's sum + the open
+ * segments' entries = the clean instances' chain lengths, column 3 = family 4's sum, column 4 = family 7's sum, column 5 = family 8's
+ * sum, column 6 = family 9's sum; family 7's samples = family 6's samples - the instances with L > 0.
+ * Refused in this order, before any HIP call and with nothing written: NULL arguments, bin_width, bins or epoch_bins of 0,
+ * epoch_bins > LBFT_EPOCH_MAX_BINS, groups * bins > 2^31 (LBFT_ERR_INVALID); before a finished run (LBFT_ERR_STATE; legal wherever
+ * lbft_batch_commit_counts is, see lbft_batch_chain_stats, also after lbft_batch_manual_finalize).  The batch may be plain or
+ * parameter-set, timed or not, traced or not, of any kernel class (2 to 128 nodes).  The call changes no state.  Computed on the device
+ * (lbft_k_ps_epochs, liblbft_paramsets.so beside this library; LBFT_ERR_UNSUPPORTED naming it when it is missing or lacks the launcher);
+ * every accumulation is an integer add, min or max, and every sum of times a 64-bit one: bit-reproducible. */
+#define LBFT_EPOCH_FAMILIES 10
+#define LBFT_EPOCH_STATS 40     /* 10 families x {samples, sum, min, max} */
+#define LBFT_EPOCH_COLUMNS 7    /* segments, complete, entries, duration, handover, stranded, blocks */
+#define LBFT_EPOCH_MAX_BINS 512 /* the most rows of the epoch table */
+int lbft_batch_epoch_stats(const lbft_batch* b, uint32_t bin_width, uint32_t bins, uint32_t epoch_bins, uint64_t* handover_hist /* [groups * bins] */,
+                           uint64_t* epoch_table /* [groups * epoch_bins * LBFT_EPOCH_COLUMNS] */, uint64_t* stats /* [groups * LBFT_EPOCH_STATS] */);
+
 /* Commit finality: when is an entry final in the network -- committed by the first node, by nodes holding a quorum of the voting rights,
  * by every node -- per group, computed on the device from the recorded commit times, the commit logs, the block pool, the startup times,
  * the voting rights and the fault words.  The per-node statistics (latency histogram, timelines) never look across the nodes of one

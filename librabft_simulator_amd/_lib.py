@@ -87,6 +87,12 @@ LOAD_CAPS = ("queue", "chunks", "snapshots", "blocks", "log")  # LBFT_LOAD_CAPS:
 VOTE_STATS = 32  # LBFT_VOTE_STATS: (samples, sum, min, max) of the eight families below, per group
 VOTE_FAMILIES = ("votes", "weight", "margin", "skipped", "blocks", "orphaned", "pending", "certified_off_chain")  # LBFT_VOTE_FAMILIES
 VOTE_NODE_COLUMNS = ("proposed", "orphaned", "voted")  # LBFT_VOTE_NODE_COLUMNS: a node's row of lbft_batch_vote_stats' node_table
+EPOCH_STATS = 40  # LBFT_EPOCH_STATS: (samples, sum, min, max) of the ten families below, per group
+EPOCH_FAMILIES = ("segments", "node_epoch", "behind", "length", "duration", "last_round", "first_round", "handover", "stranded",
+                  "blocks")  # LBFT_EPOCH_FAMILIES
+# LBFT_EPOCH_COLUMNS: an epoch's row of lbft_batch_epoch_stats' epoch_table
+EPOCH_COLUMNS = ("segments", "complete", "entries", "duration", "handover", "stranded", "blocks")
+EPOCH_MAX_BINS = 512  # LBFT_EPOCH_MAX_BINS
 MAX_PHASES = 8  # LBFT_MAX_PHASES: at most 7 edges per group
 PHASE_STATS = 24  # LBFT_PHASE_STATS: (samples, sum, min, max) of the six families below, per (group, phase)
 PHASE_FAMILIES = ("latency", "first", "valid", "quorum", "all", "spread")  # LBFT_PHASE_FAMILIES: the latency, the finality's first five
@@ -166,7 +172,7 @@ ABI_SYMBOLS = [
     "lbft_batch_device_bytes", "lbft_batch_set_max_steps", "lbft_batch_set_lanes_per_wavefront",
     "lbft_batch_set_lds_queue_slots", "lbft_batch_set_calendar_queue", "lbft_batch_phase_cycles", "lbft_batch_layout",
     "lbft_batch_run_steps", "lbft_batch_checkpoint_bytes", "lbft_batch_checkpoint_save", "lbft_batch_checkpoint_load",
-    "lbft_batch_enable_round_trace", "lbft_batch_keep_retired_stores", "lbft_batch_counters_allreduce", "lbft_batch_counters_allgather_reduce", "lbft_node_calls", "lbft_batch_round_switches", "lbft_batch_round_switches_all", "lbft_batch_round_stats", "lbft_batch_chain_stats", "lbft_batch_load_stats", "lbft_batch_instance_load", "lbft_batch_vote_stats", "lbft_batch_chain_record_hashes", "lbft_batch_manual_begin", "lbft_batch_manual_finalize", "lbft_node_update", "lbft_node_create_notification",
+    "lbft_batch_enable_round_trace", "lbft_batch_keep_retired_stores", "lbft_batch_counters_allreduce", "lbft_batch_counters_allgather_reduce", "lbft_node_calls", "lbft_batch_round_switches", "lbft_batch_round_switches_all", "lbft_batch_round_stats", "lbft_batch_chain_stats", "lbft_batch_load_stats", "lbft_batch_instance_load", "lbft_batch_vote_stats", "lbft_batch_epoch_stats", "lbft_batch_chain_record_hashes", "lbft_batch_manual_begin", "lbft_batch_manual_finalize", "lbft_node_update", "lbft_node_create_notification",
     "lbft_node_handle_notification", "lbft_node_release_notification", "lbft_node_create_request", "lbft_node_handle_request",
     "lbft_node_handle_response", "lbft_node_view_get", "lbft_device_leaders", "lbft_device_sample_delays",
     "lbft_device_exp_log", "lbft_last_error", "lbft_build_info",
@@ -353,6 +359,8 @@ def lib():
     L.lbft_batch_instance_load.restype = C.c_int
     L.lbft_batch_vote_stats.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
     L.lbft_batch_vote_stats.restype = C.c_int
+    L.lbft_batch_epoch_stats.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp]
+    L.lbft_batch_epoch_stats.restype = C.c_int
     L.lbft_batch_chain_record_hashes.argtypes = [vp, vp, C.c_size_t, vp, vp]
     L.lbft_batch_chain_record_hashes.restype = C.c_int
     L.lbft_batch_manual_begin.argtypes = [vp, C.c_int64]

@@ -22,9 +22,9 @@ TABLE = (
     _lib("hip", None, (), "the C ABI of include/lbft.h and its kernels; opens the others beside itself on first use, so that its own "
                           "code object stays as it is"),
     _lib("paramsets", "lbft_k_ps_", ("lbft_ps_launch_init", "lbft_ps_launch_run", "lbft_ps_launch_counters", "lbft_ps_launch_load",
-                                     "lbft_ps_launch_votes"),
-         "the kernels of parameter-set batches (lbft_batch_create_param_sets) and the counters, run-load and vote-statistics kernels behind "
-         "every finished run"),
+                                     "lbft_ps_launch_votes", "lbft_ps_launch_epochs"),
+         "the kernels of parameter-set batches (lbft_batch_create_param_sets) and the counters, run-load, vote-statistics and "
+         "epoch-statistics kernels behind every finished run"),
     _lib("commit_times", "lbft_k_ct_", ("lbft_ct_launch_run", "lbft_ct_launch_histogram", "lbft_ct_launch_timeline", "lbft_ct_launch_finality",
                                         "lbft_ct_launch_instances", "lbft_ct_launch_phases"),
          "the kernels of batches that record commit times (lbft_batch_record_commit_times)"),

@@ -436,6 +436,7 @@ static lbft_ps_run_fn g_ps_run = nullptr;
 static lbft_ps_counters_fn g_ps_counters = nullptr;
 static lbft_ps_load_fn g_ps_load = nullptr;
 static lbft_ps_votes_fn g_ps_votes = nullptr;
+static lbft_ps_epochs_fn g_ps_epochs = nullptr;
 static std::string side_lib_path(const char* name) {  // a library beside this one
   Dl_info self;
   std::string path = name;
@@ -469,7 +470,7 @@ static int load_side_lib(const char* lib, const char* what, std::initializer_lis
 static int load_paramsets_lib() {
   return load_side_lib(LBFT_PARAMSETS_LIB, "parameter sets", {{"lbft_ps_launch_init", (void**)&g_ps_init}, {"lbft_ps_launch_run", (void**)&g_ps_run},
                                                               {"lbft_ps_launch_counters", (void**)&g_ps_counters}, {"lbft_ps_launch_load", (void**)&g_ps_load},
-                                                              {"lbft_ps_launch_votes", (void**)&g_ps_votes}});
+                                                              {"lbft_ps_launch_votes", (void**)&g_ps_votes}, {"lbft_ps_launch_epochs", (void**)&g_ps_epochs}});
 }
 // lbft_k_ps_counters serves batches of every kind.  A parameter-set batch has the library open since its creation; any other batch tries
 // once per process and, where the library is missing or lacks a launcher, keeps the path it always had (lbft_k_finalize per run): a
@@ -1559,6 +1560,30 @@ int lbft_batch_vote_stats(const lbft_batch* b, uint32_t bin_width, uint32_t bins
   if (gc.e == hipSuccess) gc.e = g_ps_votes(&b->p, b->d_state, gc.d_inst, gc.d_off, (u32)groups, gc.gi.max_group, bin_width, bins, d_margin, d_votes, d_nodes, d_stats,
                                             b->stream);
   return gc.finish("vote statistics");
+}
+
+// ---- epoch statistics (lbft_batch_epoch_stats) ----
+// The committed chain cut into segments of one epoch, the handover between them, the epochs the nodes ended in and the pool blocks
+// stranded in an epoch the chain has left, per group and per epoch (lbft_k_ps_epochs, liblbft_paramsets.so: the library behind every
+// finished run).  Legality and refusal order are lbft_batch_vote_stats', with epoch_bins beside the binning; arguments are checked
+// before the first HIP call; the call changes no state.  (The static_assert that ties lbft.h's macros to lbft_epoch_rules.h stands beside
+// the kernel: the rule header belongs to that library's sources alone.)
+int lbft_batch_epoch_stats(const lbft_batch* b, uint32_t bin_width, uint32_t bins, uint32_t epoch_bins, uint64_t* handover_hist, uint64_t* epoch_table,
+                           uint64_t* stats) {
+  const bool args_ok = handover_hist && epoch_table && stats && epoch_bins != 0;  // (epoch_bins of 0: refused with the binning's zeros)
+  if (b && args_ok && bin_width && bins && epoch_bins > LBFT_EPOCH_MAX_BINS) { g_err = "epoch_bins exceeds LBFT_EPOCH_MAX_BINS"; return LBFT_ERR_INVALID; }
+  int rc = refuse_grouped(b, args_ok, bin_width, bins, false);
+  if (rc != LBFT_OK) return rc;
+  rc = load_paramsets_lib();
+  if (rc != LBFT_OK) return rc;
+  const size_t groups = group_count(b);
+  HIP_TRY(hipSetDevice(b->device));
+  GroupedCall gc(b);
+  unsigned long long *d_hist = gc.out(handover_hist, groups * bins), *d_table = gc.out(epoch_table, groups * epoch_bins * LBFT_EPOCH_COLUMNS);
+  unsigned long long* d_stats = gc.out(stats, groups * LBFT_EPOCH_STATS, true);
+  if (gc.e == hipSuccess) gc.e = g_ps_epochs(&b->p, b->d_state, gc.d_inst, gc.d_off, (u32)groups, gc.gi.max_group, bin_width, bins, epoch_bins, d_hist, d_table, d_stats,
+                                             b->stream);
+  return gc.finish("epoch statistics");
 }
 
 // Every instance's round-switch table in one call: out[(inst * cap_rounds + round) * num_nodes + node], what lbft_batch_round_switches

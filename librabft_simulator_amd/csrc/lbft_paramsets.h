@@ -38,6 +38,13 @@ typedef hipError_t (*lbft_ps_votes_fn)(const lbft::Params* p, const lbft::u32* s
                                        lbft::u32 n_groups, lbft::u32 max_group, lbft::u32 bin_width, lbft::u32 bins,
                                        unsigned long long* margin_hist, unsigned long long* votes_hist, unsigned long long* node_table,
                                        unsigned long long* stats, hipStream_t stream);
+// The epoch statistics of a finished run (lbft_epoch_rules.h; lbft_k_ps_epochs), for batches of every kind.  grp_inst / grp_off: the group
+// index (NULL: one group of every instance).  handover_hist[groups * bins], epoch_table[groups * epoch_bins * 7] and stats[groups * 40],
+// which the caller zeroed; 1 <= epoch_bins <= 512.  A library built before this launcher existed is refused as a whole, as above.
+typedef hipError_t (*lbft_ps_epochs_fn)(const lbft::Params* p, const lbft::u32* state, const lbft::u32* grp_inst, const lbft::u32* grp_off,
+                                        lbft::u32 n_groups, lbft::u32 max_group, lbft::u32 bin_width, lbft::u32 bins, lbft::u32 epoch_bins,
+                                        unsigned long long* handover_hist, unsigned long long* epoch_table, unsigned long long* stats,
+                                        hipStream_t stream);
 }
 
 #endif  // LBFT_PARAMSETS_H

@@ -7,10 +7,11 @@
 // layout, LDS layout (lbft_launch.h) -- is the batch's, so the host side of liblbft_hip.so sizes and reads back these batches as any other.
 // Built as a library of its own (build.py): the code object of liblbft_hip.so, whose kernels are pinned byte for byte by the codegen
 // manifest, does not change.
-// The library also holds the three kernels behind every finished run of every kind of batch: lbft_k_ps_counters (the batch counters),
-// lbft_k_ps_load (the run load per group and per instance) and lbft_k_ps_votes (the vote statistics per group).  liblbft_hip.so looks
-// up all five launchers or refuses the file: one built before lbft_ps_launch_load or lbft_ps_launch_votes existed is refused as a
-// whole, and plain batches then reduce their counters with lbft_k_finalize, as they do when the file is missing.
+// The library also holds the four kernels behind every finished run of every kind of batch: lbft_k_ps_counters (the batch counters),
+// lbft_k_ps_load (the run load per group and per instance), lbft_k_ps_votes (the vote statistics per group) and lbft_k_ps_epochs (the
+// epoch statistics per group).  liblbft_hip.so looks up all six launchers or refuses the file: one built before lbft_ps_launch_load,
+// lbft_ps_launch_votes or lbft_ps_launch_epochs existed is refused as a whole, and plain batches then reduce their counters with
+// lbft_k_finalize, as they do when the file is missing.
 #include <hip/hip_runtime.h>
 
 #include "../../include/lbft.h"
@@ -297,7 +298,208 @@ __global__ __launch_bounds__(VT_BLOCK) void lbft_k_ps_votes(Params p, const u32*
   }
 }
 
+// The epoch statistics (lbft_batch_epoch_stats): per group, the committed chain cut into segments of one epoch -- their length, duration
+// and rounds, the handover between two of them --, the epochs the nodes ended in and the pool blocks stranded in an epoch the chain has
+// left; the same per epoch in the epoch table.  lbft_k_ps_votes' shape: one wavefront per instance, the generic Sim accessors (every
+// layout).  The kernel reads the fault word, I_NBLOCKS, NF_NCOMMITS, NF_EPOCH and NF_STARTUP of the nodes, the reference node's log row and
+// of the block records B_LINK, B_ROUND, B_EPOCH, B_TIME and B_DEPTH.
+//   node pass (lane = node, two rounds above 64 nodes): cw_commits / cw_node_pass give L and the reference node; the same lanes read
+//     NF_EPOCH, and wavefront max, min and sum of it give families node_epoch and behind whole.
+//   chain pass (lane = entry, 64 at a time): the id is checked (rh_valid_id) before its record is read; the first id outside the pool
+//     ends the chain there (by ballot).  e, r and g of the predecessor come by __shfl_up, lane 0 takes what the previous chunk carried.
+//     The segment starts of a chunk are a ballot; a start at k > 0 is a boundary and closes the segment before it, whose first entry is
+//     the highest start below the lane or the carried one (ep_segment_first; its g by one more shuffle): length, duration, last_round
+//     and the row of the EARLIER epoch (complete, duration), handover and the row of the LATER one.  Every start gives first_round and
+//     counts a segment, every entry counts into its epoch's row: the open segment at the chain's end has thereby given all it gives.
+//   pool pass (lane = block id, 64 at a time over 1 .. nb; first pass only): a block counts into its epoch's row; membership is
+//     vt_member's one gather; stranded (ep_stranded) by ballot for the instance and per block for the row.
+// LDS: the handover histogram in passes of EP_LDS_BINS bins (16 KiB); the table's five counting columns as u32 cells for all 512 rows
+// (10 KiB) and its two time columns as 64-bit cells for the first EP_LDS_SUM_ROWS rows (4 KiB) -- a sum of times is never held in less
+// than 64 bits; rows above that, which only a chain of more than 256 epochs reaches, add to the global table directly --; the
+// statistics.  Table and statistics are taken in the first pass.  Instances with a non-zero fault word are skipped.
+#include "lbft_epoch_rules.h"
+#define EP_BLOCK 256
+#define EP_WAVES (EP_BLOCK / 64)
+#define EP_LDS_BINS 4096  // the handover histogram: 16 KiB of u32 counts
+#define EP_WORKGROUPS 1024u
+#define EP_NODE_ROUNDS ((LBFT_MAX_NODES + 63) / 64)
+#define EP_COUNT_COLUMNS 5u  // segments, complete, entries, stranded, blocks
+#define EP_SUM_COLUMNS 2u    // duration, handover
+#define EP_LDS_SUM_ROWS 256u
+static_assert(LBFT_EPOCH_STATS == EP_FAMILIES * 4 && LBFT_EPOCH_FAMILIES == EP_FAMILIES && LBFT_EPOCH_COLUMNS == EP_COLUMNS && LBFT_EPOCH_MAX_BINS == EP_MAX_BINS, "lbft.h");
+static_assert(EP_COUNT_COLUMNS + EP_SUM_COLUMNS == EP_COLUMNS && EP_COL_DURATION == 3 && EP_COL_HANDOVER == 4, "ep_count_slot / ep_count_column");
+__device__ __forceinline__ u32 ep_count_slot(u32 column) { return column < EP_COL_DURATION ? column : column - EP_SUM_COLUMNS; }  // column -> its LDS cell of a row
+__device__ __forceinline__ u32 ep_count_column(u32 slot) { return slot < EP_COL_DURATION ? slot : slot + EP_SUM_COLUMNS; }
+__device__ __forceinline__ void ep_count(u32* t_cnt, u32 row, u32 column) { atomicAdd(&t_cnt[row * EP_COUNT_COLUMNS + ep_count_slot(column)], 1u); }
+// A time into column `column` of row `row`: the 64-bit LDS cell, or above EP_LDS_SUM_ROWS the group's global row (table_g).
+__device__ __forceinline__ void ep_time(unsigned long long* t_sum, unsigned long long* table_g, u32 row, u32 column, u32 v) {
+  if (row < EP_LDS_SUM_ROWS) atomicAdd(&t_sum[row * EP_SUM_COLUMNS + (column - EP_COL_DURATION)], (unsigned long long)v);
+  else atomicAdd(&table_g[ep_cell(row, column)], (unsigned long long)v);
+}
+// `cnt` samples of family f, summing to `sum` and lying in [lo, hi], straight into the workgroup's statistics (GsStat's words: the
+// minimum as max(~v)).  For the families with one sample per instance or per node, by one lane per instance: held in registers like the
+// others, each would take eight in every lane.
+__device__ __forceinline__ void ep_stat_lds(unsigned long long* s_stat, u32 f, u64 cnt, u64 sum, u32 lo, u32 hi) {
+  atomicAdd(&s_stat[4 * f], (unsigned long long)cnt); atomicAdd(&s_stat[4 * f + 1], (unsigned long long)sum);
+  atomicMax(&s_stat[4 * f + 2], ~(unsigned long long)lo); atomicMax(&s_stat[4 * f + 3], (unsigned long long)hi);
+}
+#define EP_LANE_FIRST EP_LENGTH  // families EP_LENGTH .. EP_HANDOVER have a sample per segment or boundary: registers of the lanes
+#define EP_LANE_FAMILIES (EP_HANDOVER - EP_LENGTH + 1)
+__global__ __launch_bounds__(EP_BLOCK) void lbft_k_ps_epochs(Params p, const u32* __restrict__ state, const u32* __restrict__ grp_inst,
+                                                             const u32* __restrict__ grp_off, u32 bin_width, u32 bins, u32 epoch_bins,
+                                                             unsigned long long* __restrict__ handover_hist, unsigned long long* __restrict__ epoch_table,
+                                                             unsigned long long* __restrict__ stats) {
+  __shared__ u32 h_hand[EP_LDS_BINS], t_cnt[EP_MAX_BINS * EP_COUNT_COLUMNS];
+  __shared__ unsigned long long t_sum[EP_LDS_SUM_ROWS * EP_SUM_COLUMNS], s_stat[LBFT_EPOCH_STATS];
+  const u32 g = blockIdx.y;
+  const uint2 grp = gs_group(grp_inst, grp_off, g, p.m);
+  const u32 first = grp.x, cnt = grp.y;
+  if (blockIdx.x * EP_WAVES >= cnt) return;  // (the whole workgroup: its group has fewer instances)
+  const u32 wave = threadIdx.x / 64, lane = threadIdx.x % 64;
+  const u32 n = p.n, lcap = p.lcap, lg = p.off_log;
+  const u32 sum_rows = epoch_bins < EP_LDS_SUM_ROWS ? epoch_bins : EP_LDS_SUM_ROWS;
+  unsigned long long* const table_g = epoch_table + (size_t)g * epoch_bins * EP_COLUMNS;
+  gs_stats_clear<LBFT_EPOCH_STATS>(s_stat);
+  GsStat st[EP_LANE_FAMILIES] = {};  // family f at st[f - EP_LANE_FIRST]
+  for (u32 base = 0; base < bins; base += EP_LDS_BINS) {
+    const u32 span = bins - base < EP_LDS_BINS ? bins - base : EP_LDS_BINS;
+    const bool stat_pass = base == 0;
+    gs_lds_clear<EP_BLOCK>(h_hand, span);
+    if (stat_pass) {
+      gs_lds_clear<EP_BLOCK>(t_cnt, epoch_bins * EP_COUNT_COLUMNS);
+      for (u32 k = threadIdx.x; k < sum_rows * EP_SUM_COLUMNS; k += EP_BLOCK) t_sum[k] = 0;
+    }
+    __syncthreads();
+    for (u32 q = blockIdx.x * EP_WAVES + wave; q < cnt; q += gridDim.x * EP_WAVES) {  // (one instance per wavefront: uniform in it)
+      const u32 i = gs_instance(grp_inst, first, q);
+      Sim s(p, const_cast<u32*>(state), i);
+      if (s.ld(I_FAULT) != 0) continue;
+      // node pass
+      u32 nc[EP_NODE_ROUNDS], e_max = 0, e_min = ~0u;
+      unsigned long long e_sum = 0;
+#pragma unroll
+      for (u32 r = 0; r < EP_NODE_ROUNDS; r++) {
+        nc[r] = cw_commits(s, r * 64 + lane, n, lcap);
+        if (r * 64 + lane < n) {
+          const u32 e = s.nfm(r * 64 + lane, NF_EPOCH);
+          e_max = e > e_max ? e : e_max; e_min = e < e_min ? e : e_min; e_sum += e;
+        }
+      }
+      const CwChain ch = cw_node_pass<EP_NODE_ROUNDS>(nc, lane, n, 64u);
+      if (stat_pass) {  // E_max, E_min and the sum of the E_j: behind's samples E_max - E_j lie in [0, E_max - E_min] and sum to n E_max - sum
+        for (int d = 32; d; d >>= 1) {
+          const u32 hi = (u32)__shfl_xor((int)e_max, d, 64), lo = (u32)__shfl_xor((int)e_min, d, 64);
+          e_max = hi > e_max ? hi : e_max; e_min = lo < e_min ? lo : e_min; e_sum += __shfl_xor(e_sum, d, 64);
+        }
+        if (lane == 0) {
+          ep_stat_lds(s_stat, EP_NODE_EPOCH, n, e_sum, e_min, e_max);
+          ep_stat_lds(s_stat, EP_BEHIND, n, (u64)n * e_max - e_sum, 0u, e_max - e_min);
+        }
+      }
+      const u32 row = lg + ch.ref * lcap;  // (ch.L <= lcap, ref < n: both from keys built from the counts)
+      const u32 nb = s.ld(I_NBLOCKS) < p.bcap ? s.ld(I_NBLOCKS) : p.bcap;
+      // chain pass
+      u32 L = ch.L;  // the chain's entries: up to the first id outside the pool
+      u32 carry_e = 0, carry_r = 0, carry_start = 0, tip_e = 0, segments = 0;
+      i32 carry_g = 0, carry_first_g = 0;  // g of the previous chunk's last entry; g of the entry at carry_start
+      for (u32 c0 = 0; c0 < L; c0 += 64) {
+        const u32 k = c0 + lane;
+        const bool have = k < L;
+        const u32 y = have ? s.ld(row + k) : 0;  // (k < L <= lcap: inside the row)
+        const unsigned long long bad = __ballot(have && !rh_valid_id(y, nb));
+        const u32 inblk = L - c0 < 64 ? L - c0 : 64;
+        const u32 jb = bad ? (u32)__builtin_ctzll(bad) : 64u;
+        const u32 nv = jb < inblk ? jb : inblk;  // the chunk's entries before the first bad id
+        const bool live = lane < nv;
+        u32 epoch = 0, round = 0;
+        i32 gt = 0;
+        if (live) {
+          epoch = s.bf(y, B_EPOCH); round = s.bf(y, B_ROUND);
+          gt = cw_proposal(s, y, s.blk_author(y));
+        }
+        u32 pe = (u32)__shfl_up((int)epoch, 1, 64), pr = (u32)__shfl_up((int)round, 1, 64);
+        i32 pg = __shfl_up(gt, 1, 64);
+        if (lane == 0) { pe = carry_e; pr = carry_r; pg = carry_g; }
+        carry_e = (u32)__shfl((int)epoch, 63, 64);  // (of a chunk that is not full: the last one, nothing reads it)
+        carry_r = (u32)__shfl((int)round, 63, 64);
+        carry_g = __shfl(gt, 63, 64);
+        if (nv) tip_e = (u32)__shfl((int)epoch, (int)nv - 1, 64);
+        const bool start = live && ep_segment_start(k, epoch, pe);
+        const unsigned long long starts = __ballot(start), below = starts & ((1ull << lane) - 1ull);
+        const i32 lane_first_g = __shfl(gt, (int)ep_start_lane(below), 64);
+        const i32 first_g = below ? lane_first_g : carry_first_g;  // g of the first entry of the segment that ends before this lane
+        if (start && k > 0) {  // a boundary
+          const u32 handover = ep_clamped(gt, pg);
+          gs_lds_count(h_hand, handover, bin_width, bins, base, span);
+          if (stat_pass) {
+            const u32 duration = ep_clamped(pg, first_g), x_prev = ep_bin(pe, epoch_bins);
+            gs_stat_add(st[EP_LENGTH - EP_LANE_FIRST], k - ep_segment_first(below, c0, carry_start));
+            gs_stat_add(st[EP_DURATION - EP_LANE_FIRST], duration); gs_stat_add(st[EP_LAST_ROUND - EP_LANE_FIRST], pr); gs_stat_add(st[EP_HANDOVER - EP_LANE_FIRST], handover);
+            ep_count(t_cnt, x_prev, EP_COL_COMPLETE);
+            ep_time(t_sum, table_g, x_prev, EP_COL_DURATION, duration);
+            ep_time(t_sum, table_g, ep_bin(epoch, epoch_bins), EP_COL_HANDOVER, handover);
+          }
+        }
+        if (stat_pass && live) {
+          const u32 x = ep_bin(epoch, epoch_bins);
+          ep_count(t_cnt, x, EP_COL_ENTRIES);
+          if (start) { gs_stat_add(st[EP_FIRST_ROUND - EP_LANE_FIRST], round); ep_count(t_cnt, x, EP_COL_SEGMENTS); }
+        }
+        if (starts) carry_first_g = __shfl(gt, (int)ep_highest(starts), 64);
+        carry_start = ep_carry_start(starts, c0, carry_start);
+        segments += (u32)__popcll(starts);
+        if (nv < inblk) L = c0 + nv;  // (ends the loop)
+      }
+      if (!stat_pass) continue;
+      // pool pass
+      u32 stranded = 0;
+      for (u32 b0 = 1; b0 <= nb; b0 += 64) {
+        const u32 b = b0 + lane;
+        const bool have = b <= nb;
+        bool off = false;
+        if (have) {
+          const u32 epoch = s.bf(b, B_EPOCH), slot = vt_chain_slot(s.bf(b, B_DEPTH), L), x = ep_bin(epoch, epoch_bins);
+          const u32 at = slot < L ? s.ld(row + slot) : 0;  // (slot < L <= lcap: inside the row)
+          off = ep_stranded(vt_member(slot, L, at, b), L != 0, epoch, tip_e);
+          ep_count(t_cnt, x, EP_COL_BLOCKS);
+          if (off) ep_count(t_cnt, x, EP_COL_STRANDED);
+        }
+        stranded += vt_ballot_count(off);
+      }
+      if (lane == 0) {  // one sample per instance
+        ep_stat_lds(s_stat, EP_SEGMENTS, 1, segments, segments, segments); ep_stat_lds(s_stat, EP_STRANDED, 1, stranded, stranded, stranded);
+        ep_stat_lds(s_stat, EP_BLOCKS, 1, nb, nb, nb);
+      }
+    }
+    if (stat_pass) gs_reduce_to_lds<EP_LANE_FAMILIES>(st, s_stat + 4 * EP_LANE_FIRST, lane == 0);
+    __syncthreads();
+    gs_lds_flush<EP_BLOCK>(h_hand, handover_hist, g, bins, base, span);
+    if (stat_pass) {
+      for (u32 k = threadIdx.x; k < epoch_bins * EP_COUNT_COLUMNS; k += EP_BLOCK)
+        if (t_cnt[k]) atomicAdd(&table_g[ep_cell(k / EP_COUNT_COLUMNS, ep_count_column(k % EP_COUNT_COLUMNS))], (unsigned long long)t_cnt[k]);
+      for (u32 k = threadIdx.x; k < sum_rows * EP_SUM_COLUMNS; k += EP_BLOCK)
+        if (t_sum[k]) atomicAdd(&table_g[ep_cell(k / EP_SUM_COLUMNS, EP_COL_DURATION + k % EP_SUM_COLUMNS)], t_sum[k]);
+      gs_stats_out<LBFT_EPOCH_STATS>(s_stat, stats, g);
+    }
+    __syncthreads();  // (before the next pass clears the histogram)
+  }
+}
+
 extern "C" {
+
+// The caller zeroed all three outputs.
+__attribute__((visibility("default"))) hipError_t lbft_ps_launch_epochs(const Params* p, const u32* state, const u32* grp_inst, const u32* grp_off, u32 n_groups,
+                                                                       u32 max_group, u32 bin_width, u32 bins, u32 epoch_bins,
+                                                                       unsigned long long* handover_hist, unsigned long long* epoch_table,
+                                                                       unsigned long long* stats, hipStream_t stream) {
+  if (bin_width == 0 || bins == 0 || epoch_bins == 0 || epoch_bins > EP_MAX_BINS || n_groups == 0 || max_group == 0 || p->n == 0 || p->n > LBFT_MAX_NODES ||
+      !handover_hist || !epoch_table || !stats)
+    return hipErrorInvalidValue;
+  // (an instance of the largest group gives at most bcap >= lcap samples to a bin of the histogram or a counting cell of the table)
+  const u64 gx = gs_workgroups(EP_WORKGROUPS, n_groups, ((u64)max_group + EP_WAVES - 1) / EP_WAVES, (u64)max_group * p->bcap);
+  lbft_k_ps_epochs<<<dim3((u32)gx, n_groups), EP_BLOCK, 0, stream>>>(*p, state, grp_inst, grp_off, bin_width, bins, epoch_bins, handover_hist, epoch_table, stats);
+  return hipGetLastError();
+}
 
 // The caller zeroed all four outputs.
 __attribute__((visibility("default"))) hipError_t lbft_ps_launch_votes(const Params* p, const u32* state, const u32* grp_inst, const u32* grp_off, u32 n_groups,

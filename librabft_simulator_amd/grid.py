@@ -35,6 +35,10 @@ to a capacity); like ``--chain`` it needs neither commit times nor the trace and
 ``--votes`` adds a ``"votes"`` object (BatchResult.votes_by_param_set: the votes, weight and margin of the chain's quorum certificates,
 the rounds the chain skipped, the blocks proposed, orphaned and pending, each node's participation, the orphan rate and the round
 utilisation); it too needs neither commit times nor the trace.
+``--epochs`` adds an ``"epochs"`` object (BatchResult.epochs_by_param_set: the chain's segments of one epoch -- length, duration, first
+and last round --, the handover between two epochs and its cost against the interval inside an epoch, the blocks stranded in an epoch
+the chain has left, how far the nodes' epochs lie behind the foremost, and the same per epoch); it goes with a small
+``--commands-per-epoch`` and needs neither commit times nor the trace.
 """
 import argparse
 import itertools
@@ -140,6 +144,7 @@ def main(argv=None):
     ap.add_argument("--chain", action="store_true", help="add each point's chain statistics (agreement, chain quality, block cadence)")
     ap.add_argument("--load", action="store_true", help="add each point's run load (message counts per commit, capacity headroom, worst seeds)")
     ap.add_argument("--votes", action="store_true", help="add each point's vote statistics (QC sizes and margins, participation, orphaned blocks)")
+    ap.add_argument("--epochs", action="store_true", help="add each point's epoch statistics (handover cost, stranded blocks, nodes left behind)")
     ap.add_argument("--round-trace", type=int, default=None, metavar="N", help="with --rounds: rounds per node the trace keeps")
     args = ap.parse_args(argv)
     if args.round_trace is not None and (args.round_trace < 1 or not args.rounds):
@@ -172,6 +177,7 @@ def main(argv=None):
         chain = res.chain_by_param_set() if args.chain else None
         load = res.load_by_param_set() if args.load else None
         votes = res.votes_by_param_set() if args.votes else None
+        epochs = res.epochs_by_param_set() if args.epochs else None
         for k, (pt, row) in enumerate(zip(points, res.by_param_set())):
             line = dict(pt, nodes=args.nodes, max_clock=args.max_clock, seeds=args.seeds_per_point, assign=args.assign)
             line.update(instances=row["instances"], faulted=row["faulted"], commits=row["commits"], rounds=row["rounds"])
@@ -195,6 +201,8 @@ def main(argv=None):
                 line["load"] = load[k]
             if votes is not None:
                 line["votes"] = votes[k]
+            if epochs is not None:
+                line["epochs"] = epochs[k]
             print(json.dumps(line), flush=True)
     finally:
         sim.close()

@@ -543,6 +543,73 @@ class BatchResult:
             out.append(row)
         return out
 
+    def _epoch_binning(self, bin_width, bins):
+        """(bin_width, bins) of ``epoch_stats``: by default the handover histogram covers [0, max_clock] in at most 4 096 bins, one pass
+        through the kernel's LDS -- width ceil((max_clock + 1) / 4096) and as many bins as that width needs."""
+        span = int(self._sim._max_clock) + 1
+        if bin_width is None:
+            bin_width = -(-span // (int(bins) if bins else 4096))
+        if bins is None:
+            bins = -(-span // int(bin_width))
+        return int(bin_width), int(bins)
+
+    def epoch_stats(self, bin_width=None, bins=None, epoch_bins=64):
+        """Epoch statistics computed on the device (lbft_batch_epoch_stats), per group (the parameter sets of a ``with_param_sets`` batch,
+        else one group): ``(handover_hist, epoch_table, stats)``.  An instance's chain is that of ``vote_stats``; a *segment* is a maximal
+        run of chain entries of one epoch, the last one *open*, the others *complete*; a *boundary* is a chain pair of two epochs.
+        ``stats[group]`` (40 uint64) holds ``(samples, sum, min, max)`` of the ten families of ``EPOCH_FAMILIES``: per instance its
+        ``segments``; per node its ``node_epoch`` and how far that lies ``behind`` the instance's foremost node; per complete segment its
+        ``length`` in entries, its ``duration`` (last proposal - first) and its ``last_round``; per segment its ``first_round``; per
+        boundary the ``handover`` (the later entry's proposal - the earlier one's); per instance the ``stranded`` blocks (off the chain,
+        in an epoch below the tip's) and the ``blocks`` of its pool.  ``handover_hist[group, min(handover // bin_width, bins - 1)]`` bins
+        the handovers; ``epoch_table[group, min(epoch, epoch_bins - 1)]`` holds, in the order of ``EPOCH_COLUMNS``, the epoch's
+        ``segments``, the ``complete`` ones, its chain ``entries``, the sums of its segments' ``duration`` and of the ``handover`` into
+        it, its ``stranded`` blocks and its pool ``blocks``.  Instances with a fault are skipped.  By default the histogram covers
+        [0, max_clock] in at most 4 096 bins.  Needs nothing of the run: no commit times, no round trace; serves every kind of batch."""
+        if (bin_width is not None and int(bin_width) < 1) or (bins is not None and int(bins) < 1):
+            raise ValueError("bin_width and bins must be at least 1")
+        if not 1 <= int(epoch_bins) <= _lib.EPOCH_MAX_BINS:
+            raise ValueError("epoch_bins: 1 to %d" % _lib.EPOCH_MAX_BINS)
+        bin_width, bins = self._epoch_binning(bin_width, bins)
+        groups, epoch_bins = self._groups(), int(epoch_bins)
+        hist = np.zeros((groups, bins), dtype=np.uint64)
+        table = np.zeros((groups, epoch_bins, len(_lib.EPOCH_COLUMNS)), dtype=np.uint64)
+        stats = np.zeros((groups, _lib.EPOCH_STATS), dtype=np.uint64)
+        check(_lib.lib().lbft_batch_epoch_stats(self._sim._h, bin_width, bins, epoch_bins, hist.ctypes.data, table.ctypes.data, stats.ctypes.data))
+        return hist, table, stats
+
+    def epochs_by_param_set(self, epoch_bins=64, quantiles=(0.5, 0.9, 0.99)):
+        """Per group of ``epoch_stats`` (default binning), in set order: the ten families of ``EPOCH_FAMILIES`` = samples (``instances``,
+        ``nodes``, ``segments`` or ``boundaries``), mean, min, max; ``handover["quantiles"]`` ({str(q): ticks}, exact, the inverted-CDF
+        rule of ``histogram_quantile``; ``None`` when the default bins are wider than one tick); ``handover_cost`` = the mean handover
+        minus the mean interval inside an epoch, sum(duration) / (sum(length) - segments) over the complete segments: what an epoch
+        change adds to a block interval; ``stranded_per_epoch`` = stranded blocks / complete segments; ``behind_share`` = the share of the
+        clean instances' nodes that ended in an epoch below their instance's foremost node's; ``per_epoch``: the epoch table's rows up
+        to the last one that is not empty, each ``{"epoch", *EPOCH_COLUMNS}`` (the row ``epoch_bins - 1`` also holds every epoch above
+        it).  ``None`` where a denominator is 0."""
+        width, _ = self._epoch_binning(None, None)
+        hist, table, stats = self.epoch_stats(epoch_bins=epoch_bins)
+        names = _lib.EPOCH_FAMILIES
+        keys = ("instances", "nodes", "nodes", "segments", "segments", "segments", "segments", "boundaries", "instances", "instances")
+        set_of = getattr(self._sim, "set_of_instance", None) if self._sim.param_sets is not None else None
+        node_epochs, clean = self.epochs.astype(np.int64), self.faults == 0
+        behind = node_epochs.max(axis=1, keepdims=True) - node_epochs > 0
+        out = []
+        for g in range(hist.shape[0]):
+            row = {"set": g, **_families(stats[g], tuple(zip(names, keys)))}
+            row["handover"]["quantiles"] = {str(q): histogram_quantile(hist[g], 1, q) for q in quantiles} if width == 1 else None
+            total = lambda name, word: int(stats[g, 4 * names.index(name) + word])
+            complete, inner = total("length", 0), total("length", 1) - total("length", 0)
+            row["handover_cost"] = row["handover"]["mean"] - total("duration", 1) / inner if complete and inner else None
+            row["stranded_per_epoch"] = total("stranded", 1) / complete if complete else None
+            members = clean if set_of is None else clean & (set_of == g)
+            row["behind_share"] = float(behind[members].mean()) if members.any() else None
+            used = np.flatnonzero(table[g].any(axis=1))
+            row["per_epoch"] = [{"epoch": x, **{c: int(v) for c, v in zip(_lib.EPOCH_COLUMNS, table[g, x])}}
+                                for x in range(int(used[-1]) + 1 if len(used) else 0)]
+            out.append(row)
+        return out
+
     def by_param_set(self):
         """Per parameter set of a ``BatchSimulator.with_param_sets`` batch, in set order: the number of instances, of faulted instances,
         and mean / min / max over its instances of the commits and of the active round (each instance's minimum over its nodes)."""
