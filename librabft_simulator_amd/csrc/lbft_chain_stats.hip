@@ -14,16 +14,15 @@
 
 using namespace lbft;
 
-#include "lbft_chain_walk.h"  // the node pass, the proposal time
+#include "lbft_chain_walk.h"  // the workgroup prologue, the node pass, the proposal time, the predecessor by shuffle
 
-// One wavefront per instance.  The kernel reads, through the generic Sim accessors (every layout: tile widths 1, lanes per wavefront,
-// 64), the instance's fault word, NF_NCOMMITS and NF_STARTUP of its nodes, the log rows log[n][lcap] and of the block records B_LINK
-// and B_TIME.
-//   node pass (lane = node, two rounds for more than 64 nodes): nc_j = min(NF_NCOMMITS, lcap); a butterfly over the keys
-//     (nc_j, ~j) gives the chain's length L and the reference node; each lane adds its nodes' lag samples.
-//   chain pass (lane = entry, 64 at a time): b = log[ref][k], then the dependent gathers B_LINK, B_TIME and startup[author]; the
-//     predecessor's time and author come by __shfl_up, lane 0 takes what the previous chunk carried.  A lane that begins a run of its
-//     author finds the previous run start as the highest set bit below it in the ballot of the run starts, or carried.
+// One wavefront per instance, walked with lbft_chain_walk.h.  The kernel reads, through the generic Sim accessors (every layout: tile
+// widths 1, lanes per wavefront, 64), the instance's fault word, NF_NCOMMITS and NF_STARTUP of its nodes, the log rows log[n][lcap] and of
+// the block records B_LINK and B_TIME.
+//   node pass: each lane adds its nodes' lag samples L - nc_j.
+//   chain pass (lane = entry, 64 at a time): b = log[ref][k], then the dependent gathers B_LINK, B_TIME and startup[author]; time and
+//     author of the predecessor (cw_prev).  A lane that begins a run of its author finds the previous run start as the highest set bit
+//     below it in the ballot of the run starts, or carried.
 //   audit (inside the chain pass, the chunk's block ids in registers): the same 64 entries of every other node's row, compared below
 //     that node's nc_j (<= L: the chain is the longest log).  The rows are read whether or not they are compared (k < L <= lcap: inside
 //     the row), so the loads do not wait for the counts.
@@ -48,11 +47,9 @@ __global__ __launch_bounds__(LBFT_CS_BLOCK) void lbft_k_cs_chain(Params p, const
                                                                  unsigned long long* __restrict__ stats) {
   __shared__ u32 h_int[LBFT_CS_LDS_BINS], h_auth[LBFT_MAX_NODES];
   __shared__ unsigned long long s_stat[LBFT_CHAIN_STATS];
-  const u32 g = blockIdx.y;
-  const uint2 grp = gs_group(grp_inst, grp_off, g, p.m);
-  const u32 first = grp.x, cnt = grp.y;
-  if (blockIdx.x * LBFT_CS_WAVES >= cnt) return;  // (the whole workgroup: its group has fewer instances)
-  const u32 wave = threadIdx.x / 64, lane = threadIdx.x % 64;
+  CwGroup w;
+  if (!cw_group_begin<LBFT_CS_WAVES>(w, p, grp_inst, grp_off)) return;
+  const u32 g = w.g, first = w.first, cnt = w.cnt, wave = w.wave, lane = w.lane;
   const u32 n = p.n, lcap = p.lcap, lg = p.off_log;
   gs_stats_clear<LBFT_CHAIN_STATS>(s_stat);
   GsStat st[CHN_FAMILIES] = {};
@@ -68,9 +65,7 @@ __global__ __launch_bounds__(LBFT_CS_BLOCK) void lbft_k_cs_chain(Params p, const
       if (s.ld(I_FAULT) != 0) continue;
       // node pass
       u32 nc[LBFT_CS_NODE_ROUNDS];
-#pragma unroll
-      for (u32 r = 0; r < LBFT_CS_NODE_ROUNDS; r++) nc[r] = cw_commits(s, r * 64 + lane, n, lcap);
-      const CwChain ch = cw_node_pass<LBFT_CS_NODE_ROUNDS>(nc, lane, n, 64u);
+      const CwChain ch = cw_chain_of(s, lane, n, lcap, 64u, nc);
       const u32 L = ch.L, ref = ch.ref;
       if (stat_pass) {
 #pragma unroll
@@ -91,11 +86,8 @@ __global__ __launch_bounds__(LBFT_CS_BLOCK) void lbft_k_cs_chain(Params p, const
           a = s.blk_author(b);
           gt = cw_proposal(s, b, a);
         }
-        i32 pg = __shfl_up(gt, 1, 64);
-        u32 pa = (u32)__shfl_up((int)a, 1, 64);
-        if (lane == 0) { pg = carry_g; pa = carry_a; }
-        carry_g = __shfl(gt, 63, 64);  // (of a chunk that is not full: the last one, nothing reads it)
-        carry_a = (u32)__shfl((int)a, 63, 64);
+        const i32 pg = cw_prev(gt, carry_g, lane);
+        const u32 pa = cw_prev(a, carry_a, lane);
         if (have && k > 0) {
           const u32 v = chn_interval(pg, gt);
           gs_lds_count(h_int, v, bin_width, bins, base, span);

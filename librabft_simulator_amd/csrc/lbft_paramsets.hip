@@ -148,23 +148,20 @@ __global__ __launch_bounds__(LD_BLOCK) void lbft_k_ps_load(Params p, const u32* 
 
 // The vote statistics (lbft_batch_vote_stats): per group, the voter sets of the committed chain -- votes, weight and margin of every
 // quorum certificate, who voted, the rounds the chain skipped -- and the block pool sorted into chain, orphaned and pending, by author.
-// One wavefront per instance, lbft_k_cs_chain's shape: the kernel reads, through the generic Sim accessors (every layout), the fault
-// word, I_NBLOCKS, NF_NCOMMITS of the nodes, the reference node's log row and of the block records B_LINK, B_ROUND, B_EPOCH, B_DEPTH and
-// the mw voter words.
-//   node pass (lane = node, two rounds above 64 nodes): the chain walk's cw_commits / cw_node_pass give L and the reference node.
-//   chain pass (lane = entry, 64 at a time): the id is checked (rh_valid_id) before its record is read; the first id outside the pool
-//     ends the chain there (by ballot).  Popcounts of the voter words; the weight from the rights table in LDS at the epoch's rotation
-//     (unit rights: the popcount); every voter bit counts into the LDS node table.  The predecessor's round and epoch come by
-//     __shfl_up, lane 0 takes what the previous chunk carried.  The tip is broadcast from the last valid entry.
-//   pool pass (lane = block id, 64 at a time over 1 .. nb; first pass only): chain membership is one dependent gather,
-//     log[ref][B_DEPTH - 1] == id (vt_chain_slot / vt_member); proposed and orphaned count into the LDS node table by author, the
-//     per-instance counts are ballots.
+// One wavefront per instance, walked with lbft_chain_walk.h (node pass, pool bound, chunk head, predecessor and tip, membership): the
+// kernel reads, through the generic Sim accessors (every layout), the fault word, I_NBLOCKS, NF_NCOMMITS of the nodes, the reference
+// node's log row and of the block records B_LINK, B_ROUND, B_EPOCH, B_DEPTH and the mw voter words.
+//   chain pass (lane = entry, 64 at a time): popcounts of the voter words; the weight from the rights table in LDS at the epoch's
+//     rotation (unit rights: the popcount); every voter bit counts into the LDS node table.  Round and epoch of the predecessor and of
+//     the tip.
+//   pool pass (lane = block id, 64 at a time over 1 .. nb; first pass only): proposed and orphaned count into the LDS node table by
+//     author, the per-instance counts are ballots.
 // grid = (workgroups per group, groups); a workgroup's VT_WAVES wavefronts stride over the instances of its group and accumulate by the
 // scheme of lbft_group_stats.h: the margin histogram in passes of VT_LDS_BINS bins; the vote-count histogram, the node table and the
 // statistics in the first pass.  Instances with a non-zero fault word are skipped.
-#include "lbft_chain_walk.h"  // the node pass
-#include "lbft_record_hash_rules.h"  // rh_valid_id, rh_voter_field, rh_author_bits
+#include "lbft_record_hash_rules.h"  // rh_voter_field, rh_author_bits
 #include "lbft_vote_rules.h"
+#include "lbft_chain_walk.h"  // (after the vote rules: cw_pool_member)
 #define VT_BLOCK 256
 #define VT_WAVES (VT_BLOCK / 64)
 #define VT_LDS_BINS 4096  // the margin histogram: 16 KiB of u32 counts
@@ -173,17 +170,17 @@ __global__ __launch_bounds__(LD_BLOCK) void lbft_k_ps_load(Params p, const u32* 
 #define VT_MASK_WORDS ((LBFT_MAX_NODES + 31) / 32)
 static_assert(LBFT_VOTE_STATS == VT_FAMILIES * 4 && LBFT_VOTE_FAMILIES == VT_FAMILIES && LBFT_VOTE_NODE_COLUMNS == VT_NODE_COLUMNS, "lbft.h");
 static_assert(LBFT_MAX_NODES <= VT_BLOCK, "the rights table is copied by one lane per node");
-__device__ __forceinline__ u32 vt_ballot_count(bool v) { return (u32)__popcll(__ballot(v)); }
 __global__ __launch_bounds__(VT_BLOCK) void lbft_k_ps_votes(Params p, const u32* __restrict__ state, const u32* __restrict__ grp_inst,
                                                             const u32* __restrict__ grp_off, u32 bin_width, u32 bins,
                                                             unsigned long long* __restrict__ margin_hist, unsigned long long* __restrict__ votes_hist,
                                                             unsigned long long* __restrict__ node_table, unsigned long long* __restrict__ stats) {
   __shared__ u32 h_margin[VT_LDS_BINS], h_votes[LBFT_MAX_NODES + 1], h_node[LBFT_MAX_NODES * VT_NODE_COLUMNS], s_rights[LBFT_MAX_NODES];
   __shared__ unsigned long long s_stat[LBFT_VOTE_STATS];
+  // cw_group_begin, written out: through the helper this kernel takes 128 vector registers for 127 (EXPERIMENTS.md "One pool walk")
   const u32 g = blockIdx.y;
   const uint2 grp = gs_group(grp_inst, grp_off, g, p.m);
   const u32 first = grp.x, cnt = grp.y;
-  if (blockIdx.x * VT_WAVES >= cnt) return;  // (the whole workgroup: its group has fewer instances)
+  if (blockIdx.x * VT_WAVES >= cnt) return;
   const u32 wave = threadIdx.x / 64, lane = threadIdx.x % 64;
   const u32 n = p.n, lcap = p.lcap, lg = p.off_log, mw = p.mw, quorum = p.quorum, rot = p.rot;
   const bool unit = p.unit_weights != 0;
@@ -205,22 +202,15 @@ __global__ __launch_bounds__(VT_BLOCK) void lbft_k_ps_votes(Params p, const u32*
       if (s.ld(I_FAULT) != 0) continue;
       // node pass
       u32 nc[VT_NODE_ROUNDS];
-#pragma unroll
-      for (u32 r = 0; r < VT_NODE_ROUNDS; r++) nc[r] = cw_commits(s, r * 64 + lane, n, lcap);
-      const CwChain ch = cw_node_pass<VT_NODE_ROUNDS>(nc, lane, n, 64u);
-      const u32 ref = ch.ref, row = lg + ref * lcap;  // (ch.L <= lcap, ref < n: both from keys built from the counts)
-      const u32 nb = s.ld(I_NBLOCKS) < p.bcap ? s.ld(I_NBLOCKS) : p.bcap;
+      const CwChain ch = cw_chain_of(s, lane, n, lcap, 64u, nc);
+      const u32 row = lg + ch.ref * lcap, nb = cw_pool_blocks(s, p);
       // chain pass
       u32 L = ch.L;  // the chain's entries: up to the first id outside the pool
       u32 carry_r = 0, carry_e = 0, tip_r = 0, tip_e = 0;
       for (u32 c0 = 0; c0 < L; c0 += 64) {
         const u32 k = c0 + lane;
-        const bool have = k < L;
-        const u32 y = have ? s.ld(row + k) : 0;  // (k < L <= lcap: inside the row)
-        const unsigned long long bad = __ballot(have && !rh_valid_id(y, nb));
-        const u32 inblk = L - c0 < 64 ? L - c0 : 64;
-        const u32 jb = bad ? (u32)__builtin_ctzll(bad) : 64u;
-        const u32 nv = jb < inblk ? jb : inblk;  // the chunk's entries before the first bad id
+        const CwChunk ck = cw_chunk(s, row, c0, L, nb, lane, 64u, 0u);
+        const u32 y = ck.y, nv = ck.nv;
         const bool live = lane < nv;
         u32 round = 0, epoch = 0, votes = 0, weight = 0;
         if (live) {
@@ -240,11 +230,8 @@ __global__ __launch_bounds__(VT_BLOCK) void lbft_k_ps_votes(Params p, const u32*
           }
           if (unit) weight = votes;
         }
-        u32 pr = (u32)__shfl_up((int)round, 1, 64), pe = (u32)__shfl_up((int)epoch, 1, 64);
-        if (lane == 0) { pr = carry_r; pe = carry_e; }
-        carry_r = (u32)__shfl((int)round, 63, 64);  // (of a chunk that is not full: the last one, nothing reads it)
-        carry_e = (u32)__shfl((int)epoch, 63, 64);
-        if (nv) { tip_r = (u32)__shfl((int)round, (int)nv - 1, 64); tip_e = (u32)__shfl((int)epoch, (int)nv - 1, 64); }
+        const u32 pr = cw_prev(round, carry_r, lane), pe = cw_prev(epoch, carry_e, lane);
+        if (nv) { tip_r = cw_tip(round, nv); tip_e = cw_tip(epoch, nv); }
         if (live && votes) {
           const u32 margin = vt_margin(weight, quorum);
           gs_lds_count(h_margin, margin, bin_width, bins, base, span);
@@ -254,7 +241,7 @@ __global__ __launch_bounds__(VT_BLOCK) void lbft_k_ps_votes(Params p, const u32*
           }
         }
         if (stat_pass && live && k > 0 && vt_same_epoch(pe, epoch)) gs_stat_add(st[VT_SKIPPED], vt_skipped(pr, round));
-        if (nv < inblk) L = c0 + nv;  // (ends the loop)
+        if (cw_ends(ck)) L = c0 + nv;  // (ends the loop)
       }
       if (!stat_pass) continue;
       // pool pass
@@ -266,20 +253,19 @@ __global__ __launch_bounds__(VT_BLOCK) void lbft_k_ps_votes(Params p, const u32*
         bool certified = false;
         if (have) {
           author = s.bf(b, B_LINK) >> 16;
-          const u32 round = s.bf(b, B_ROUND), epoch = s.bf(b, B_EPOCH), slot = vt_chain_slot(s.bf(b, B_DEPTH), L);
+          const u32 round = s.bf(b, B_ROUND), epoch = s.bf(b, B_EPOCH), depth = s.bf(b, B_DEPTH);
 #pragma unroll
           for (u32 w = 0; w < VT_MASK_WORDS; w++)
             if (w < mw) certified |= (s.bf(b, rh_voter_field(w, mw)) & rh_author_bits(w, n)) != 0;
-          const u32 at = slot < L ? s.ld(row + slot) : 0;  // (slot < L <= lcap: inside the row)
-          cls = vt_classify(vt_member(slot, L, at, b), L != 0, epoch, round, tip_e, tip_r);
+          cls = vt_classify(cw_pool_member(s, row, depth, L, b), L != 0, epoch, round, tip_e, tip_r);
           if (author < n) {
             atomicAdd(&h_node[vt_node_cell(author, VT_COL_PROPOSED)], 1u);
             if (cls == VT_ORPHAN) atomicAdd(&h_node[vt_node_cell(author, VT_COL_ORPHANED)], 1u);
           }
         }
-        orphaned += vt_ballot_count(have && cls == VT_ORPHAN);
-        pending += vt_ballot_count(have && cls == VT_PENDING_BLOCK);
-        certified_off += vt_ballot_count(have && cls != VT_ON_CHAIN && certified);
+        orphaned += cw_ballot_count(have && cls == VT_ORPHAN);
+        pending += cw_ballot_count(have && cls == VT_PENDING_BLOCK);
+        certified_off += cw_ballot_count(have && cls != VT_ON_CHAIN && certified);
       }
       if (lane == 0) {  // one sample per instance
         gs_stat_add(st[VT_BLOCKS], nb); gs_stat_add(st[VT_ORPHANED], orphaned);
@@ -300,19 +286,17 @@ __global__ __launch_bounds__(VT_BLOCK) void lbft_k_ps_votes(Params p, const u32*
 
 // The epoch statistics (lbft_batch_epoch_stats): per group, the committed chain cut into segments of one epoch -- their length, duration
 // and rounds, the handover between two of them --, the epochs the nodes ended in and the pool blocks stranded in an epoch the chain has
-// left; the same per epoch in the epoch table.  lbft_k_ps_votes' shape: one wavefront per instance, the generic Sim accessors (every
-// layout).  The kernel reads the fault word, I_NBLOCKS, NF_NCOMMITS, NF_EPOCH and NF_STARTUP of the nodes, the reference node's log row and
-// of the block records B_LINK, B_ROUND, B_EPOCH, B_TIME and B_DEPTH.
-//   node pass (lane = node, two rounds above 64 nodes): cw_commits / cw_node_pass give L and the reference node; the same lanes read
-//     NF_EPOCH, and wavefront max, min and sum of it give families node_epoch and behind whole.
-//   chain pass (lane = entry, 64 at a time): the id is checked (rh_valid_id) before its record is read; the first id outside the pool
-//     ends the chain there (by ballot).  e, r and g of the predecessor come by __shfl_up, lane 0 takes what the previous chunk carried.
+// left; the same per epoch in the epoch table.  One wavefront per instance, walked with lbft_chain_walk.h as lbft_k_ps_votes is, the
+// generic Sim accessors (every layout).  The kernel reads the fault word, I_NBLOCKS, NF_NCOMMITS, NF_EPOCH and NF_STARTUP of the nodes, the
+// reference node's log row and of the block records B_LINK, B_ROUND, B_EPOCH, B_TIME and B_DEPTH.
+//   node pass: the same lanes read NF_EPOCH, and wavefront max, min and sum of it give families node_epoch and behind whole.
+//   chain pass (lane = entry, 64 at a time): e, r and g of the predecessor (cw_prev).
 //     The segment starts of a chunk are a ballot; a start at k > 0 is a boundary and closes the segment before it, whose first entry is
 //     the highest start below the lane or the carried one (ep_segment_first; its g by one more shuffle): length, duration, last_round
 //     and the row of the EARLIER epoch (complete, duration), handover and the row of the LATER one.  Every start gives first_round and
 //     counts a segment, every entry counts into its epoch's row: the open segment at the chain's end has thereby given all it gives.
-//   pool pass (lane = block id, 64 at a time over 1 .. nb; first pass only): a block counts into its epoch's row; membership is
-//     vt_member's one gather; stranded (ep_stranded) by ballot for the instance and per block for the row.
+//   pool pass (lane = block id, 64 at a time over 1 .. nb; first pass only): a block counts into its epoch's row; stranded
+//     (ep_stranded) by ballot for the instance and per block for the row.
 // LDS: the handover histogram in passes of EP_LDS_BINS bins (16 KiB); the table's five counting columns as u32 cells for all 512 rows
 // (10 KiB) and its two time columns as 64-bit cells for the first EP_LDS_SUM_ROWS rows (4 KiB) -- a sum of times is never held in less
 // than 64 bits; rows above that, which only a chain of more than 256 epochs reaches, add to the global table directly --; the
@@ -351,11 +335,9 @@ __global__ __launch_bounds__(EP_BLOCK) void lbft_k_ps_epochs(Params p, const u32
                                                              unsigned long long* __restrict__ stats) {
   __shared__ u32 h_hand[EP_LDS_BINS], t_cnt[EP_MAX_BINS * EP_COUNT_COLUMNS];
   __shared__ unsigned long long t_sum[EP_LDS_SUM_ROWS * EP_SUM_COLUMNS], s_stat[LBFT_EPOCH_STATS];
-  const u32 g = blockIdx.y;
-  const uint2 grp = gs_group(grp_inst, grp_off, g, p.m);
-  const u32 first = grp.x, cnt = grp.y;
-  if (blockIdx.x * EP_WAVES >= cnt) return;  // (the whole workgroup: its group has fewer instances)
-  const u32 wave = threadIdx.x / 64, lane = threadIdx.x % 64;
+  CwGroup wg;
+  if (!cw_group_begin<EP_WAVES>(wg, p, grp_inst, grp_off)) return;
+  const u32 g = wg.g, first = wg.first, cnt = wg.cnt, wave = wg.wave, lane = wg.lane;
   const u32 n = p.n, lcap = p.lcap, lg = p.off_log;
   const u32 sum_rows = epoch_bins < EP_LDS_SUM_ROWS ? epoch_bins : EP_LDS_SUM_ROWS;
   unsigned long long* const table_g = epoch_table + (size_t)g * epoch_bins * EP_COLUMNS;
@@ -377,15 +359,13 @@ __global__ __launch_bounds__(EP_BLOCK) void lbft_k_ps_epochs(Params p, const u32
       // node pass
       u32 nc[EP_NODE_ROUNDS], e_max = 0, e_min = ~0u;
       unsigned long long e_sum = 0;
+      const CwChain ch = cw_chain_of(s, lane, n, lcap, 64u, nc);
 #pragma unroll
-      for (u32 r = 0; r < EP_NODE_ROUNDS; r++) {
-        nc[r] = cw_commits(s, r * 64 + lane, n, lcap);
+      for (u32 r = 0; r < EP_NODE_ROUNDS; r++)
         if (r * 64 + lane < n) {
           const u32 e = s.nfm(r * 64 + lane, NF_EPOCH);
           e_max = e > e_max ? e : e_max; e_min = e < e_min ? e : e_min; e_sum += e;
         }
-      }
-      const CwChain ch = cw_node_pass<EP_NODE_ROUNDS>(nc, lane, n, 64u);
       if (stat_pass) {  // E_max, E_min and the sum of the E_j: behind's samples E_max - E_j lie in [0, E_max - E_min] and sum to n E_max - sum
         for (int d = 32; d; d >>= 1) {
           const u32 hi = (u32)__shfl_xor((int)e_max, d, 64), lo = (u32)__shfl_xor((int)e_min, d, 64);
@@ -396,20 +376,15 @@ __global__ __launch_bounds__(EP_BLOCK) void lbft_k_ps_epochs(Params p, const u32
           ep_stat_lds(s_stat, EP_BEHIND, n, (u64)n * e_max - e_sum, 0u, e_max - e_min);
         }
       }
-      const u32 row = lg + ch.ref * lcap;  // (ch.L <= lcap, ref < n: both from keys built from the counts)
-      const u32 nb = s.ld(I_NBLOCKS) < p.bcap ? s.ld(I_NBLOCKS) : p.bcap;
+      const u32 row = lg + ch.ref * lcap, nb = cw_pool_blocks(s, p);
       // chain pass
       u32 L = ch.L;  // the chain's entries: up to the first id outside the pool
       u32 carry_e = 0, carry_r = 0, carry_start = 0, tip_e = 0, segments = 0;
       i32 carry_g = 0, carry_first_g = 0;  // g of the previous chunk's last entry; g of the entry at carry_start
       for (u32 c0 = 0; c0 < L; c0 += 64) {
         const u32 k = c0 + lane;
-        const bool have = k < L;
-        const u32 y = have ? s.ld(row + k) : 0;  // (k < L <= lcap: inside the row)
-        const unsigned long long bad = __ballot(have && !rh_valid_id(y, nb));
-        const u32 inblk = L - c0 < 64 ? L - c0 : 64;
-        const u32 jb = bad ? (u32)__builtin_ctzll(bad) : 64u;
-        const u32 nv = jb < inblk ? jb : inblk;  // the chunk's entries before the first bad id
+        const CwChunk ck = cw_chunk(s, row, c0, L, nb, lane, 64u, 0u);
+        const u32 y = ck.y, nv = ck.nv;
         const bool live = lane < nv;
         u32 epoch = 0, round = 0;
         i32 gt = 0;
@@ -417,13 +392,9 @@ __global__ __launch_bounds__(EP_BLOCK) void lbft_k_ps_epochs(Params p, const u32
           epoch = s.bf(y, B_EPOCH); round = s.bf(y, B_ROUND);
           gt = cw_proposal(s, y, s.blk_author(y));
         }
-        u32 pe = (u32)__shfl_up((int)epoch, 1, 64), pr = (u32)__shfl_up((int)round, 1, 64);
-        i32 pg = __shfl_up(gt, 1, 64);
-        if (lane == 0) { pe = carry_e; pr = carry_r; pg = carry_g; }
-        carry_e = (u32)__shfl((int)epoch, 63, 64);  // (of a chunk that is not full: the last one, nothing reads it)
-        carry_r = (u32)__shfl((int)round, 63, 64);
-        carry_g = __shfl(gt, 63, 64);
-        if (nv) tip_e = (u32)__shfl((int)epoch, (int)nv - 1, 64);
+        const u32 pe = cw_prev(epoch, carry_e, lane), pr = cw_prev(round, carry_r, lane);
+        const i32 pg = cw_prev(gt, carry_g, lane);
+        if (nv) tip_e = cw_tip(epoch, nv);
         const bool start = live && ep_segment_start(k, epoch, pe);
         const unsigned long long starts = __ballot(start), below = starts & ((1ull << lane) - 1ull);
         const i32 lane_first_g = __shfl(gt, (int)ep_start_lane(below), 64);
@@ -448,7 +419,7 @@ __global__ __launch_bounds__(EP_BLOCK) void lbft_k_ps_epochs(Params p, const u32
         if (starts) carry_first_g = __shfl(gt, (int)ep_highest(starts), 64);
         carry_start = ep_carry_start(starts, c0, carry_start);
         segments += (u32)__popcll(starts);
-        if (nv < inblk) L = c0 + nv;  // (ends the loop)
+        if (cw_ends(ck)) L = c0 + nv;  // (ends the loop)
       }
       if (!stat_pass) continue;
       // pool pass
@@ -458,13 +429,12 @@ __global__ __launch_bounds__(EP_BLOCK) void lbft_k_ps_epochs(Params p, const u32
         const bool have = b <= nb;
         bool off = false;
         if (have) {
-          const u32 epoch = s.bf(b, B_EPOCH), slot = vt_chain_slot(s.bf(b, B_DEPTH), L), x = ep_bin(epoch, epoch_bins);
-          const u32 at = slot < L ? s.ld(row + slot) : 0;  // (slot < L <= lcap: inside the row)
-          off = ep_stranded(vt_member(slot, L, at, b), L != 0, epoch, tip_e);
+          const u32 epoch = s.bf(b, B_EPOCH), x = ep_bin(epoch, epoch_bins);
+          off = ep_stranded(cw_pool_member(s, row, s.bf(b, B_DEPTH), L, b), L != 0, epoch, tip_e);
           ep_count(t_cnt, x, EP_COL_BLOCKS);
           if (off) ep_count(t_cnt, x, EP_COL_STRANDED);
         }
-        stranded += vt_ballot_count(off);
+        stranded += cw_ballot_count(off);
       }
       if (lane == 0) {  // one sample per instance
         ep_stat_lds(s_stat, EP_SEGMENTS, 1, segments, segments, segments); ep_stat_lds(s_stat, EP_STRANDED, 1, stranded, stranded, stranded);

@@ -13,15 +13,13 @@
 
 using namespace lbft;
 
-#include "lbft_chain_walk.h"  // the node pass
+#include "lbft_chain_walk.h"  // the node pass, the pool bound, the chunk head
 
 // One segment of W = rh_width(n) lanes per instance, 64 / W instances per wavefront, LBFT_RH_BLOCK / 64 wavefronts per workgroup; no
 // LDS, no atomics.  State is read through the generic Sim accessors (every layout).  The lanes of a segment run the same control flow;
-// every shuffle and ballot is read inside the segment only.
-//   node pass (lane = node, two rounds above 64 nodes): nc_j = min(NF_NCOMMITS, lcap); a butterfly over chn_ref_key gives the chain's
-//     length L and the reference node.
-//   then the chain in blocks of W entries (lane = entry k = c0 + lane): the lane loads its block id and, when it is one of the pool's
-//     (1 .. min(I_NBLOCKS, bcap): nothing else is ever an address), the record's fields.  The first id outside the pool ends the walk.
+// every shuffle and ballot is read inside the segment only.  Node pass and chunk head are lbft_chain_walk.h's, at the segment's width.
+//   the chain in blocks of W entries (lane = entry k = c0 + lane): a lane whose id is one of the pool's loads the record's fields.  The
+//     id that ends the walk is an entry of its own (nx = nv + 1), flagged RH_BAD_ID.
 //     state step: lane k hashes (k + 1, entries 0 .. k); the entries (author, B_CMD, B_TIME) are gathered W at a time by the segment,
 //       from the chain's start, and broadcast by __shfl.
 //     chain step, entry by entry: the values of entry k come from lane k, the block hash is computed by every lane alike, the vote
@@ -48,11 +46,9 @@ __global__ __launch_bounds__(LBFT_RH_BLOCK) void lbft_k_rh_chain(Params p, const
   if (s.ld(I_FAULT) != 0) return;
   // node pass
   u32 nc[LBFT_RH_NODE_ROUNDS];
-#pragma unroll
-  for (u32 r = 0; r < LBFT_RH_NODE_ROUNDS; r++) nc[r] = cw_commits(s, r * 64 + sl, n, lcap);
-  const CwChain ch = cw_node_pass<LBFT_RH_NODE_ROUNDS>(nc, sl, n, W);
-  const u32 L = ch.L, ref = ch.ref;  // (L <= lcap, ref < n: both from keys built from the counts)
-  const u32 nb = s.ld(I_NBLOCKS) < p.bcap ? s.ld(I_NBLOCKS) : p.bcap;
+  const CwChain ch = cw_chain_of(s, sl, n, lcap, W, nc);
+  const u32 L = ch.L, ref = ch.ref;
+  const u32 nb = cw_pool_blocks(s, p);
   const u32 row = lg + ref * lcap;
 
   u64 qc_prev = 0, st_prev = 0, st_prev2 = 0;
@@ -65,14 +61,10 @@ __global__ __launch_bounds__(LBFT_RH_BLOCK) void lbft_k_rh_chain(Params p, const
   u32 last_votes = 0, last_flags = 0;
   for (u32 c0 = 0; c0 < L; c0 += W) {
     const u32 k = c0 + sl;
-    const bool have = k < L;
-    const u32 y = have ? s.ld(row + k) : 0;
-    const bool ok = have && rh_valid_id(y, nb);
-    const u64 bad = (__ballot(have && !ok) >> seg0) & segmask;
-    const u32 inblk = L - c0 < W ? L - c0 : W;
-    const u32 jb = bad ? (u32)__builtin_ctzll(bad) : W;
-    const u32 nv = jb < inblk ? jb : inblk;  // the block's entries before the first bad id
-    const u32 nx = jb < inblk ? nv + 1 : nv;  // ... and with it
+    const CwChunk ck = cw_chunk(s, row, c0, L, nb, sl, W, seg0);
+    const u32 y = ck.y, jb = ck.jb, nv = ck.nv;
+    const bool ok = ck.have && rh_valid_id(y, nb);
+    const u32 nx = cw_ends(ck) ? nv + 1 : nv;  // the block's entries with the bad id that ends the walk
     u32 link = 0, round = 0, prev_round = 0, pp = 0, pp_round = 0, epoch = 0, cmd = 0, tm = 0;
     u32 vw[LBFT_RH_MASK_WORDS] = {};
     if (ok) {

@@ -2,29 +2,14 @@
 // kernel logic on the host (oracle/host_model_common.h; networks above 32 nodes as the run-time-generic class on the planner's own
 // capacities), then every instance's nodes, chain and block pool walked the way lbft_k_ps_epochs (csrc/lbft_paramsets.hip) walks them --
 // the node pass, the chain pass, the pool pass, the same steps in the same order over csrc/lbft_epoch_rules.h -- with the chunk width W
-// a parameter: a lane is an array element, a shuffle an index, a ballot a loop.  Every read of a block record goes through rec(), which
-// counts the reads whose id was not checked against the pool first: the walk must give 0.  The state stays in the handle, so a test can
-// edit log entries, block fields and fault words and walk again.
+// a parameter: a lane is an array element, a shuffle an index, a ballot a loop.  The model, its accessors and the shared steps of the
+// walk are tests/pool_walk_host.h's; every read of a block record goes through its counted reader: the walk must give 0.  The state
+// stays in the handle, so a test can edit log entries, block fields and fault words and walk again.
 // With -DEPM_MAIN the file is a program of its own (for a run under the address and undefined-behaviour sanitizers).
-#include <thread>
-#include <vector>
-
-#include "../oracle/host_model_common.h"
-#include "../librabft_simulator_amd/csrc/lbft_chain_rules.h"
-#include "../librabft_simulator_amd/csrc/lbft_record_hash_rules.h"
-#include "../librabft_simulator_amd/csrc/lbft_vote_rules.h"
+#include "pool_walk_host.h"
 #include "../librabft_simulator_amd/csrc/lbft_epoch_rules.h"
 
-using namespace lbft;
-
 static_assert(LBFT_EPOCH_STATS == EP_FAMILIES * 4 && LBFT_EPOCH_FAMILIES == EP_FAMILIES && LBFT_EPOCH_COLUMNS == EP_COLUMNS && LBFT_EPOCH_MAX_BINS == EP_MAX_BINS, "lbft.h");
-
-struct EpModel {
-  TwinBatch tb;
-  std::vector<u32> state;
-  size_t m;
-  int cls;
-};
 
 struct EpOut {
   u32 bin_width, bins, epoch_bins;
@@ -39,40 +24,27 @@ static void walk_instance(const Params& p, u32* state, u32 i, u32 W, EpOut& o) {
   Sim s(p, state, i);
   if (s.ld(I_FAULT) != 0) return;
   // node pass
-  u64 best = 0;
+  const CwChain ch = cw_chain_of(s, n, lcap);
   u32 e_max = 0;
-  for (u32 j = 0; j < n; j++) {
-    best = chn_ref_max(best, chn_ref_key(chn_commits(s.nfm(j, NF_NCOMMITS), lcap), j));
-    const u32 e = s.nfm(j, NF_EPOCH);
-    e_max = e > e_max ? e : e_max;
-  }
+  for (u32 j = 0; j < n; j++) e_max = s.nfm(j, NF_EPOCH) > e_max ? s.nfm(j, NF_EPOCH) : e_max;
   for (u32 j = 0; j < n; j++) { gs_stat_add(o.st[EP_NODE_EPOCH], s.nfm(j, NF_EPOCH)); gs_stat_add(o.st[EP_BEHIND], e_max - s.nfm(j, NF_EPOCH)); }
-  const u32 ref = chn_ref_node(best), row = lg + ref * lcap;
-  const u32 nb = s.ld(I_NBLOCKS) < p.bcap ? s.ld(I_NBLOCKS) : p.bcap;
-  auto rec = [&](u32 b, u32 f) -> u32 {
-    if (!rh_valid_id(b, nb)) { o.unchecked++; return 0; }
-    return s.bf(b, f);
-  };
+  const u32 row = lg + ch.ref * lcap, nb = cw_pool_blocks(s, p);
+  const CwRec rec{s, nb, o.unchecked};
   // chain pass
-  u32 L = chn_ref_len(best);
+  u32 L = ch.L;
   u32 carry_e = 0, carry_r = 0, carry_start = 0, tip_e = 0, segments = 0;
   i32 carry_g = 0, carry_first_g = 0;
-  struct Lane { u32 y, epoch, round; i32 g; bool start; };
+  struct Lane { u32 epoch, round; i32 g; bool start; };
   for (u32 c0 = 0; c0 < L; c0 += W) {
     std::vector<Lane> ln(W, Lane{});
-    const u32 inblk = L - c0 < W ? L - c0 : W;
-    u32 jb = W;
-    for (u32 sl = 0; sl < W; sl++) {
-      const u32 k = c0 + sl;
-      ln[sl].y = k < L ? s.ld(row + k) : 0;
-      if (k < L && !rh_valid_id(ln[sl].y, nb) && jb == W) jb = sl;
-    }
-    const u32 nv = jb < inblk ? jb : inblk;
+    const CwChunk ck = cw_chunk(s, row, c0, L, nb, W);
+    const u32 nv = ck.nv;
     for (u32 sl = 0; sl < nv; sl++) {
       Lane& l = ln[sl];
-      l.epoch = rec(l.y, B_EPOCH); l.round = rec(l.y, B_ROUND);
-      const u32 author = rec(l.y, B_LINK) >> 16;
-      l.g = (i32)(s.nfm(author, NF_STARTUP) + rec(l.y, B_TIME));  // cw_proposal
+      const u32 y = ck.y[sl];
+      l.epoch = rec(y, B_EPOCH); l.round = rec(y, B_ROUND);
+      const u32 author = rec(y, B_LINK) >> 16;
+      l.g = (i32)(s.nfm(author, NF_STARTUP) + rec(y, B_TIME));  // cw_proposal
     }
     u64 starts = 0;
     for (u32 sl = 0; sl < nv; sl++) {
@@ -104,89 +76,36 @@ static void walk_instance(const Params& p, u32* state, u32 i, u32 W, EpOut& o) {
     segments += (u32)__builtin_popcountll(starts);
     carry_e = ln[W - 1].epoch; carry_r = ln[W - 1].round; carry_g = ln[W - 1].g;
     if (nv) tip_e = ln[nv - 1].epoch;
-    if (nv < inblk) L = c0 + nv;
+    if (cw_ends(ck)) L = c0 + nv;
   }
   // pool pass
   u32 stranded = 0;
   for (u32 b0 = 1; b0 <= nb; b0 += W)
     for (u32 sl = 0; sl < W && b0 + sl <= nb; sl++) {
       const u32 b = b0 + sl;
-      const u32 epoch = rec(b, B_EPOCH), slot = vt_chain_slot(rec(b, B_DEPTH), L), x = ep_bin(epoch, eb);
-      const u32 at = slot < L ? s.ld(row + slot) : 0;
-      const bool off = ep_stranded(vt_member(slot, L, at, b), L != 0, epoch, tip_e);
+      const u32 epoch = rec(b, B_EPOCH), x = ep_bin(epoch, eb);
+      const bool off = ep_stranded(cw_pool_member(s, row, rec(b, B_DEPTH), L, b), L != 0, epoch, tip_e);
       o.table[ep_cell(x, EP_COL_BLOCKS)]++;
       if (off) { o.table[ep_cell(x, EP_COL_STRANDED)]++; stranded++; }
     }
   gs_stat_add(o.st[EP_SEGMENTS], segments); gs_stat_add(o.st[EP_STRANDED], stranded); gs_stat_add(o.st[EP_BLOCKS], nb);
 }
 
-// Networks above 32 nodes: the planner's capacities for a run to max_clock without the calendar queue, stepped as the generic class.
-static int setup_large(const lbft_config* base, size_t m, int64_t max_clock, TwinBatch& t) {
-  lbft_config c = *base;
-  c.queue_capacity = c.snapshot_capacity = c.block_capacity = c.log_capacity = 0;
-  Params& p = t.p;
-  if (fill_params(&c, m, p, t.weights) != LBFT_OK) return -1;
-  p.weights = t.weights.data();
-  bool relayout;
-  std::string err;
-  if (plan_layout(c, p, max_clock, 0, false, false, 0, ~0ull, PlanKnobs(), false, relayout, err) != LBFT_OK) return -1;
-  attach_tables(p, c.delta, c.gamma, t.dur, t.leaders);
-  p.ql = 0;
-  set_tile_width(p, layout_tile_width(p));
-  return K_GENERIC;
-}
-
 extern "C" {
 
-// A plain batch of `base` run to max_clock; NULL on a bad argument.  info: num_nodes, log capacity, block capacity, kernel class.
-void* epm_create(const lbft_config* base, const uint64_t* seeds, size_t m, int64_t max_clock, uint32_t threads, uint32_t* info) {
-  const u32 n = base->num_nodes;
-  if (n == 0 || n > LBFT_MAX_NODES) return nullptr;
-  EpModel* h = new EpModel;
-  h->m = m;
-  h->cls = n <= 32 ? setup_twin_batch(base, nullptr, 0, (base->quirks & 1u) ? 0 : (16 * n < 64 ? 64 : 16 * n), m, max_clock, h->tb) : setup_large(base, m, max_clock, h->tb);
-  if (h->cls < 0) { delete h; return nullptr; }
-  const Params& p = h->tb.p;
-  h->state.assign(state_words(p), 0);
-  if (threads == 0) threads = 1;
-  auto worker = [&](u32 tid) {
-    for (size_t i = tid; i < m; i += threads) {
-      { Sim s0(p, h->state.data(), (u32)i); s0.init(seeds[i]); }
-      if (h->cls == K_SMALL) { SimT<K_SMALL> s(p, h->state.data(), (u32)i); run_one(s, p, 0); }
-      else if (h->cls == K_MID) { SimT<K_MID> s(p, h->state.data(), (u32)i); run_one(s, p, 0); }
-      else { Sim s(p, h->state.data(), (u32)i); run_one(s, p, 0); }
-    }
-  };
-  std::vector<std::thread> ts;
-  for (u32 t = 1; t < threads; t++) ts.emplace_back(worker, t);
-  worker(0);
-  for (auto& t : ts) t.join();
-  if (info) { info[0] = n; info[1] = p.lcap; info[2] = p.bcap; info[3] = (u32)h->cls; }
-  return h;
-}
-void epm_destroy(void* handle) { delete static_cast<EpModel*>(handle); }
-
-// commit_counts [m][n] (as stored, not clamped), faults [m], nblocks [m], startup [m][n], epochs [m][n]
-void epm_counts(void* handle, uint32_t* commit_counts, uint32_t* faults, uint32_t* nblocks, int32_t* startup, uint32_t* epochs) {
-  EpModel* h = static_cast<EpModel*>(handle);
-  const Params& p = h->tb.p;
-  for (size_t i = 0; i < h->m; i++) {
-    Sim s(p, h->state.data(), (u32)i);
-    faults[i] = s.ld(I_FAULT);
-    nblocks[i] = s.ld(I_NBLOCKS);
-    for (u32 q = 0; q < p.n; q++) {
-      commit_counts[i * p.n + q] = s.nfm(q, NF_NCOMMITS);
-      startup[i * p.n + q] = (i32)s.nfm(q, NF_STARTUP);
-      epochs[i * p.n + q] = s.nfm(q, NF_EPOCH);
-    }
-  }
-}
+void* epm_create(const lbft_config* base, const uint64_t* seeds, size_t m, int64_t max_clock, uint32_t threads, uint32_t* info) { return pw_create(base, seeds, m, max_clock, threads, info, true); }
+void epm_destroy(void* handle) { pw_destroy(handle); }
+void epm_counts(void* handle, uint32_t* commit_counts, uint32_t* faults, uint32_t* nblocks, int32_t* startup, uint32_t* epochs) { pw_counts(handle, commit_counts, faults, nblocks, startup, epochs); }
+void epm_chain(void* handle, uint32_t inst, uint32_t* ref, uint32_t* length) { pw_chain(handle, inst, ref, length); }
+uint32_t epm_log(void* handle, uint32_t inst, uint32_t node, uint32_t k, int set, uint32_t value) { return pw_log(handle, inst, node, k, set, value); }
+void epm_set_fault(void* handle, uint32_t inst, uint32_t value) { pw_set_fault(handle, inst, value); }
+uint32_t epm_block(void* handle, uint32_t inst, uint32_t b, uint32_t what, int set, uint32_t value) { return pw_block(handle, inst, b, what, set, value); }
 
 // Every instance walked in chunks of W lanes (1 .. 64), one group: hist [bins], table [epoch_bins * 7], stats [40], all zeroed here
 // first.  check[0] = block-record reads with an unchecked id (0 is right).  -> 0, < 0 on a bad argument
 int epm_walk(void* handle, uint32_t W, uint32_t bin_width, uint32_t bins, uint32_t epoch_bins, uint64_t* hist, uint64_t* table, uint64_t* stats,
              uint64_t* check) {
-  EpModel* h = static_cast<EpModel*>(handle);
+  PwModel* h = static_cast<PwModel*>(handle);
   if (!h || W == 0 || W > 64 || bin_width == 0 || bins == 0 || epoch_bins == 0 || epoch_bins > EP_MAX_BINS || !hist || !table || !stats || !check) return -1;
   const Params& p = h->tb.p;
   EpOut o = {};
@@ -200,41 +119,6 @@ int epm_walk(void* handle, uint32_t W, uint32_t bin_width, uint32_t bins, uint32
   }
   check[0] = o.unchecked;
   return 0;
-}
-
-// The reference node and the clamped chain length of an instance (the node pass)
-void epm_chain(void* handle, uint32_t inst, uint32_t* ref, uint32_t* length) {
-  EpModel* h = static_cast<EpModel*>(handle);
-  const Params& p = h->tb.p;
-  Sim s(p, h->state.data(), inst);
-  u64 best = 0;
-  for (u32 j = 0; j < p.n; j++) best = chn_ref_max(best, chn_ref_key(chn_commits(s.nfm(j, NF_NCOMMITS), p.lcap), j));
-  *ref = chn_ref_node(best); *length = chn_ref_len(best);
-}
-// Entry k of a node's log: returns it, and stores `value` there when `set` is not 0
-uint32_t epm_log(void* handle, uint32_t inst, uint32_t node, uint32_t k, int set, uint32_t value) {
-  EpModel* h = static_cast<EpModel*>(handle);
-  const Params& p = h->tb.p;
-  Sim s(p, h->state.data(), inst);
-  const u32 w = p.off_log + node * p.lcap + k;
-  const u32 old = s.ld(w);
-  if (set) s.st(w, value);
-  return old;
-}
-void epm_set_fault(void* handle, uint32_t inst, uint32_t value) {
-  EpModel* h = static_cast<EpModel*>(handle);
-  Sim s(h->tb.p, h->state.data(), inst);
-  s.st(I_FAULT, value);
-}
-// A field of pool block b (1 .. block count; what: 0 epoch, 1 round, 2 author, 3 time, 4 ledger depth): returns it, and stores `value`
-// there when `set` is not 0 (epoch, round and time only)
-uint32_t epm_block(void* handle, uint32_t inst, uint32_t b, uint32_t what, int set, uint32_t value) {
-  EpModel* h = static_cast<EpModel*>(handle);
-  Sim s(h->tb.p, h->state.data(), inst);
-  const u32 f = what == 0 ? (u32)B_EPOCH : what == 1 ? (u32)B_ROUND : what == 2 ? (u32)B_LINK : what == 3 ? (u32)B_TIME : (u32)B_DEPTH;
-  const u32 old = s.bf(b, f);
-  if (set && what != 2 && what != 4) s.bfs(b, f, value);
-  return what == 2 ? old >> 16 : old;
 }
 
 }  // extern "C"

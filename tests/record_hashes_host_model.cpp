@@ -3,24 +3,11 @@
 // way lbft_k_rh_chain (csrc/lbft_record_hashes.hip) walks it -- a segment of W lanes, the chain in blocks of W entries, the same steps
 // in the same order with csrc/lbft_record_hash_rules.h -- with W a parameter: a lane is an array element, a shuffle an index, a ballot a
 // loop.  (The kernel takes W >= n, up to two rounds of 64; here nodes and authors take as many rounds of W as they need, so any power of
-// two walks any network.)  Every read of a block record goes through rec(), which counts the reads whose id was not checked against the
-// pool first: the walk must give 0.  The state stays in the handle, so a test can edit log entries and fault words and walk again.
+// two walks any network.)  The model, its accessors and the shared steps of the walk are tests/pool_walk_host.h's; every read of a block
+// record goes through its counted reader: the walk must give 0.  The state stays in the handle, so a test can edit log entries and fault
+// words and walk again.
 // With -DRHM_MAIN the file is a program of its own (for a run under the address and undefined-behaviour sanitizers).
-#include <thread>
-#include <vector>
-
-#include "../oracle/host_model_common.h"
-#include "../librabft_simulator_amd/csrc/lbft_chain_rules.h"
-#include "../librabft_simulator_amd/csrc/lbft_record_hash_rules.h"
-
-using namespace lbft;
-
-struct RhModel {
-  TwinBatch tb;
-  std::vector<u32> state;
-  size_t m;
-  int cls;
-};
+#include "pool_walk_host.h"
 
 // One instance, as one segment of the kernel.  -> reads of block records with an unchecked id
 static u64 walk_instance(const Params& p, u32* state, u32 i, u32 W, lbft_record_hash* out, size_t cap, lbft_chain_head* head, u32* node_prefix) {
@@ -30,46 +17,25 @@ static u64 walk_instance(const Params& p, u32* state, u32 i, u32 W, lbft_record_
   u64 unchecked = 0;
   const u32 rounds = (n + W - 1) / W;
   // node pass
-  std::vector<u32> nc((size_t)rounds * W, 0);
-  std::vector<u64> key(W, 0);
-  for (u32 r = 0; r < rounds; r++)
-    for (u32 sl = 0; sl < W; sl++) {
-      const u32 j = r * W + sl;
-      if (j >= n) continue;
-      nc[j] = chn_commits(s.nfm(j, NF_NCOMMITS), lcap);
-      key[sl] = chn_ref_max(key[sl], chn_ref_key(nc[j], j));
-    }
-  for (u32 d = W >> 1; d; d >>= 1) {
-    std::vector<u64> next(W);
-    for (u32 sl = 0; sl < W; sl++) next[sl] = chn_ref_max(key[sl], key[sl ^ d]);
-    key = next;
-  }
-  const u32 L = chn_ref_len(key[0]), ref = chn_ref_node(key[0]);
-  const u32 nb = s.ld(I_NBLOCKS) < p.bcap ? s.ld(I_NBLOCKS) : p.bcap;
-  const u32 row = lg + ref * lcap;
-  auto rec = [&](u32 b, u32 f) -> u32 {
-    if (!rh_valid_id(b, nb)) { unchecked++; return 0; }
-    return s.bf(b, f);
-  };
+  std::vector<u32> nc(n, 0);
+  for (u32 j = 0; j < n; j++) nc[j] = chn_commits(s.nfm(j, NF_NCOMMITS), lcap);
+  const CwChain ch = cw_chain_of(s, n, lcap);
+  const u32 L = ch.L, ref = ch.ref, nb = cw_pool_blocks(s, p), row = lg + ref * lcap;
+  const CwRec rec{s, nb, unchecked};
   u64 qc_prev = 0, st_prev = 0, st_prev2 = 0;
   u32 y_prev = 0, y_prev2 = 0;
-  std::vector<u32> pfx((size_t)rounds * W, 0xffffffffu);
+  std::vector<u32> pfx(n, 0xffffffffu);
   u32 Lw = L;
   lbft_record_hash last = {};
   struct Lane { u32 y, link, round, prev_round, pp, pp_round, epoch, cmd, tm, vw[LBFT_MAX_NODES / 32]; bool ok; u64 state; lbft_record_hash mine; };
   for (u32 c0 = 0; c0 < L; c0 += W) {
     std::vector<Lane> ln(W, Lane{});
-    u64 bad = 0;
+    const CwChunk ck = cw_chunk(s, row, c0, L, nb, W);
+    const u32 jb = ck.jb, nv = ck.nv, nx = cw_ends(ck) ? nv + 1 : nv;
     for (u32 sl = 0; sl < W; sl++) {
-      const u32 k = c0 + sl;
-      const bool have = k < L;
-      ln[sl].y = have ? s.ld(row + k) : 0;
-      ln[sl].ok = have && rh_valid_id(ln[sl].y, nb);
-      if (have && !ln[sl].ok) bad |= 1ull << sl;
+      ln[sl].y = ck.y[sl];
+      ln[sl].ok = c0 + sl < L && rh_valid_id(ck.y[sl], nb);
     }
-    const u32 inblk = L - c0 < W ? L - c0 : W;
-    const u32 jb = bad ? (u32)__builtin_ctzll(bad) : W;
-    const u32 nv = jb < inblk ? jb : inblk, nx = jb < inblk ? nv + 1 : nv;
     for (u32 sl = 0; sl < W; sl++) {
       Lane& l = ln[sl];
       if (!l.ok) continue;
@@ -156,48 +122,16 @@ static u64 walk_instance(const Params& p, u32* state, u32 i, u32 W, lbft_record_
 
 extern "C" {
 
-// A plain batch of `base` run to max_clock; NULL on a bad argument.  info: num_nodes, log capacity, block capacity, kernel class.
-void* rhm_create(const lbft_config* base, const uint64_t* seeds, size_t m, int64_t max_clock, uint32_t threads, uint32_t* info) {
-  const u32 n = base->num_nodes;
-  RhModel* h = new RhModel;
-  h->m = m;
-  h->cls = setup_twin_batch(base, nullptr, 0, (base->quirks & 1u) ? 0 : (16 * n < 64 ? 64 : 16 * n), m, max_clock, h->tb);
-  if (h->cls < 0) { delete h; return nullptr; }
-  const Params& p = h->tb.p;
-  h->state.assign(state_words(p), 0);
-  if (threads == 0) threads = 1;
-  auto worker = [&](u32 tid) {
-    for (size_t i = tid; i < m; i += threads) {
-      { Sim s0(p, h->state.data(), (u32)i); s0.init(seeds[i]); }
-      if (h->cls == K_SMALL) { SimT<K_SMALL> s(p, h->state.data(), (u32)i); run_one(s, p, 0); }
-      else { SimT<K_MID> s(p, h->state.data(), (u32)i); run_one(s, p, 0); }
-    }
-  };
-  std::vector<std::thread> ts;
-  for (u32 t = 1; t < threads; t++) ts.emplace_back(worker, t);
-  worker(0);
-  for (auto& t : ts) t.join();
-  if (info) { info[0] = n; info[1] = p.lcap; info[2] = p.bcap; info[3] = (u32)h->cls; }
-  return h;
-}
-void rhm_destroy(void* handle) { delete static_cast<RhModel*>(handle); }
-
-// commit_counts [m][n] (as stored, not clamped), faults [m], nblocks [m]
-void rhm_counts(void* handle, uint32_t* commit_counts, uint32_t* faults, uint32_t* nblocks) {
-  RhModel* h = static_cast<RhModel*>(handle);
-  const Params& p = h->tb.p;
-  for (size_t i = 0; i < h->m; i++) {
-    Sim s(p, h->state.data(), (u32)i);
-    faults[i] = s.ld(I_FAULT);
-    nblocks[i] = s.ld(I_NBLOCKS);
-    for (u32 q = 0; q < p.n; q++) commit_counts[i * p.n + q] = s.nfm(q, NF_NCOMMITS);
-  }
-}
+void* rhm_create(const lbft_config* base, const uint64_t* seeds, size_t m, int64_t max_clock, uint32_t threads, uint32_t* info) { return pw_create(base, seeds, m, max_clock, threads, info, false); }
+void rhm_destroy(void* handle) { pw_destroy(handle); }
+void rhm_counts(void* handle, uint32_t* commit_counts, uint32_t* faults, uint32_t* nblocks) { pw_counts(handle, commit_counts, faults, nblocks, nullptr, nullptr); }
+uint32_t rhm_log(void* handle, uint32_t inst, uint32_t node, uint32_t k, int set, uint32_t value) { return pw_log(handle, inst, node, k, set, value); }
+void rhm_set_fault(void* handle, uint32_t inst, uint32_t value) { pw_set_fault(handle, inst, value); }
 
 // Every instance walked with segments of W lanes (a power of two, 1 .. 64): out [m][cap] (may be NULL), heads [m], node_prefix [m][n]
 // (may be NULL), all zeroed here first.  -> the number of block-record reads with an unchecked id (0 is right), < 0 on a bad argument
 int64_t rhm_walk(void* handle, uint32_t W, lbft_record_hash* out, size_t cap, lbft_chain_head* heads, uint32_t* node_prefix) {
-  RhModel* h = static_cast<RhModel*>(handle);
+  PwModel* h = static_cast<PwModel*>(handle);
   if (!h || !heads || W == 0 || W > 64 || (W & (W - 1)) || (out && cap == 0)) return -1;
   const Params& p = h->tb.p;
   u64 unchecked = 0;
@@ -212,29 +146,12 @@ int64_t rhm_walk(void* handle, uint32_t W, lbft_record_hash* out, size_t cap, lb
 
 // SimT::committed_record_hashes of one node (what lbft_batch_committed_record_hashes runs) -> its commit count
 uint32_t rhm_node(void* handle, uint32_t inst, uint32_t node, lbft_record_hash* out, uint32_t cap) {
-  RhModel* h = static_cast<RhModel*>(handle);
-  Sim s(h->tb.p, h->state.data(), inst);
+  Sim s = pw_sim(handle, inst);
   std::vector<u64> raw((size_t)4 * (cap ? cap : 1));
   const u32 nc = s.committed_record_hashes(node, raw.data(), cap);
   for (u32 k = 0; k < nc && k < cap; k++)
     out[k] = lbft_record_hash{raw[4 * k], raw[4 * k + 1], raw[4 * k + 2], (uint32_t)raw[4 * k + 3], (uint32_t)(raw[4 * k + 3] >> 32)};
   return nc;
-}
-
-// Entry k of a node's log: returns it, and stores `value` there when `set` is not 0
-uint32_t rhm_log(void* handle, uint32_t inst, uint32_t node, uint32_t k, int set, uint32_t value) {
-  RhModel* h = static_cast<RhModel*>(handle);
-  const Params& p = h->tb.p;
-  Sim s(p, h->state.data(), inst);
-  const u32 w = p.off_log + node * p.lcap + k;
-  const u32 old = s.ld(w);
-  if (set) s.st(w, value);
-  return old;
-}
-void rhm_set_fault(void* handle, uint32_t inst, uint32_t value) {
-  RhModel* h = static_cast<RhModel*>(handle);
-  Sim s(h->tb.p, h->state.data(), inst);
-  s.st(I_FAULT, value);
 }
 
 }  // extern "C"

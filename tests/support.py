@@ -66,6 +66,17 @@ def plain(amd, seeds, n, ps, **kw):
                                   partition=ps.partition, **kw)
 
 
+def device_batch(amd, kw, seeds, **extra):
+    """The plain device batch of an oracle configuration `kw` (the reference CLI defaults for everything else)."""
+    kw = dict(kw)
+    n = kw.pop("num_nodes")
+    delay = amd.RandomDelay.new(kw.pop("mean", 10.0), kw.pop("variance", 4.0))
+    node = amd.NodeConfig(kw.pop("target_commit_interval", 100000), kw.pop("delta", 20), 2.0, 0.5)
+    part = (kw.pop("partition_size"), kw.pop("partition_start"), kw.pop("partition_end")) if "partition_size" in kw else None
+    ps = amd.ParamSet(delay, node, drop_per_million=kw.pop("drop_per_million", 0), partition=part)
+    return plain(amd, np.asarray(list(seeds), dtype=np.uint64), n, ps, **kw, **extra)
+
+
 def binning(max_clock, width, bins):
     """latency_histogram's defaults: width 1 up to 65 536 bins, above that the smallest width that fits."""
     span = max_clock + 1
@@ -173,3 +184,69 @@ def build_shim(tmp_dir, source, name, *extra_flags):
     out = str(tmp_dir / name)
     subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", *extra_flags, os.path.join(TESTS, source), "-o", out])
     return ctypes.CDLL(out)
+
+
+def build_pool_walk_shim(tmp_dir, source, name, prefix):
+    """A host model over tests/pool_walk_host.h (symbol prefix `prefix`: vtm, epm, rhm) with the accessors they share bound; the caller
+    binds its own walk and counts."""
+    L = build_shim(tmp_dir, source, name, "-ffp-contract=off", "-pthread", "-w")
+    vp, u32 = ctypes.c_void_p, ctypes.c_uint32
+    sym = lambda what: getattr(L, "%s_%s" % (prefix, what))
+    sym("create").argtypes, sym("create").restype = [vp, vp, ctypes.c_size_t, ctypes.c_int64, u32, vp], vp
+    sym("destroy").argtypes = [vp]
+    sym("log").argtypes, sym("log").restype = [vp, u32, u32, u32, ctypes.c_int, u32], u32
+    sym("set_fault").argtypes = [vp, u32, u32]
+    if prefix != "rhm":
+        sym("chain").argtypes = [vp, u32, vp, vp]
+    L.pw_chain_entries.argtypes, L.pw_chain_entries.restype = [vp, u32, u32, vp, u32, vp], u32
+    L.pw_cut.argtypes = [vp, u32, u32]
+    return L
+
+
+class ModelBase:
+    """A plain batch run on the host and kept in a handle of a pool-walk shim: the configuration (the reference CLI defaults, `kw` on
+    top), the accessors the three models share.  A subclass sets PREFIX and WIDTHS and has its own walk and counts."""
+    PREFIX, WIDTHS = None, (1, 7, 64)
+
+    def __init__(self, L, kw, max_clock, seeds):
+        from librabft_simulator_amd import _lib
+        self.L, self.max_clock = L, max_clock
+        cfg = _lib.LbftConfig()
+        defaults = dict(mean=10.0, variance=4.0, commands_per_epoch=30000, target_commit_interval=100000, delta=20, gamma=2.0, lambda_=0.5)
+        for k, v in {**defaults, **kw}.items():
+            if k == "voting_rights":
+                self._rights = np.ascontiguousarray(v, dtype=np.uint64)
+                cfg.voting_rights = self._rights.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+            else:
+                setattr(cfg, k, v)
+        info = np.zeros(4, dtype=np.uint32)
+        seeds = np.ascontiguousarray(list(seeds), dtype=np.uint64)
+        self.h = self.sym("create")(ctypes.byref(cfg), seeds.ctypes.data, len(seeds), max_clock, 4, info.ctypes.data)
+        assert self.h, "the host model refused the configuration"
+        self.m = len(seeds)
+        self.n, self.lcap, self.bcap, self.cls = (int(x) for x in info)
+        self.rights = kw.get("voting_rights")
+
+    def sym(self, what):
+        return getattr(self.L, "%s_%s" % (self.PREFIX, what))
+
+    def chain(self, i):
+        r, length = ctypes.c_uint32(), ctypes.c_uint32()
+        self.sym("chain")(self.h, i, ctypes.byref(r), ctypes.byref(length))
+        return r.value, length.value
+
+    def log(self, i, q, k, value=None):
+        return self.sym("log")(self.h, i, q, k, 0 if value is None else 1, 0 if value is None else value)
+
+    def set_fault(self, i, value):
+        self.sym("set_fault")(self.h, i, value)
+
+    def same_for_every_width(self, **kw):
+        got = [self.walk(W, **kw) for W in self.WIDTHS]
+        for other in got[1:]:
+            for a, b in zip(got[0], other):
+                assert a.tobytes() == b.tobytes()
+        return got[0]
+
+    def close(self):
+        self.sym("destroy")(self.h)

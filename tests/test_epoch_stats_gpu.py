@@ -17,24 +17,13 @@ import pytest
 import edge_cases
 import epoch_stats_cases as cases
 import epoch_stats_reference as ref
-from support import amd, oracle_cfg, plain, same  # noqa: F401
+from support import amd, device_batch, oracle_cfg, plain, same  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 pytestmark = pytest.mark.gpu
 BINNINGS = ((None, None), (7, 5))
 CPE5 = dict(cases.Q3, commands_per_epoch=5)
-
-
-def device_batch(amd, kw, seeds, **extra):
-    """The plain device batch of an oracle configuration `kw` (the reference CLI defaults for everything else)."""
-    kw = dict(kw)
-    n = kw.pop("num_nodes")
-    delay = amd.RandomDelay.new(kw.pop("mean", 10.0), kw.pop("variance", 4.0))
-    node = amd.NodeConfig(kw.pop("target_commit_interval", 100000), kw.pop("delta", 20), 2.0, 0.5)
-    part = (kw.pop("partition_size"), kw.pop("partition_start"), kw.pop("partition_end")) if "partition_size" in kw else None
-    ps = amd.ParamSet(delay, node, drop_per_million=kw.pop("drop_per_million", 0), partition=part)
-    return plain(amd, np.asarray(list(seeds), dtype=np.uint64), n, ps, **kw, **extra)
 
 
 def check(res, instances, max_clock, epoch_bins=64, binnings=BINNINGS, **groups):

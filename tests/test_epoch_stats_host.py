@@ -15,51 +15,31 @@ import pytest
 
 import epoch_stats_cases as cases
 import epoch_stats_reference as ref
-from support import build_shim
+from support import ModelBase, build_pool_walk_shim
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "epoch_stats_host_model.cpp")
-WIDTHS = (1, 7, 64)
 EPOCH, ROUND, AUTHOR, TIME, DEPTH = range(5)  # epm_block's `what`
 
 
-@pytest.fixture(scope="module")
-def shim(tmp_path_factory):
-    L = build_shim(tmp_path_factory.mktemp("ep_host"), "epoch_stats_host_model.cpp", "libep_hostmodel.so", "-ffp-contract=off", "-pthread", "-w")
+def load_shim(tmp_dir):
+    L = build_pool_walk_shim(tmp_dir, "epoch_stats_host_model.cpp", "libep_hostmodel.so", "epm")
     vp, u32 = C.c_void_p, C.c_uint32
-    L.epm_create.argtypes = [vp, vp, C.c_size_t, C.c_int64, u32, vp]
-    L.epm_create.restype = vp
-    L.epm_destroy.argtypes = [vp]
     L.epm_counts.argtypes = [vp, vp, vp, vp, vp, vp]
     L.epm_walk.argtypes = [vp, u32, u32, u32, u32, vp, vp, vp, vp]
     L.epm_walk.restype = C.c_int
-    L.epm_chain.argtypes = [vp, u32, vp, vp]
-    L.epm_log.argtypes = [vp, u32, u32, u32, C.c_int, u32]
-    L.epm_log.restype = u32
-    L.epm_set_fault.argtypes = [vp, u32, u32]
     L.epm_block.argtypes = [vp, u32, u32, u32, C.c_int, u32]
     L.epm_block.restype = u32
     return L
 
 
-class Model:
-    def __init__(self, L, kw, max_clock, seeds):
-        from librabft_simulator_amd import _lib
-        self.L, self.max_clock = L, max_clock
-        cfg = _lib.LbftConfig()
-        defaults = dict(mean=10.0, variance=4.0, commands_per_epoch=30000, target_commit_interval=100000, delta=20, gamma=2.0, lambda_=0.5)
-        for k, v in {**defaults, **kw}.items():
-            if k == "voting_rights":
-                self._rights = np.ascontiguousarray(v, dtype=np.uint64)
-                cfg.voting_rights = self._rights.ctypes.data_as(C.POINTER(C.c_uint64))
-            else:
-                setattr(cfg, k, v)
-        info = np.zeros(4, dtype=np.uint32)
-        seeds = np.ascontiguousarray(list(seeds), dtype=np.uint64)
-        self.h = L.epm_create(C.byref(cfg), seeds.ctypes.data, len(seeds), max_clock, 4, info.ctypes.data)
-        assert self.h, "the host model refused the configuration"
-        self.m = len(seeds)
-        self.n, self.lcap, self.bcap, self.cls = (int(x) for x in info)
+@pytest.fixture(scope="module")
+def shim(tmp_path_factory):
+    return load_shim(tmp_path_factory.mktemp("ep_host"))
+
+
+class Model(ModelBase):
+    PREFIX = "epm"
 
     def counts(self):
         cc, faults, nblocks = np.zeros((self.m, self.n), dtype=np.uint32), np.zeros(self.m, dtype=np.uint32), np.zeros(self.m, dtype=np.uint32)
@@ -76,14 +56,6 @@ class Model:
         assert self.L.epm_walk(self.h, W, width, bins, epoch_bins, hist.ctypes.data, table.ctypes.data, stats.ctypes.data, check.ctypes.data) == 0
         assert check[0] == 0, "the walk read %d block records whose id it had not checked" % check[0]
         return hist, table, stats
-
-    def chain(self, i):
-        r, length = C.c_uint32(), C.c_uint32()
-        self.L.epm_chain(self.h, i, C.byref(r), C.byref(length))
-        return r.value, length.value
-
-    def log(self, i, q, k, value=None):
-        return self.L.epm_log(self.h, i, q, k, 0 if value is None else 1, 0 if value is None else value)
 
     def block(self, i, b, what, value=None):
         return self.L.epm_block(self.h, i, b, what, 0 if value is None else 1, 0 if value is None else value)
@@ -112,17 +84,6 @@ class Model:
     def expected(self, width=None, bins=None, epoch_bins=64):
         instances, faults = self.instances()
         return cases.expected(instances, self.max_clock, epoch_bins, width, bins, faults=faults), instances
-
-    def close(self):
-        self.L.epm_destroy(self.h)
-
-
-def same_for_every_width(model, **kw):
-    got = [model.walk(W, **kw) for W in WIDTHS]
-    for other in got[1:]:
-        for a, b in zip(got[0], other):
-            assert a.tobytes() == b.tobytes()
-    return got[0]
 
 
 def equal(got, want):
@@ -174,7 +135,7 @@ def test_walk_equals_the_reference_for_every_width(shim, oracle, name):
     assert epochs.tolist() == [i["node_epochs"] for i in instances]
     lengths, with_chain = sum(i["length"] for i in instances), sum(1 for i in instances if i["length"])
     for width, bins in ((None, None), (7, 5)):
-        got = same_for_every_width(model, width=width, bins=bins, epoch_bins=epoch_bins)
+        got = model.same_for_every_width(width=width, bins=bins, epoch_bins=epoch_bins)
         equal(got, cases.expected(instances, max_clock, epoch_bins, width, bins))
         equal(got, model.expected(width, bins, epoch_bins)[0])  # (the read-back of the hand-edit tests gives the same)
         ref.identities(*got, lengths_sum=[lengths], with_chain=[with_chain])
@@ -194,9 +155,9 @@ def test_ids_outside_the_pool_end_the_chain_and_its_open_segment(shim):
         nb = int(model.counts()[2][0])
         r, length = model.chain(0)
         assert length > 71
-        _, table0, stats0 = same_for_every_width(model)
+        _, table0, stats0 = model.same_for_every_width()
         model.log(0, r, k, nb + 1 if value is None else value)
-        got = same_for_every_width(model)  # (asserts: no read of an unchecked record, for every width)
+        got = model.same_for_every_width()  # (asserts: no read of an unchecked record, for every width)
         want, _ = model.expected()
         equal(got, want)
         hist, table, stats = got
@@ -218,7 +179,7 @@ def test_decreasing_and_huge_epochs_still_give_maximal_runs(shim):
         model.block(0, ids[k], EPOCH, 0)
     model.block(0, ids[20], EPOCH, 1 << 31)  # ... 3 x 5 | 2^31 | 4 4 4 4 | 5
     for epoch_bins in (64, 3, 512):
-        got = same_for_every_width(model, epoch_bins=epoch_bins)
+        got = model.same_for_every_width(epoch_bins=epoch_bins)
         want, instances = model.expected(epoch_bins=epoch_bins)
         equal(got, want)
         ref.identities(*got, lengths_sum=[26 + model.chain(1)[1]], with_chain=[2])
@@ -235,9 +196,9 @@ def test_a_faulted_instance_is_skipped(shim, oracle):
     seeds = list(seeds)[:3]
     model = Model(shim, kw, max_clock, seeds)
     instances = cases.oracle_instances(oracle, kw, max_clock, seeds)
-    equal(same_for_every_width(model), cases.expected(instances, max_clock))
+    equal(model.same_for_every_width(), cases.expected(instances, max_clock))
     model.L.epm_set_fault(model.h, 1, 1 << 3)
-    got = same_for_every_width(model)
+    got = model.same_for_every_width()
     equal(got, cases.expected(instances, max_clock, faults=[0, 8, 0]))
     assert got[2][0, 4 * ref.BLOCKS] == 2 and got[2][0, 4 * ref.NODE_EPOCH] == 8
     model.close()
@@ -253,7 +214,7 @@ def test_sums_of_times_past_2_to_the_32_stay_exact(shim):
             r, length = model.chain(i)
             for k in range(length):
                 model.block(i, model.log(i, r, k), TIME, (1 << 30) - 1000 + k if hot(k) else 0)
-        got = same_for_every_width(model, width=1 << 20, bins=2048)
+        got = model.same_for_every_width(width=1 << 20, bins=2048)
         want, _ = model.expected(1 << 20, 2048)
         equal(got, want)
         hist, table, stats = got

@@ -12,11 +12,10 @@ import subprocess
 import numpy as np
 import pytest
 
-from support import build_shim
+from support import ModelBase, build_pool_walk_shim
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "record_hashes_host_model.cpp")
-WIDTHS = (4, 8, 64)
 HEAD_DTYPE = np.dtype([("block_hash", "<u8"), ("state", "<u8"), ("qc_hash", "<u8"), ("length", "<u4"), ("ref_node", "<u4"),
                        ("num_votes", "<u4"), ("flags", "<u4")])
 SEEDS = np.array([52, 7, 1234567], dtype=np.uint64)
@@ -33,40 +32,21 @@ BAD_ID = 4
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    L = build_shim(tmp_path_factory.mktemp("rh_host"), "record_hashes_host_model.cpp", "librh_hostmodel.so", "-ffp-contract=off", "-pthread", "-w")
+    L = build_pool_walk_shim(tmp_path_factory.mktemp("rh_host"), "record_hashes_host_model.cpp", "librh_hostmodel.so", "rhm")
     vp, u32 = C.c_void_p, C.c_uint32
-    L.rhm_create.argtypes = [vp, vp, C.c_size_t, C.c_int64, u32, vp]
-    L.rhm_create.restype = vp
-    L.rhm_destroy.argtypes = [vp]
     L.rhm_counts.argtypes = [vp, vp, vp, vp]
     L.rhm_walk.argtypes = [vp, u32, vp, C.c_size_t, vp, vp]
     L.rhm_walk.restype = C.c_int64
     L.rhm_node.argtypes = [vp, u32, u32, vp, u32]
     L.rhm_node.restype = u32
-    L.rhm_log.argtypes = [vp, u32, u32, u32, C.c_int, u32]
-    L.rhm_log.restype = u32
-    L.rhm_set_fault.argtypes = [vp, u32, u32]
     return L
 
 
-class Model:
+class Model(ModelBase):
+    PREFIX, WIDTHS = "rhm", (4, 8, 64)
+
     def __init__(self, L, kw, max_clock, seeds=SEEDS):
-        from librabft_simulator_amd import _lib
-        self.L = L
-        cfg = _lib.LbftConfig()
-        defaults = dict(mean=10.0, variance=4.0, commands_per_epoch=30000, target_commit_interval=100000, delta=20, gamma=2.0, lambda_=0.5)
-        for k, v in {**defaults, **kw}.items():
-            if k == "voting_rights":
-                self._rights = np.ascontiguousarray(v, dtype=np.uint64)
-                cfg.voting_rights = self._rights.ctypes.data_as(C.POINTER(C.c_uint64))
-            else:
-                setattr(cfg, k, v)
-        info = np.zeros(4, dtype=np.uint32)
-        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
-        self.h = L.rhm_create(C.byref(cfg), seeds.ctypes.data, len(seeds), max_clock, 4, info.ctypes.data)
-        assert self.h, "the host model refused the configuration"
-        self.m = len(seeds)
-        self.n, self.lcap, self.bcap, self.cls = (int(x) for x in info)
+        super().__init__(L, kw, max_clock, seeds)
 
     def counts(self):
         cc = np.zeros((self.m, self.n), dtype=np.uint32)
@@ -93,20 +73,6 @@ class Model:
         nc = self.L.rhm_node(self.h, i, q, out.ctypes.data, self.lcap)
         return out[:min(nc, self.lcap)]
 
-    def log(self, i, q, k, value=None):
-        return self.L.rhm_log(self.h, i, q, k, 0 if value is None else 1, 0 if value is None else value)
-
-    def close(self):
-        self.L.rhm_destroy(self.h)
-
-
-def same_for_every_width(model, **kw):
-    got = [model.walk(W, **kw) for W in WIDTHS]
-    for other in got[1:]:
-        for a, b in zip(got[0], other):
-            assert a.tobytes() == b.tobytes()
-    return got[0]
-
 
 @pytest.mark.parametrize("name", sorted(CONFIGS))
 def test_walk_equals_every_node_and_the_oracle_for_every_width(shim, oracle, name):
@@ -114,7 +80,7 @@ def test_walk_equals_every_node_and_the_oracle_for_every_width(shim, oracle, nam
     model = Model(shim, kw, max_clock)
     cc, faults, _ = model.counts()
     assert not faults.any() and cc.max() <= model.lcap
-    out, heads, pre = same_for_every_width(model)
+    out, heads, pre = model.same_for_every_width()
     assert HEAD_DTYPE.itemsize == 40 and out.dtype.itemsize == 32
     assert (pre == cc).all()  # every history is a prefix of its chain
     assert (heads["length"] == cc.max(axis=1)).all() and (heads["ref_node"] == cc.argmax(axis=1)).all()
@@ -138,9 +104,9 @@ def test_walk_equals_every_node_and_the_oracle_for_every_width(shim, oracle, nam
     if "epochs" in name or "rotating" in name:  # the epoch-id hash was taken: more commits than an epoch holds
         assert cc.max() > kw["commands_per_epoch"]
     # heads alone, and a capacity below the chains: the heads stay, the entries are cut
-    _, heads_only, _ = same_for_every_width(model, entries=False, prefix=False)
+    _, heads_only, _ = model.same_for_every_width(entries=False, prefix=False)
     assert heads_only.tobytes() == heads.tobytes()
-    short, heads_short, _ = same_for_every_width(model, cap=5)
+    short, heads_short, _ = model.same_for_every_width(cap=5)
     assert heads_short.tobytes() == heads.tobytes() and short.tobytes() == np.ascontiguousarray(out[:, :5]).tobytes()
     model.close()
 
@@ -148,14 +114,14 @@ def test_walk_equals_every_node_and_the_oracle_for_every_width(shim, oracle, nam
 def test_ids_outside_the_pool_stop_the_walk(shim):
     model = Model(shim, dict(num_nodes=4), 1000)
     cc, _, nblocks = model.counts()
-    out0, heads0, _ = same_for_every_width(model)
+    out0, heads0, _ = model.same_for_every_width()
     assert heads0["length"].min() > 12
     refs = heads0["ref_node"]
     # (instance, entry, value): 0, just above the block count, far outside the state array, and at entry 0 / at a seam of W = 4 and 8
     edits = [(0, 6, 0), (1, 8, int(nblocks[1]) + 1), (2, 0, 0xfffffff0)]
     for i, k, v in edits:
         model.log(i, int(refs[i]), k, v)
-    out, heads, pre = same_for_every_width(model)
+    out, heads, pre = model.same_for_every_width()
     for i, k, v in edits:
         assert heads[i]["length"] == k + 1 and heads[i]["flags"] == BAD_ID and heads[i]["ref_node"] == refs[i]
         assert heads[i]["block_hash"] == heads[i]["state"] == heads[i]["qc_hash"] == heads[i]["num_votes"] == 0
@@ -166,7 +132,7 @@ def test_ids_outside_the_pool_stop_the_walk(shim):
             assert pre[i, q] == (k + 1 if q == refs[i] else min(k, cc[i, q])), (i, q)
     # the largest id of the pool is one of the pool's
     model.log(0, int(refs[0]), 6, int(nblocks[0]))
-    _, heads, _ = same_for_every_width(model)
+    _, heads, _ = model.same_for_every_width()
     assert heads[0]["length"] == heads0[0]["length"] and heads[0]["flags"] in (0, 2)
     model.close()
 
@@ -174,7 +140,7 @@ def test_ids_outside_the_pool_stop_the_walk(shim):
 def test_node_prefix_is_the_first_differing_entry(shim):
     model = Model(shim, dict(num_nodes=4), 1000)
     cc, _, _ = model.counts()
-    _, heads0, pre0 = same_for_every_width(model)
+    _, heads0, pre0 = model.same_for_every_width()
     assert (pre0 == cc).all()
     for i in range(model.m):
         ref = int(heads0["ref_node"][i])
@@ -184,7 +150,7 @@ def test_node_prefix_is_the_first_differing_entry(shim):
         for q, k in edits:
             old = model.log(i, q, k)
             model.log(i, q, k, old + 1)  # (another id)
-        out, heads, pre = same_for_every_width(model)
+        out, heads, pre = model.same_for_every_width()
         assert heads[i].tobytes() == heads0[i].tobytes()  # the chain is the reference node's: untouched
         want = cc[i].copy()
         for q, k in edits:
@@ -195,9 +161,9 @@ def test_node_prefix_is_the_first_differing_entry(shim):
 
 def test_a_faulted_instance_is_skipped(shim):
     model = Model(shim, dict(num_nodes=4), 600)
-    out0, heads0, pre0 = same_for_every_width(model)
+    out0, heads0, pre0 = model.same_for_every_width()
     model.L.rhm_set_fault(model.h, 1, 1 << 3)
-    out, heads, pre = same_for_every_width(model)
+    out, heads, pre = model.same_for_every_width()
     assert not heads[1].tobytes().strip(b"\0") and not out[1].tobytes().strip(b"\0") and not pre[1].any()
     for i in (0, 2):
         assert out[i].tobytes() == out0[i].tobytes() and heads[i].tobytes() == heads0[i].tobytes() and (pre[i] == pre0[i]).all()
@@ -208,7 +174,7 @@ def test_an_empty_chain_gives_zeros(shim):
     model = Model(shim, dict(num_nodes=4), 5)
     cc, _, _ = model.counts()
     assert not cc.any()
-    out, heads, pre = same_for_every_width(model)
+    out, heads, pre = model.same_for_every_width()
     assert not heads.tobytes().strip(b"\0") and not out.tobytes().strip(b"\0") and not pre.any()
     model.close()
 

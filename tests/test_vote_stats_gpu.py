@@ -15,21 +15,12 @@ import pytest
 
 import vote_stats_cases as cases
 import vote_stats_reference as ref
-from support import amd, oracle_cfg, plain, same  # noqa: F401
+from support import amd, device_batch, oracle_cfg, plain, same  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 pytestmark = pytest.mark.gpu
 BINNINGS = ((None, None), (7, 5))
-
-
-def device_batch(amd, kw, seeds, **extra):
-    """The plain device batch of an oracle configuration `kw` (the reference CLI defaults for everything else)."""
-    kw = dict(kw)
-    n = kw.pop("num_nodes")
-    part = (kw.pop("partition_size"), kw.pop("partition_start"), kw.pop("partition_end")) if "partition_size" in kw else None
-    ps = amd.ParamSet(drop_per_million=kw.pop("drop_per_million", 0), partition=part)
-    return plain(amd, np.asarray(list(seeds), dtype=np.uint64), n, ps, **kw, **extra)
 
 
 def check(res, instances, n, rights, binnings=BINNINGS, **groups):

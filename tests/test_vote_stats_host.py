@@ -15,51 +15,30 @@ import pytest
 
 import vote_stats_cases as cases
 import vote_stats_reference as ref
-from support import build_shim
+from support import ModelBase, build_pool_walk_shim
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "vote_stats_host_model.cpp")
-WIDTHS = (1, 7, 64)
 
 
-@pytest.fixture(scope="module")
-def shim(tmp_path_factory):
-    L = build_shim(tmp_path_factory.mktemp("vt_host"), "vote_stats_host_model.cpp", "libvt_hostmodel.so", "-ffp-contract=off", "-pthread", "-w")
+def load_shim(tmp_dir):
+    L = build_pool_walk_shim(tmp_dir, "vote_stats_host_model.cpp", "libvt_hostmodel.so", "vtm")
     vp, u32 = C.c_void_p, C.c_uint32
-    L.vtm_create.argtypes = [vp, vp, C.c_size_t, C.c_int64, u32, vp]
-    L.vtm_create.restype = vp
-    L.vtm_destroy.argtypes = [vp]
     L.vtm_counts.argtypes = [vp, vp, vp, vp]
     L.vtm_walk.argtypes = [vp, u32, u32, u32, vp, vp, vp, vp, vp]
     L.vtm_walk.restype = C.c_int
-    L.vtm_chain.argtypes = [vp, u32, vp, vp]
-    L.vtm_log.argtypes = [vp, u32, u32, u32, C.c_int, u32]
-    L.vtm_log.restype = u32
-    L.vtm_set_fault.argtypes = [vp, u32, u32]
     L.vtm_clear_voters.argtypes = [vp, u32, u32]
     L.vtm_clear_voters.restype = u32
     return L
 
 
-class Model:
-    def __init__(self, L, kw, max_clock, seeds):
-        from librabft_simulator_amd import _lib
-        self.L = L
-        cfg = _lib.LbftConfig()
-        defaults = dict(mean=10.0, variance=4.0, commands_per_epoch=30000, target_commit_interval=100000, delta=20, gamma=2.0, lambda_=0.5)
-        for k, v in {**defaults, **kw}.items():
-            if k == "voting_rights":
-                self._rights = np.ascontiguousarray(v, dtype=np.uint64)
-                cfg.voting_rights = self._rights.ctypes.data_as(C.POINTER(C.c_uint64))
-            else:
-                setattr(cfg, k, v)
-        info = np.zeros(4, dtype=np.uint32)
-        seeds = np.ascontiguousarray(list(seeds), dtype=np.uint64)
-        self.h = L.vtm_create(C.byref(cfg), seeds.ctypes.data, len(seeds), max_clock, 4, info.ctypes.data)
-        assert self.h, "the host model refused the configuration"
-        self.m = len(seeds)
-        self.n, self.lcap, self.bcap, self.cls = (int(x) for x in info)
-        self.rights = kw.get("voting_rights")
+@pytest.fixture(scope="module")
+def shim(tmp_path_factory):
+    return load_shim(tmp_path_factory.mktemp("vt_host"))
+
+
+class Model(ModelBase):
+    PREFIX = "vtm"
 
     def counts(self):
         cc = np.zeros((self.m, self.n), dtype=np.uint32)
@@ -80,25 +59,6 @@ class Model:
         assert check[0] == 0, "the walk read %d block records whose id it had not checked" % check[0]
         assert check[1] == 0, "the membership rule differs from set membership on %d blocks" % check[1]
         return margin, votes, nodes, stats
-
-    def chain(self, i):
-        r, length = C.c_uint32(), C.c_uint32()
-        self.L.vtm_chain(self.h, i, C.byref(r), C.byref(length))
-        return r.value, length.value
-
-    def log(self, i, q, k, value=None):
-        return self.L.vtm_log(self.h, i, q, k, 0 if value is None else 1, 0 if value is None else value)
-
-    def close(self):
-        self.L.vtm_destroy(self.h)
-
-
-def same_for_every_width(model, **kw):
-    got = [model.walk(W, **kw) for W in WIDTHS]
-    for other in got[1:]:
-        for a, b in zip(got[0], other):
-            assert a.tobytes() == b.tobytes()
-    return got[0]
 
 
 def equal(got, want):
@@ -143,7 +103,7 @@ def test_walk_equals_the_reference_for_every_width(shim, oracle, name):
     assert nblocks.tolist() == [i["blocks"] for i in instances] and cc.max(axis=1).tolist() == [i["length"] for i in instances]
     lengths = sum(i["length"] for i in instances)
     for width, bins in ((None, None), (7, 5)):
-        got = same_for_every_width(model, width=width, bins=bins)
+        got = model.same_for_every_width(width=width, bins=bins)
         equal(got, cases.expected(instances, model.n, model.rights, width, bins))
         ref.identities(*got, lengths_sum=[lengths], unit=model.rights is None)
     margin, votes, nodes, stats = got
@@ -167,9 +127,9 @@ def test_ids_outside_the_pool_end_the_chain(shim):
         nb = int(nblocks[0])
         r, length = model.chain(0)
         assert length > 71
-        _, votes0, nodes0, stats0 = same_for_every_width(model)
+        _, votes0, nodes0, stats0 = model.same_for_every_width()
         model.log(0, r, k, nb + 1 if value is None else value)
-        margin, votes, nodes, stats = same_for_every_width(model)  # (asserts: no read of an unchecked record, for every width)
+        margin, votes, nodes, stats = model.same_for_every_width()  # (asserts: no read of an unchecked record, for every width)
         # entries 0 .. k - 1 are the chain: each has a certificate of three votes; the pool is sorted against that chain
         assert stats[0, 4 * ref.VOTES:4 * ref.VOTES + 2].tolist() == [k, 3 * k] and stats[0, 4 * ref.SKIPPED] == max(k - 1, 0)
         assert stats[0, 4 * ref.BLOCKS + 1] == nb == k + stats[0, 4 * ref.ORPHANED + 1] + stats[0, 4 * ref.PENDING + 1]
@@ -183,10 +143,10 @@ def test_ids_outside_the_pool_end_the_chain(shim):
 def test_a_chain_entry_without_voters_gives_no_vote_sample(shim):
     model = Model(shim, dict(num_nodes=4), 1000, [1, 2])
     r, length = model.chain(1)
-    _, votes0, nodes0, stats0 = same_for_every_width(model)
+    _, votes0, nodes0, stats0 = model.same_for_every_width()
     b = model.log(1, r, 9)
     assert model.L.vtm_clear_voters(model.h, 1, b) == 3
-    margin, votes, nodes, stats = same_for_every_width(model)
+    margin, votes, nodes, stats = model.same_for_every_width()
     for f in (ref.VOTES, ref.WEIGHT, ref.MARGIN):
         assert stats[0, 4 * f] == stats0[0, 4 * f] - 1
     assert stats[0, 4 * ref.VOTES + 1] == stats0[0, 4 * ref.VOTES + 1] - 3 and votes[0, 3] == votes0[0, 3] - 1
@@ -202,9 +162,9 @@ def test_a_faulted_instance_is_skipped(shim, oracle):
     seeds = list(seeds)[:3]
     model = Model(shim, kw, max_clock, seeds)
     instances = cases.oracle_instances(oracle, kw, max_clock, seeds)
-    equal(same_for_every_width(model), cases.expected(instances, 4, None))
+    equal(model.same_for_every_width(), cases.expected(instances, 4, None))
     model.L.vtm_set_fault(model.h, 1, 1 << 3)
-    got = same_for_every_width(model)
+    got = model.same_for_every_width()
     equal(got, cases.expected(instances, 4, None, faults=[0, 8, 0]))
     assert got[3][0, 4 * ref.BLOCKS] == 2
     model.close()

@@ -2,28 +2,14 @@
 // kernel logic on the host (oracle/host_model_common.h; networks above 32 nodes as the run-time-generic class on the planner's own
 // capacities), then every instance's chain and block pool walked the way lbft_k_ps_votes (csrc/lbft_paramsets.hip) walks them -- the
 // node pass, the chain pass, the pool pass, the same steps in the same order over csrc/lbft_vote_rules.h -- with the chunk width W a
-// parameter: a lane is an array element, a shuffle an index, a ballot a loop.  Every read of a block record goes through rec(), which
-// counts the reads whose id was not checked against the pool first: the walk must give 0.  The pool pass also states the membership rule
-// (one gather by ledger depth) against set membership in the chain and counts the blocks on which the two differ: 0 as well.  The state
-// stays in the handle, so a test can edit log entries, voter words and fault words and walk again.
+// parameter: a lane is an array element, a shuffle an index, a ballot a loop.  The model, its accessors and the shared steps of the
+// walk are tests/pool_walk_host.h's; every read of a block record goes through its counted reader: the walk must give 0.  The pool pass
+// also holds the membership rule (one gather by ledger depth) against set membership in the chain and counts the blocks on which the two
+// differ: 0 as well.  The state stays in the handle, so a test can edit log entries, voter words and fault words and walk again.
 // With -DVTM_MAIN the file is a program of its own (for a run under the address and undefined-behaviour sanitizers).
 #include <set>
-#include <thread>
-#include <vector>
 
-#include "../oracle/host_model_common.h"
-#include "../librabft_simulator_amd/csrc/lbft_chain_rules.h"
-#include "../librabft_simulator_amd/csrc/lbft_record_hash_rules.h"
-#include "../librabft_simulator_amd/csrc/lbft_vote_rules.h"
-
-using namespace lbft;
-
-struct VtModel {
-  TwinBatch tb;
-  std::vector<u32> state;
-  size_t m;
-  int cls;
-};
+#include "pool_walk_host.h"
 
 struct VtOut {
   u32 bin_width, bins;
@@ -39,35 +25,24 @@ static void walk_instance(const Params& p, u32* state, u32 i, u32 W, VtOut& o) {
   Sim s(p, state, i);
   if (s.ld(I_FAULT) != 0) return;
   // node pass
-  u64 best = 0;
-  for (u32 c0 = 0; c0 < n; c0 += W)
-    for (u32 sl = 0; sl < W && c0 + sl < n; sl++) best = chn_ref_max(best, chn_ref_key(chn_commits(s.nfm(c0 + sl, NF_NCOMMITS), lcap), c0 + sl));
-  const u32 ref = chn_ref_node(best), row = lg + ref * lcap;
-  const u32 nb = s.ld(I_NBLOCKS) < p.bcap ? s.ld(I_NBLOCKS) : p.bcap;
-  auto rec = [&](u32 b, u32 f) -> u32 {
-    if (!rh_valid_id(b, nb)) { o.unchecked++; return 0; }
-    return s.bf(b, f);
-  };
+  const CwChain ch = cw_chain_of(s, n, lcap);
+  const u32 row = lg + ch.ref * lcap, nb = cw_pool_blocks(s, p);
+  const CwRec rec{s, nb, o.unchecked};
   // chain pass
-  u32 L = chn_ref_len(best);
+  u32 L = ch.L;
   u32 carry_r = 0, carry_e = 0, tip_r = 0, tip_e = 0;
-  struct Lane { u32 y, round, epoch, votes, weight; };
+  struct Lane { u32 round, epoch, votes, weight; };
   for (u32 c0 = 0; c0 < L; c0 += W) {
     std::vector<Lane> ln(W, Lane{});
-    const u32 inblk = L - c0 < W ? L - c0 : W;
-    u32 jb = W;
-    for (u32 sl = 0; sl < W; sl++) {
-      const u32 k = c0 + sl;
-      ln[sl].y = k < L ? s.ld(row + k) : 0;
-      if (k < L && !rh_valid_id(ln[sl].y, nb) && jb == W) jb = sl;
-    }
-    const u32 nv = jb < inblk ? jb : inblk;
+    const CwChunk ck = cw_chunk(s, row, c0, L, nb, W);
+    const u32 nv = ck.nv;
     for (u32 sl = 0; sl < nv; sl++) {
       Lane& l = ln[sl];
-      l.round = rec(l.y, B_ROUND); l.epoch = rec(l.y, B_EPOCH);
+      const u32 y = ck.y[sl];
+      l.round = rec(y, B_ROUND); l.epoch = rec(y, B_EPOCH);
       const u32 shift = vt_rights_shift(l.epoch, rot, n);
       for (u32 w = 0; w < mw; w++) {
-        const u32 v = rec(l.y, rh_voter_field(w, mw)) & rh_author_bits(w, n);
+        const u32 v = rec(y, rh_voter_field(w, mw)) & rh_author_bits(w, n);
         l.votes += (u32)__builtin_popcount(v);
         for (u32 m = v; m; m &= m - 1u) {
           const u32 a = 32 * w + (u32)ctz32(m);
@@ -91,7 +66,7 @@ static void walk_instance(const Params& p, u32* state, u32 i, u32 W, VtOut& o) {
     }
     carry_r = ln[W - 1].round; carry_e = ln[W - 1].epoch;
     if (nv) { tip_r = ln[nv - 1].round; tip_e = ln[nv - 1].epoch; }
-    if (nv < inblk) L = c0 + nv;
+    if (cw_ends(ck)) L = c0 + nv;
   }
   // pool pass
   std::set<u32> on_chain;  // (the statement the membership rule is held to, not the kernel's way)
@@ -100,11 +75,10 @@ static void walk_instance(const Params& p, u32* state, u32 i, u32 W, VtOut& o) {
   for (u32 b0 = 1; b0 <= nb; b0 += W)
     for (u32 sl = 0; sl < W && b0 + sl <= nb; sl++) {
       const u32 b = b0 + sl;
-      const u32 author = rec(b, B_LINK) >> 16, round = rec(b, B_ROUND), epoch = rec(b, B_EPOCH), slot = vt_chain_slot(rec(b, B_DEPTH), L);
+      const u32 author = rec(b, B_LINK) >> 16, round = rec(b, B_ROUND), epoch = rec(b, B_EPOCH);
       bool certified = false;
       for (u32 w = 0; w < mw; w++) certified |= (rec(b, rh_voter_field(w, mw)) & rh_author_bits(w, n)) != 0;
-      const u32 at = slot < L ? s.ld(row + slot) : 0;
-      const bool member = vt_member(slot, L, at, b);
+      const bool member = cw_pool_member(s, row, rec(b, B_DEPTH), L, b);
       if (member != (on_chain.count(b) != 0)) o.membership++;
       const u32 cls = vt_classify(member, L != 0, epoch, round, tip_e, tip_r);
       if (author < n) {
@@ -117,70 +91,21 @@ static void walk_instance(const Params& p, u32* state, u32 i, u32 W, VtOut& o) {
   gs_stat_add(o.st[VT_PENDING], pending); gs_stat_add(o.st[VT_CERTIFIED_OFF], certified_off);
 }
 
-// Networks above 32 nodes: the planner's capacities for a run to max_clock without the calendar queue, stepped as the generic class.
-static int setup_large(const lbft_config* base, size_t m, int64_t max_clock, TwinBatch& t) {
-  lbft_config c = *base;
-  c.queue_capacity = c.snapshot_capacity = c.block_capacity = c.log_capacity = 0;
-  Params& p = t.p;
-  if (fill_params(&c, m, p, t.weights) != LBFT_OK) return -1;
-  p.weights = t.weights.data();
-  bool relayout;
-  std::string err;
-  if (plan_layout(c, p, max_clock, 0, false, false, 0, ~0ull, PlanKnobs(), false, relayout, err) != LBFT_OK) return -1;
-  attach_tables(p, c.delta, c.gamma, t.dur, t.leaders);
-  p.ql = 0;
-  set_tile_width(p, layout_tile_width(p));
-  return K_GENERIC;
-}
-
 extern "C" {
 
-// A plain batch of `base` run to max_clock; NULL on a bad argument.  info: num_nodes, log capacity, block capacity, kernel class.
-void* vtm_create(const lbft_config* base, const uint64_t* seeds, size_t m, int64_t max_clock, uint32_t threads, uint32_t* info) {
-  const u32 n = base->num_nodes;
-  if (n == 0 || n > LBFT_MAX_NODES) return nullptr;
-  VtModel* h = new VtModel;
-  h->m = m;
-  h->cls = n <= 32 ? setup_twin_batch(base, nullptr, 0, (base->quirks & 1u) ? 0 : (16 * n < 64 ? 64 : 16 * n), m, max_clock, h->tb) : setup_large(base, m, max_clock, h->tb);
-  if (h->cls < 0) { delete h; return nullptr; }
-  const Params& p = h->tb.p;
-  h->state.assign(state_words(p), 0);
-  if (threads == 0) threads = 1;
-  auto worker = [&](u32 tid) {
-    for (size_t i = tid; i < m; i += threads) {
-      { Sim s0(p, h->state.data(), (u32)i); s0.init(seeds[i]); }
-      if (h->cls == K_SMALL) { SimT<K_SMALL> s(p, h->state.data(), (u32)i); run_one(s, p, 0); }
-      else if (h->cls == K_MID) { SimT<K_MID> s(p, h->state.data(), (u32)i); run_one(s, p, 0); }
-      else { Sim s(p, h->state.data(), (u32)i); run_one(s, p, 0); }
-    }
-  };
-  std::vector<std::thread> ts;
-  for (u32 t = 1; t < threads; t++) ts.emplace_back(worker, t);
-  worker(0);
-  for (auto& t : ts) t.join();
-  if (info) { info[0] = n; info[1] = p.lcap; info[2] = p.bcap; info[3] = (u32)h->cls; }
-  return h;
-}
-void vtm_destroy(void* handle) { delete static_cast<VtModel*>(handle); }
-
-// commit_counts [m][n] (as stored, not clamped), faults [m], nblocks [m]
-void vtm_counts(void* handle, uint32_t* commit_counts, uint32_t* faults, uint32_t* nblocks) {
-  VtModel* h = static_cast<VtModel*>(handle);
-  const Params& p = h->tb.p;
-  for (size_t i = 0; i < h->m; i++) {
-    Sim s(p, h->state.data(), (u32)i);
-    faults[i] = s.ld(I_FAULT);
-    nblocks[i] = s.ld(I_NBLOCKS);
-    for (u32 q = 0; q < p.n; q++) commit_counts[i * p.n + q] = s.nfm(q, NF_NCOMMITS);
-  }
-}
+void* vtm_create(const lbft_config* base, const uint64_t* seeds, size_t m, int64_t max_clock, uint32_t threads, uint32_t* info) { return pw_create(base, seeds, m, max_clock, threads, info, true); }
+void vtm_destroy(void* handle) { pw_destroy(handle); }
+void vtm_counts(void* handle, uint32_t* commit_counts, uint32_t* faults, uint32_t* nblocks) { pw_counts(handle, commit_counts, faults, nblocks, nullptr, nullptr); }
+void vtm_chain(void* handle, uint32_t inst, uint32_t* ref, uint32_t* length) { pw_chain(handle, inst, ref, length); }
+uint32_t vtm_log(void* handle, uint32_t inst, uint32_t node, uint32_t k, int set, uint32_t value) { return pw_log(handle, inst, node, k, set, value); }
+void vtm_set_fault(void* handle, uint32_t inst, uint32_t value) { pw_set_fault(handle, inst, value); }
 
 // Every instance walked in chunks of W lanes (1 .. 64), one group: margin_hist [bins], votes_hist [n + 1], node_table [n * 3],
 // stats [32], all zeroed here first.  check[0] = block-record reads with an unchecked id, check[1] = pool blocks on which the
 // membership rule and set membership differ (0 and 0 are right).  -> 0, < 0 on a bad argument
 int vtm_walk(void* handle, uint32_t W, uint32_t bin_width, uint32_t bins, uint64_t* margin_hist, uint64_t* votes_hist, uint64_t* node_table,
              uint64_t* stats, uint64_t* check) {
-  VtModel* h = static_cast<VtModel*>(handle);
+  PwModel* h = static_cast<PwModel*>(handle);
   if (!h || W == 0 || W > 64 || bin_width == 0 || bins == 0 || !margin_hist || !votes_hist || !node_table || !stats || !check) return -1;
   const Params& p = h->tb.p;
   VtOut o = {};
@@ -197,35 +122,10 @@ int vtm_walk(void* handle, uint32_t W, uint32_t bin_width, uint32_t bins, uint64
   return 0;
 }
 
-// The reference node and the clamped chain length of an instance (the node pass)
-void vtm_chain(void* handle, uint32_t inst, uint32_t* ref, uint32_t* length) {
-  VtModel* h = static_cast<VtModel*>(handle);
-  const Params& p = h->tb.p;
-  Sim s(p, h->state.data(), inst);
-  u64 best = 0;
-  for (u32 j = 0; j < p.n; j++) best = chn_ref_max(best, chn_ref_key(chn_commits(s.nfm(j, NF_NCOMMITS), p.lcap), j));
-  *ref = chn_ref_node(best); *length = chn_ref_len(best);
-}
-// Entry k of a node's log: returns it, and stores `value` there when `set` is not 0
-uint32_t vtm_log(void* handle, uint32_t inst, uint32_t node, uint32_t k, int set, uint32_t value) {
-  VtModel* h = static_cast<VtModel*>(handle);
-  const Params& p = h->tb.p;
-  Sim s(p, h->state.data(), inst);
-  const u32 w = p.off_log + node * p.lcap + k;
-  const u32 old = s.ld(w);
-  if (set) s.st(w, value);
-  return old;
-}
-void vtm_set_fault(void* handle, uint32_t inst, uint32_t value) {
-  VtModel* h = static_cast<VtModel*>(handle);
-  Sim s(h->tb.p, h->state.data(), inst);
-  s.st(I_FAULT, value);
-}
 // Empties the voter words of pool block b -> the votes it held
 uint32_t vtm_clear_voters(void* handle, uint32_t inst, uint32_t b) {
-  VtModel* h = static_cast<VtModel*>(handle);
-  const Params& p = h->tb.p;
-  Sim s(p, h->state.data(), inst);
+  const Params& p = static_cast<PwModel*>(handle)->tb.p;
+  Sim s = pw_sim(handle, inst);
   u32 votes = 0;
   for (u32 w = 0; w < p.mw; w++) {
     votes += (u32)__builtin_popcount(s.bf(b, rh_voter_field(w, p.mw)) & rh_author_bits(w, p.n));
